@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — MSA -> EDS input MB/s on MI355X (BASELINE.json metric), with the HBM roofline of the
-dominant kernel and a CPU baseline timed in the same run.
+dominant kernel and (--full) a CPU baseline timed in the same run.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full pass of the hot path (edsx_msa_plan_device + edsx_msa_emit_device: row index,
@@ -13,6 +13,19 @@ With N ranks (--scaling strong, the default: BASELINE configs[4] is ONE alignmen
 1000 x 100 Mb alignment is range-partitioned into N column slabs of 100/N Mb; every rank transforms its own slab
 and the boundary segments are stitched over RCCL inside the step (fixed-size tensor collectives).
 --scaling weak keeps 100 Mb columns per rank (an N x 100 Mb alignment).
+
+A plain run sets up, warms up, times the steps (per-kernel HIP-event times and the roofline of the dominant kernel come
+from those same steps), writes the outputs if --dump-outputs is given and prints one JSON line.  --full adds what takes
+work of its own after the timed region: the sampled check of the outputs against the CPU oracle ("verify"), the same
+alignment with aligned rows ("aligned_rows") and the single-core CPU baseline ("cpu_baseline"); without it these three
+fields are null.
+
+--dump-outputs DIR writes what the last timed step computed as float32/float64 .npy files (rank r of N > 1 appends
+_rank<r> to every name): sizes.npy = [.eds bytes, .seds bytes]; eds.npy / seds.npy = the output bytes, whole when they
+fit DUMP_WHOLE bytes, else a fixed sample of that many bytes (the first and last quarter of it from the two ends of the
+output, the middle half from sorted offsets drawn with numpy's default_rng(DUMP_SEED) in [k, n - k) - fixed by the
+output's size); eds_blocks.npy / seds_blocks.npy = per block of at most DUMP_BLOCKS equal blocks over the WHOLE output,
+[sum of the bytes, sum of byte * (offset in block + 1)] (exact integers).  About 34 MB at the default workload.
 """
 import argparse
 import json
@@ -24,6 +37,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md "HBM3E peak BW")
+DUMP_WHOLE = 4 << 20    # --dump-outputs: outputs up to this many bytes are written whole, larger ones as a sample this size
+DUMP_BLOCKS = 1 << 16   # --dump-outputs: the block digests cover the whole output in at most this many blocks
+DUMP_SEED = 12345
 
 
 def parse_args():
@@ -42,21 +58,27 @@ def parse_args():
     ap.add_argument("--context-len", type=int, default=0)
     ap.add_argument("--variant-fraction", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the output check against the CPU oracle (--verify), the aligned-rows "
+                         "repeat (--aligned-probe) and the CPU baseline (--cpu-baseline-mb); a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32/float64; a fixed sample of "
+                         "large outputs, see the module docstring)")
     ap.add_argument("--cpu-baseline-mb", type=float, default=3000.0,
-                    help="size of the CPU-baseline sample in MB (0 = skip)")
+                    help="--full: size of the CPU-baseline sample in MB (0 = skip)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal on a one-GPU box: every rank uses cuda:0")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: take the multi-rank code path (process group, stitch, reductions) with WORLD_SIZE=1 too")
     ap.add_argument("--verify", type=int, default=1,
-                    help="N=1, context length 0: after the timed region compare sampled column windows of the outputs "
+                    help="--full, N=1, context length 0: after the timed region compare sampled column windows of the outputs "
                          "(spread over the whole width, incl. offsets beyond 4 GiB and the last columns) with the CPU "
                          "oracle (tests/fullsize_verify.py); 0 = skip")
     ap.add_argument("--row-align", type=int, default=0,
                     help="lay the synthetic rows out with blank-padded headers so that every row starts on a multiple of "
                          "this many bytes (0: the plain FASTA image - the headline workload)")
     ap.add_argument("--aligned-probe", type=int, default=128,
-                    help="N=1: after the timed run repeat it on the same alignment laid out with rows on multiples of this many "
+                    help="--full, N=1: after the timed run repeat it on the same alignment laid out with rows on multiples of this many "
                          "bytes (what an upload that places the rows for the scan produces) and report it beside the headline "
                          "under \"aligned_rows\"; 0 = skip")
     ap.add_argument("--traffic-bytes", type=float, default=None,
@@ -98,6 +120,53 @@ def cpu_baseline(ctx, torch, rows, sample_mb, vfrac, seed, l):
             "host_cores": os.cpu_count(),
             "sample": "%d rows x %d columns (%.0f MB in, %.1f s), same generator and site fraction"
                       % (rows, cols, n / 1e6, dt)}
+
+
+def _sample(torch, v, n, cap):
+    """v[:n] as float32, whole when n <= cap, else cap bytes: both ends and sorted seeded offsets in between."""
+    import numpy as np
+    if n <= cap:
+        return v[:n].cpu().numpy().astype(np.float32)
+    k = cap // 4
+    mid = np.sort(np.random.default_rng(DUMP_SEED).integers(k, n - k, size=cap - 2 * k, dtype=np.int64))
+    idx = torch.from_numpy(mid).to(v.device)
+    return torch.cat([v[:k], v[idx], v[n - k:n]]).cpu().numpy().astype(np.float32)
+
+
+def _block_digest(torch, v, n, blocks):
+    """[sum of bytes, sum of byte * (offset in block + 1)] per block of ceil(n / blocks) bytes, over all of v[:n]."""
+    import numpy as np
+    bs = max(1, -(-n // blocks))
+    nb = -(-n // bs)
+    w = torch.arange(1, bs + 1, dtype=torch.int64, device=v.device)
+    per = max(1, (64 << 20) // bs)                            # blocks per chunk: bounds the int64 temporaries
+    parts = []
+    for b0 in range(0, nb, per):
+        b1 = min(nb, b0 + per)
+        c = v[b0 * bs:min(n, b1 * bs)].to(torch.int64)
+        full = c.numel() // bs
+        body = c[:full * bs].view(full, bs)
+        parts.append(torch.stack([body.sum(dim=1), (body * w).sum(dim=1)], dim=1))
+        if c.numel() > full * bs:
+            tail = c[full * bs:]
+            parts.append(torch.stack([tail.sum(), (tail * w[:tail.numel()]).sum()]).view(1, 2))
+    if not parts:
+        return np.zeros((0, 2), dtype=np.float64)
+    return torch.cat(parts).cpu().numpy().astype(np.float64)  # < 2^53: exact
+
+
+def dump_outputs(torch, d, out, rank, world):
+    """--dump-outputs: what the last timed step computed (module docstring)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    arrays = {"sizes": np.array([out["E"], out["Q"]], dtype=np.float64)}
+    for name, key in (("eds", "E"), ("seds", "Q")):
+        v, n = out[name], out[key]
+        arrays[name] = _sample(torch, v, n, DUMP_WHOLE // world)
+        arrays[name + "_blocks"] = _block_digest(torch, v, n, DUMP_BLOCKS // world)
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), arr)
 
 
 def main():
@@ -186,6 +255,8 @@ def main():
         n_total = float(t[0].item())
 
     info = ctx.msa_info()
+    if a.dump_outputs:
+        dump_outputs(torch, a.dump_outputs, out, rank, world)
     if rank == 0:
         total_in = n_total * a.steps
         value = total_in / dt / 1e6
@@ -223,13 +294,13 @@ def main():
                     "avg_kernel_ms": round(avg_ms, 4),
                     "algorithmic_bytes_per_launch": alg, "algorithmic_bytes": what}
         verify = None
-        if world == 1 and a.verify and l == 0:
+        if a.full and world == 1 and a.verify and l == 0:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             from fullsize_verify import verify_windows
             verify = verify_windows(ctx, torch, S, L, a.seed, a.variant_fraction, out["eds"], out["seds"],
                                     out["E"], out["Q"])
         aligned = None
-        if world == 1 and a.aligned_probe > 1 and a.row_align != a.aligned_probe:
+        if a.full and world == 1 and a.aligned_probe > 1 and a.row_align != a.aligned_probe:
             # The same cells with every row on a multiple of --aligned-probe bytes (blank-padded headers).  The scan's 16-byte
             # loads are then aligned; a FASTA image as it comes (the headline above) has every row at its own odd offset.
             first = (out["eds"][:out["E"]].clone(), out["seds"][:out["Q"]].clone(), out["E"], out["Q"])
@@ -265,7 +336,7 @@ def main():
                        "outputs_equal_headline_run": same}
             del msa2, first
         cpu = None
-        if world == 1 and a.cpu_baseline_mb > 0:
+        if a.full and world == 1 and a.cpu_baseline_mb > 0:
             cpu = cpu_baseline(ctx, torch, S, a.cpu_baseline_mb, a.variant_fraction, a.seed, l)
         line = {
             "metric": "msa2eds_input_MB_per_s", "value": round(value, 1), "unit": "MB/s",
