@@ -26,6 +26,11 @@ class VcfStats(ctypes.Structure):
                  "skipped_unsupported_sv", "variant_groups")]
 
 
+class VcfMultiInfo(ctypes.Structure):
+    _fields_ = [("partitioned", ctypes.c_int), ("fasta_windowed", ctypes.c_int)] + \
+               [(n, ctypes.c_uint64) for n in ("records_min", "records_max", "moved_line_bytes", "fasta_h2d_bytes_max")]
+
+
 class EdsStatistics(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_uint64) for n in ("n_symbols", "n_chars", "n_strings", "num_degenerate_symbols",
                                                 "total_change_size", "num_common_chars", "num_empty_strings",
@@ -123,6 +128,9 @@ def load_library():
     lib.edsx_multi_last_error.restype = ctypes.c_char_p
     lib.edsx_msa_transform_multi.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, P(_Buf), P(_Buf)]
     lib.edsx_multi_last_partition.argtypes = [ctypes.c_void_p, P(ctypes.c_int), P(ctypes.c_int)]
+    lib.edsx_vcf_transform_multi.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+                                             ctypes.c_size_t, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
+    lib.edsx_multi_last_vcf.argtypes = [ctypes.c_void_p, P(VcfMultiInfo)]
     lib.edsx_genvcf.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, P(_Buf), P(_Buf)]
     lib.edsx_msa_synth_size_aligned.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32]
     lib.edsx_msa_synth_size_aligned.restype = ctypes.c_size_t
@@ -178,6 +186,28 @@ class MultiGpu:
         p, c = ctypes.c_int(), ctypes.c_int()
         self._lib.edsx_multi_last_partition(self._h, ctypes.byref(p), ctypes.byref(c))
         return bool(p.value), int(c.value)
+
+    def vcf_transform(self, vcf, fasta, context_len=0):
+        """VCF + reference FASTA -> (eds, seds, stats) by reference-position ranges over the handle's GPUs; the same
+        outputs, stats and errors as Context.vcf_transform."""
+        e, s, st = _Buf(), _Buf(), VcfStats()
+        vcf, fasta = bytes(vcf), bytes(fasta)
+        rc = self._lib.edsx_vcf_transform_multi(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
+                                                ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
+        if rc != 0:
+            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
+        out = []
+        for b in (e, s):
+            out.append(ctypes.string_at(b.data, b.size) if b.size else b"")
+            self._lib.edsx_buf_free(ctypes.byref(b))
+        return out[0], out[1], {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+
+    def last_vcf(self):
+        """Of the last vcf_transform: partitioned, fasta_windowed, records_min / _max, moved_line_bytes,
+        fasta_h2d_bytes_max."""
+        info = VcfMultiInfo()
+        self._lib.edsx_multi_last_vcf(self._h, ctypes.byref(info))
+        return {n: (bool if n in ("partitioned", "fasta_windowed") else int)(getattr(info, n)) for n, _ in VcfMultiInfo._fields_}
 
 
 def synth_size(n_rows, n_cols, row_align=0):

@@ -267,6 +267,52 @@ int edsx_multi_last_partition(const edsx_multi* m, int* partitioned, int* chains
     return EDSX_OK;
 }
 
+int edsx_vcf_transform_multi(edsx_multi* m, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                             uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
+{
+    if (eds) { eds->data = nullptr; eds->size = 0; }
+    if (seds) { seds->data = nullptr; seds->size = 0; }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    edsx_multi_impl* mi = reinterpret_cast<edsx_multi_impl*>(m);
+    if (!mi) return EDSX_ERR_INVALID_PARAMETER;
+    VcfCounters c;
+    auto put = [&](bool groups) {          // edsx_vcf_transform's stats, on success and on failure
+        if (!stats) return;
+        stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
+        stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
+        if (groups) stats->variant_groups = c.variant_groups;
+    };
+    try {
+        mi->err.clear();
+        if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
+        HostBytes e, s;
+        try {
+            mi->m->vcf_transform(vcf, vcf_size, fasta, fasta_size, e, s, c);
+        } catch (...) { put(false); throw; }     // the reference counts while parsing, before it can throw
+        put(true);
+        if (context_len > 0) mi->m->leds_merge(e, s, context_len);      // as edsx_vcf_transform: counters already out
+        eds->size = e.size; eds->data = e.release();
+        seds->size = s.size; seds->data = s.release();
+        return EDSX_OK;
+    } catch (const FormatError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
+    } catch (const ParamError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
+    } catch (const LimitError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
+    } catch (const DeviceError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
+    } catch (const std::bad_alloc&) { mi->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
+    } catch (const std::exception& ex) { mi->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+}
+int edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out)
+{
+    const edsx_multi_impl* mi = reinterpret_cast<const edsx_multi_impl*>(m);
+    if (!mi || !out) return EDSX_ERR_INVALID_PARAMETER;
+    const VcfMultiInfo& v = mi->m->last_vcf();
+    out->partitioned = v.partitioned ? 1 : 0;
+    out->fasta_windowed = v.fasta_windowed ? 1 : 0;
+    out->records_min = v.records_min; out->records_max = v.records_max;
+    out->moved_line_bytes = v.moved_line_bytes; out->fasta_h2d_bytes_max = v.fasta_h2d_bytes_max;
+    return EDSX_OK;
+}
+
 void edsx_set_timing(edsx_ctx* ctx, int enabled) { if (ctx) ctx->msa.set_timing(enabled != 0); }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {

@@ -110,20 +110,21 @@ MsaLayout msa_layout(const uint8_t* f, size_t n)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// barrier of the rank threads, carrying the first failure to everyone
-// ---------------------------------------------------------------------------------------------------------------
-void RankBarrier::arrive(int rank, const std::string* failure)
-{
-    std::unique_lock<std::mutex> lk(mu_);
-    if (failure && (!failed_ || rank < failed_rank_)) { failed_ = true; msg_ = *failure; failed_rank_ = rank; }
-    const unsigned long g = gen_;
-    if (++count_ == n_) { count_ = 0; gen_++; cv_.notify_all(); }
-    else cv_.wait(lk, [&] { return gen_ != g; });
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // exchanges
 // ---------------------------------------------------------------------------------------------------------------
+void Exchange::all_gather_v(int rank, int world, const void* mine, size_t bytes, std::vector<uint8_t>& all, std::vector<u64>& sizes)
+{
+    sizes.assign(world, 0);
+    const u64 my = bytes;
+    all_gather(rank, &my, sizeof(my), sizes.data());
+    u64 cap = 1;
+    for (u64 s : sizes) cap = std::max(cap, s);
+    std::vector<uint8_t> pad(cap, 0);
+    if (bytes) std::memcpy(pad.data(), mine, bytes);
+    all.resize((size_t)cap * world);
+    all_gather(rank, pad.data(), cap, all.data());
+}
+
 namespace {
 
 class LocalExchange final : public Exchange {           // rank threads of one process, any device assignment
@@ -254,14 +255,6 @@ RowImage upload_row_image(const uint8_t* fasta, const MsaLayout& lay, u64 c0, u6
 // ---------------------------------------------------------------------------------------------------------------
 // MultiMsa
 // ---------------------------------------------------------------------------------------------------------------
-struct MultiMsa::Rank {
-    int device = 0;
-    MsaPipeline slab, mini;              // the slab's pipeline; boundary segments are recomputed through a second one
-    DevBuf d_img, d_eds, d_seds, d_mini;
-    std::vector<uint8_t> host_img;       // wrapped rows: the slab image is put together on the host
-    std::string error;
-};
-
 MultiMsa::MultiMsa(const std::vector<int>& devices, bool use_rccl) : devices_(devices)
 {
     if (devices.empty()) throw ParamError("edsx_multi_create: no devices");
@@ -332,13 +325,7 @@ void MultiMsa::run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& 
     const int N = world();
     Rank& me = *ranks_[r];
     std::string fail;
-    auto phase = [&](auto&& body) -> bool {               // false: some rank failed, leave
-        if (fail.empty() && !bar_->failed()) {
-            try { body(); } catch (const std::exception& ex) { fail = ex.what(); }
-        }
-        bar_->arrive(r, fail.empty() ? nullptr : &fail);
-        return !bar_->failed();
-    };
+    auto phase = [&](auto&& body) -> bool { return rank_phase(*bar_, r, fail, body); };    // false: some rank failed, leave
     const u64 S = lay.start.size(), L = lay.L;
     const u64 c0 = L * (u64)r / (u64)N, c1 = L * (u64)(r + 1) / (u64)N, ncols = c1 - c0;
     hipStream_t st = nullptr;
@@ -487,13 +474,7 @@ void MultiMsa::run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, 
     const int N = world();
     Rank& me = *ranks_[r];
     std::string fail;
-    auto phase = [&](auto&& body) -> bool {
-        if (fail.empty() && !bar_->failed()) {
-            try { body(); } catch (const std::exception& ex) { fail = ex.what(); }
-        }
-        bar_->arrive(r, fail.empty() ? nullptr : &fail);
-        return !bar_->failed();
-    };
+    auto phase = [&](auto&& body) -> bool { return rank_phase(*bar_, r, fail, body); };
     const u64 S = lay.start.size(), L = lay.L;
     const u64 c0 = L * (u64)r / (u64)N, c1 = L * (u64)(r + 1) / (u64)N, ncols = c1 - c0;
     hipStream_t st = nullptr;

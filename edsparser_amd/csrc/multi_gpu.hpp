@@ -13,8 +13,10 @@
 #pragma once
 
 #include "msa_device.hpp"
+#include "rank_barrier.hpp"
+#include "merge_device.hpp"
+#include "vcf_device.hpp"
 
-#include <condition_variable>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -57,19 +59,15 @@ public:
     virtual ~Exchange() = default;
     virtual void all_gather(int rank, const void* mine, size_t bytes, void* all) = 0;
     virtual const char* name() const = 0;
+    // variable sizes: a gather of the sizes, then one all_gather padded to the largest; piece r of `all` is
+    // [r * cap, r * cap + sizes[r]) with cap = all.size() / world
+    void all_gather_v(int rank, int world, const void* mine, size_t bytes, std::vector<uint8_t>& all, std::vector<u64>& sizes);
 };
 
-class RankBarrier {             // threads of one process; carries the first failure text to every rank
-public:
-    explicit RankBarrier(int n) : n_(n) {}
-    void arrive(int rank, const std::string* failure);     // returns when all n have arrived
-    bool failed() const { return failed_; }
-    std::string message() const { return msg_; }
-    void reset() { failed_ = false; msg_.clear(); }
-private:
-    int n_, count_ = 0; unsigned long gen_ = 0;
-    bool failed_ = false; std::string msg_; int failed_rank_ = -1;
-    std::mutex mu_; std::condition_variable cv_;
+// of the last MultiMsa::vcf_transform (edsx_vcf_multi_info)
+struct VcfMultiInfo {
+    bool partitioned = false, fasta_windowed = false;
+    u64 records_min = 0, records_max = 0, moved_line_bytes = 0, fasta_h2d_bytes_max = 0;
 };
 
 class MultiMsa {
@@ -83,10 +81,19 @@ public:
     bool partitioned() const { return partitioned_; }
     int chains() const { return chains_; }
     const char* exchange_name() const { return xch_ ? xch_->name() : "none"; }
+    // vcf2eds by position ranges (vcf_multi.hip): the outputs, counters and errors of VcfPipeline::run on the whole file
+    // (counters: as far as known when it throws)
+    void vcf_transform(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n, HostBytes& eds, HostBytes& seds,
+                       VcfCounters& stats);
+    // EDS text -> l-EDS: the LINEAR merge with defaults (compact) on the first device (vcf_transforms.cpp:735-755)
+    void leds_merge(HostBytes& eds, HostBytes& seds, uint32_t context_len);
+    const VcfMultiInfo& last_vcf() const { return vcf_info_; }
 private:
     struct Rank;
+    struct VcfShared;
     void run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& lay, HostBytes& eds, HostBytes& seds);
     void run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, HostBytes& eds, HostBytes& seds);
+    void run_rank_vcf(int r, VcfShared& sh);
     std::vector<int> devices_;
     std::vector<std::unique_ptr<Rank>> ranks_;
     std::unique_ptr<Exchange> xch_;
@@ -96,6 +103,17 @@ private:
     int chains_ = 0;
     // shared between the rank threads of one call
     std::vector<u64> piece_e_, piece_s_;
+    VcfMultiInfo vcf_info_;
+};
+
+struct MultiMsa::Rank {
+    int device = 0;
+    MsaPipeline slab, mini;              // the slab's pipeline; boundary segments are recomputed through a second one
+    DevBuf d_img, d_eds, d_seds, d_mini;
+    std::vector<uint8_t> host_img;       // wrapped rows: the slab image is put together on the host
+    std::string error;
+    std::unique_ptr<VcfPipeline> vcf;    // vcf_transform: created on first use
+    std::unique_ptr<MergePipeline> merge;   // (rank 0, context length > 0)
 };
 
 } // namespace edsx

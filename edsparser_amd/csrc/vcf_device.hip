@@ -31,8 +31,11 @@ namespace edsx {
 
 struct VcfDev {
     // reference
-    const uint8_t* fasta; u64 fasta_n; u64 seq_start, seq_size, lw;
+    const uint8_t* fasta; u64 fasta_n; u64 seq_start, seq_size, lw;   // fasta[i]: file byte cbase + i
     const uint8_t* refc; u64 refc_n; const u64* blkpre;
+    u64 cbase, wend;               // file offsets: refc / blkpre begin at cbase (seq_start, or the window's first byte), the
+                                   // device holds the file up to wend (fasta_n, or the window's end)
+    u64* oob;                      // window mode: a read outside the window is reported here (file offset | flags), not clamped
     // records
     u64 nrec; const u64* start; const u64* reflen; const u64* alt0; const u64* altstr_off; const uint8_t* altchars;
     const u64* pair0;          // per record: first (record,sample) pair; pair0[nrec] = #pairs
@@ -45,18 +48,22 @@ struct VcfDev {
 };
 
 __device__ __forceinline__ u64 fa_cpos(const VcfDev& d, u64 file_off)
-{   // position in refc of file offset file_off (>= seq_start); offsets past EOF map to refc_n
+{   // position in refc of file offset file_off (>= cbase); offsets past EOF map to refc_n
     if (file_off >= d.fasta_n) return d.refc_n;
-    const u64 rel = file_off - d.seq_start;
+    if (file_off < d.cbase || file_off >= d.wend) {      // (whole file: never)
+        if (d.oob && file_off != d.wend) *d.oob = file_off | (1ull << 63);
+        return d.refc_n;
+    }
+    const u64 rel = file_off - d.cbase;
     u64 c = d.blkpre[rel >> 8];
     // sequence bytes in [block start, file_off): eight bytes per (unaligned) load, line breaks counted with an exact
-    // SWAR zero-byte test; the buffer has 16 bytes of slack behind fasta_n, bytes at or past file_off are masked out
-    u64 f = d.seq_start + (rel & ~255ull);
+    // SWAR zero-byte test; the buffer has 16 bytes of slack behind wend, bytes at or past file_off are masked out
+    u64 f = rel & ~255ull;
     u64 breaks = 0;
-    while (f < file_off) {
+    while (f < rel) {
         u64 w;
         __builtin_memcpy(&w, d.fasta + f, 8);
-        const u64 left = file_off - f;
+        const u64 left = rel - f;
         const u64 keep = left >= 8 ? ~0ull : ((1ull << (8 * left)) - 1ull);
         const u64 a = w ^ 0x0a0a0a0a0a0a0a0aull, b = w ^ 0x0d0d0d0d0d0d0d0dull;
         const u64 nza = (((a & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | a) & 0x8080808080808080ull;   // high bit = byte != '\n'
@@ -64,7 +71,7 @@ __device__ __forceinline__ u64 fa_cpos(const VcfDev& d, u64 file_off)
         breaks += __builtin_popcountll(~(nza & nzb) & 0x8080808080808080ull & keep);
         f += 8;
     }
-    return c + (file_off - (d.seq_start + (rel & ~255ull))) - breaks;
+    return c + (rel - (rel & ~255ull)) - breaks;
 }
 
 // ---- reference stream ---------------------------------------------------------------------------
@@ -119,6 +126,43 @@ __global__ void k_fa_seq_bytes(const uint8_t* __restrict__ f, u64 from, const u6
     if ((threadIdx.x & 63) == 0 && c) atomicAdd((unsigned long long*)count, (unsigned long long)c);
 }
 
+// The same two passes over one slice [a, b) of the FASTA body (partitioned runs: every rank scans its slice; the slices'
+// results are put together on the host, vcf_multi.hip).  s[i] is file byte s0 + i, s0 = a - 1 (the byte in front of the
+// slice decides whether a '>' at a starts a line).  k_fa_slice_end: the first "\n>" with its '>' in [from, b).
+__global__ void k_fa_slice_end(const uint8_t* __restrict__ s, u64 s0, u64 from, u64 b, u64* __restrict__ rec_end)
+{
+    u64 best = ~0ull;
+    for (u64 i = from + blockIdx.x * (u64)blockDim.x + threadIdx.x; i < b; i += (u64)gridDim.x * blockDim.x)
+        if (s[i - s0] == '>' && s[i - 1 - s0] == '\n') { best = i; break; }
+    if (best != ~0ull) atomicMin((unsigned long long*)rec_end, (unsigned long long)best);
+}
+// [a, min(rec_end, b)): bytes that are not '\n' (k_fa_seq_bytes) and what breaks the line grid of a regular file: the
+// byte at (i - seq_start) % (lw + 1) == lw is '\n' and no other is; no '\r'.  A thread takes 16 consecutive bytes.
+// out[0] count, out[1] flags (1: '\r', 2: grid byte that is not '\n'), out[2] first '\n' off the grid
+__global__ void k_fa_slice_scan(const uint8_t* __restrict__ s, u64 s0, u64 a, u64 b, const u64* __restrict__ rec_end, u64 seq_start,
+                                u64 lw, u64* __restrict__ out)
+{
+    const u64 re = *rec_end, hi = re < b ? re : b, period = lw + 1;
+    u64 cnt = 0, flags = 0, off = ~0ull;
+    for (u64 c0 = a + 16 * (blockIdx.x * (u64)blockDim.x + threadIdx.x); c0 < hi; c0 += 16 * (u64)gridDim.x * blockDim.x) {
+        const u64 c1 = c0 + 16 < hi ? c0 + 16 : hi;
+        u64 m = (c0 - seq_start) % period;
+        for (u64 i = c0; i < c1; i++) {
+            const uint8_t ch = s[i - s0];
+            const bool grid = m == lw;
+            cnt += ch != '\n';
+            if (ch == '\r') flags |= 1;
+            if (grid && ch != '\n') flags |= 2;
+            if (!grid && ch == '\n' && i < off) off = i;
+            if (++m == period) m = 0;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long*)&out[0], (unsigned long long)cnt);
+    if (flags) atomicOr((unsigned long long*)&out[1], (unsigned long long)flags);
+    if (off != ~0ull) atomicMin((unsigned long long*)&out[2], (unsigned long long)off);
+}
+
 // ---- grouping -------------------------------------------------------------------------------------
 __global__ void k_rec_ends(const u64* __restrict__ start, const u64* __restrict__ reflen, u64 n, u64* __restrict__ ends)
 {
@@ -171,6 +215,7 @@ __global__ void k_grp_count(VcfDev d, GrpArrays a)
             if (gs + length > d.seq_size) length = d.seq_size - gs;
             cs = fa_cpos(d, d.seq_start + gs + gs / d.lw);
             spanlen = length < d.refc_n - cs ? length : d.refc_n - cs;
+            if (d.oob && spanlen < length) *d.oob = (d.seq_start + gs + gs / d.lw) | (1ull << 62);   // the window is too short
         }
         a.gs[g] = gs; a.spanlen[g] = spanlen; a.cs[g] = cs;
         u64 nraw = 1, chars = spanlen;
@@ -311,6 +356,7 @@ __global__ void k_grp_common(VcfDev d, GrpArrays a)
             if (cur + length > d.seq_size) length = d.seq_size - cur;
             const u64 c0 = fa_cpos(d, d.seq_start + cur + cur / d.lw);
             clen = length < d.refc_n - c0 ? length : d.refc_n - c0;
+            if (d.oob && clen < length) *d.oob = (d.seq_start + cur + cur / d.lw) | (1ull << 62);
         }
         a.commonlen[g] = clen;
         if (clen) { a.eds_len[g] += clen + 2; a.seds_len[g] += 3; }
@@ -1070,6 +1116,42 @@ bool VcfPipeline::index_device(const uint8_t* vcf, size_t n, hipStream_t st, std
     return !h.bad;
 }
 
+void fasta_head(const uint8_t* fasta, size_t fasta_n, u64& seq_start, u64& lw, u64& rest_from)
+{
+    size_t pos = 0;
+    std::string line;
+    bool eof = false;
+    if (!next_line(fasta, fasta_n, pos, line, &eof) || line.empty() || line[0] != '>')
+        throw FormatError("Invalid FASTA format: expected header line starting with '>'");
+    seq_start = eof ? fasta_n : pos;
+    if (!next_line(fasta, fasta_n, pos, line)) throw FormatError("FASTA file is empty");
+    lw = line.size();
+    rest_from = pos;
+}
+
+FaSlice VcfPipeline::fasta_slice(const uint8_t* fasta, u64 a, u64 b, u64 seq_start, u64 rest_from, u64 lw, hipStream_t st, u64& h2d)
+{
+    FaSlice r{~0ull, 0, 0, ~0ull};
+    h2d = 0;
+    if (a >= b) return r;
+    if (a == 0 || a < seq_start) throw ParamError("fasta_slice: the slice must lie behind the header line");
+    const u64 s0 = a - 1, n = b - s0;
+    d_slice_.ensure(n + 16);
+    slice_ctl_.ensure(8 * 8);
+    u64* ctl = slice_ctl_.as<u64>();
+    EDSX_HIP(hipMemcpyAsync(d_slice_.ptr, fasta + s0, n, hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemcpyAsync(ctl, &r, sizeof(r), hipMemcpyHostToDevice, st));
+    h2d = n;
+    const uint8_t* sl = d_slice_.as<uint8_t>();
+    const u64 from = std::max(a, rest_from);
+    if (from < b) hipLaunchKernelGGL(k_fa_slice_end, dim3(1024), dim3(256), 0, st, sl, s0, from, b, ctl + 0);
+    hipLaunchKernelGGL(k_fa_slice_scan, dim3(1024), dim3(256), 0, st, sl, s0, a, b, ctl + 0, seq_start, lw, ctl + 1);
+    EDSX_HIP(hipMemcpyAsync(&r, ctl, sizeof(r), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    return r;
+}
+
 void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n, HostBytes& eds,
                       HostBytes& seds, VcfCounters& stats, hipStream_t st, const VcfRange& range)
 {
@@ -1083,20 +1165,12 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         t_last = now;
     };
     stats = VcfCounters();
+    fasta_h2d_ = 0;
     // ---- FASTA metadata (:51-86)
     u64 seq_start, lw, seq_size, rest_from = 0;
-    {
-        size_t pos = 0;
-        std::string line;
-        bool eof = false;
-        if (!next_line(fasta, fasta_n, pos, line, &eof) || line.empty() || line[0] != '>')
-            throw FormatError("Invalid FASTA format: expected header line starting with '>'");
-        seq_start = eof ? fasta_n : pos;
-        if (!next_line(fasta, fasta_n, pos, line)) throw FormatError("FASTA file is empty");
-        lw = line.size();
-        seq_size = line.size();                                // + the later lines, counted on the device (below)
-        rest_from = pos;
-    }
+    fasta_head(fasta, fasta_n, seq_start, lw, rest_from);
+    seq_size = lw;                                             // + the later lines, counted on the device (below)
+    const FastaMeta* meta = range.fasta;
     mark("fasta metadata");
     // ---- VCF records (:690-712) and the unstable sort (:715-718)
     std::vector<VcfPart> parts;
@@ -1135,10 +1209,22 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     // line_width (UB), refuse instead
     if (lw == 0) throw FormatError("Invalid FASTA format: empty first sequence line");
 
-    // ---- reference stream on the device
-    d_fasta_.ensure(fasta_n + 16);
-    EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta, fasta_n, hipMemcpyHostToDevice, st));
-    const u64 body = fasta_n > seq_start ? fasta_n - seq_start : 0;
+    // ---- reference stream on the device: the whole file, or (a regular file in a partitioned run) the window of this
+    // position range, [off(cur0), off(end)) with 16 bytes of slack
+    const bool window = meta && meta->regular;
+    u64 up0 = 0, up1 = fasta_n;
+    if (window) {
+        auto off = [&](u64 p) { return seq_start + p + p / lw; };
+        const u64 p0 = std::min(range.cur0, meta->seq_size);
+        const u64 p1 = std::max(p0, std::min(range.next_start, meta->seq_size));
+        up0 = std::min<u64>(off(p0), fasta_n);
+        up1 = std::max(up0, std::min<u64>(off(p1) + 16, fasta_n));
+    }
+    const u64 up_n = up1 - up0, cbase = window ? up0 : seq_start;
+    d_fasta_.ensure(up_n + 16);
+    if (up_n) EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta + up0, up_n, hipMemcpyHostToDevice, st));
+    fasta_h2d_ = up_n;
+    const u64 body = window ? up_n : fasta_n > seq_start ? fasta_n - seq_start : 0;
     const u64 nblk = (body + 255) / 256;
     ctl_.ensure(8 * 32);
     u64* ctl = ctl_.as<u64>();
@@ -1149,26 +1235,33 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     hctl[0] = nblk; hctl[10] = ~0ull;
     hctl[12] = fasta_n;                                      // record end (atomicMin), [13] bytes of the later lines
     EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
-    if (rest_from < fasta_n) {
+    if (!meta && rest_from < fasta_n) {
         hipLaunchKernelGGL(k_fa_record_end, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), (u64)fasta_n, rest_from, ctl + 12);
         hipLaunchKernelGGL(k_fa_seq_bytes, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), rest_from, ctl + 12, ctl + 13);
     }
     if (nblk) {
-        hipLaunchKernelGGL(k_fa_count, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), (u64)fasta_n, seq_start,
-                           blkpre_.as<u64>(), nblk);
+        // (window: the buffer is the window, compacted from its first byte)
+        const u64 kn = window ? up_n : fasta_n, ks = window ? 0 : seq_start;
+        hipLaunchKernelGGL(k_fa_count, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), kn, ks, blkpre_.as<u64>(), nblk);
         exclusive_scan_u64(blkpre_.as<u64>(), blkpre_.as<u64>(), ctl + 0, ctl + 1, scan_tmp_.as<u64>(), st);
-        hipLaunchKernelGGL(k_fa_compact, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), (u64)fasta_n, seq_start,
-                           blkpre_.as<u64>(), nblk, refc_.as<uint8_t>());
+        hipLaunchKernelGGL(k_fa_compact, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), kn, ks, blkpre_.as<u64>(), nblk,
+                           refc_.as<uint8_t>());
     }
     EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     const u64 refc_n = nblk ? hctl[1] : 0;
-    seq_size += hctl[13];
+    seq_size = meta ? meta->seq_size : seq_size + hctl[13];
     mark("fasta upload, metadata, compaction");
 
     VcfDev d{};
-    d.fasta = d_fasta_.as<uint8_t>(); d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
+    d.fasta = d_fasta_.as<uint8_t>() + (cbase - up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
     d.refc = refc_.as<uint8_t>(); d.refc_n = refc_n; d.blkpre = blkpre_.as<u64>();
+    d.cbase = cbase; d.wend = up1; d.oob = window ? ctl + 20 : nullptr;          // (ctl[20] is zero from the upload above)
+    auto window_check = [&](u64 v) {
+        if (v) throw DeviceError("VCF reference window: read at file offset " + std::to_string(v & ((1ull << 62) - 1)) +
+                                 " outside the window [" + std::to_string(up0) + ", " + std::to_string(up1) + ") (flags " +
+                                 std::to_string(v >> 62) + ")");
+    };
     d.nrec = nrec; d.cur0 = range.cur0;
 
     u64 cur = range.cur0, ngrp = 0, E = 0, Q = 0;
@@ -1301,6 +1394,7 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         EDSX_HIP(hipMemcpyAsync(&last_cur, g_cur_.as<u64>() + (ngrp - 1), 8, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         E = hctl[7]; Q = hctl[8]; cur = last_cur;
+        if (window) window_check(hctl[20]);
         mark("groups, haplotypes, sizes");
     }
     // ---- tail (:658-665)
@@ -1317,6 +1411,7 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         EDSX_HIP(hipMemcpyAsync(&c0, ctl + 11, 8, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         tail = std::min<u64>(length, refc_n - c0);
+        if (window && tail < length) window_check((seq_start + cur + cur / lw) | (1ull << 62));
     }
     const u64 Etot = E + (tail ? tail + 2 : 0), Qtot = Q + (tail ? 3 : 0);
     d_eds_.ensure(Etot + 16); d_seds_.ensure(Qtot + 16);
@@ -1334,8 +1429,11 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     seds.take(Qtot);
     PinnedDownload::copy(eds.data, d_eds_.ptr, Etot, st);
     PinnedDownload::copy(seds.data, d_seds_.ptr, Qtot, st);
+    u64 oob = 0;
+    if (window) EDSX_HIP(hipMemcpyAsync(&oob, ctl + 20, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
+    window_check(oob);
     stats.variant_groups = ngrp;                             // :724-726
     mark("emit + download");
 }

@@ -14,6 +14,19 @@ struct VcfCounters {   // vcf_transforms.hpp:24-35
     u64 total_variants = 0, processed_variants = 0, skipped_malformed = 0, skipped_unsupported_sv = 0, variant_groups = 0;
 };
 
+// FASTA metadata of a partitioned run, found once over the slices of all ranks (VcfPipeline::fasta_slice, vcf_multi.hip).
+// regular: the file is one record without '\r' or blank lines, and every line but its last (non-empty) one has exactly the first
+// line's width lw, so position p sits at file offset seq_start + p + p / lw (vcf_transforms.cpp:98-129 read it there)
+// and a range of positions can be read from a window of the file.
+struct FastaMeta { u64 seq_size = 0; bool regular = false; };
+// one rank's slice [a, b) of the FASTA body, exchanged as it is: the first "\n>" in it (its '>', ~0: none), and in front of
+// that: the bytes that are not '\n', flags (1: '\r', 2: a byte on the line grid of width lw + 1 that is not '\n'), the
+// first '\n' off that grid (~0: none)
+struct FaSlice { u64 rec_end, count, flags, offgrid; };
+// header line and first sequence line (:51-86) with the reference's error texts: sequence start, width of the first
+// line, offset of the second line
+void fasta_head(const uint8_t* fasta, size_t fasta_n, u64& seq_start, u64& lw, u64& rest_from);
+
 // One position range of a partitioned run: the records are handed over in their final order, the
 // walk starts at cur0 (no common text in front of the first group when cur0 is its start) and the closing common
 // text stops at the first group of the next range.
@@ -21,6 +34,9 @@ struct VcfRange {
     bool presorted = false;
     u64 cur0 = 0;
     u64 next_start = ~0ull;        // ~0: last (or only) range, flush to the end of the reference
+    // set: seq_size comes from here, and a regular file is read from the window [off(cur0), off(end)) only (end =
+    // next_start, or seq_size for the last range; 16 bytes of slack, clipped to the file); otherwise the whole file
+    const FastaMeta* fasta = nullptr;
 };
 
 // index pass of a partitioned run: positions, REF lengths and line spans of the accepted records, file order
@@ -36,11 +52,15 @@ public:
              VcfCounters& stats, hipStream_t st, const VcfRange& range = VcfRange());
 
     bool tokenised_on_device() const { return tokenised_on_device_; }
+    u64 fasta_h2d_bytes() const { return fasta_h2d_; }          // FASTA bytes the last run copied to the device
+    // metadata pass of a partitioned run over the slice [a, b) of the FASTA body (a > seq_start - 1); h2d: bytes copied
+    FaSlice fasta_slice(const uint8_t* fasta, u64 a, u64 b, u64 seq_start, u64 rest_from, u64 lw, hipStream_t st, u64& h2d);
     bool index_device(const uint8_t* vcf, size_t n, hipStream_t st, std::vector<u64>& pos, std::vector<u64>& reflen,
                       std::vector<u64>& line_off, std::vector<u64>& line_len, VcfCounters& stats);
 
 private:
     bool tokenised_on_device_ = false;
+    u64 fasta_h2d_ = 0;
     bool tokenize_device(const uint8_t* vcf, size_t n, bool presorted, hipStream_t st, u64& nrec, u64& max_samples,
                          VcfCounters& stats);
     DevBuf vt_raw_, vt_idx_, vt_lstart_, vt_pos_, vt_reflen_, vt_nalt_, vt_altc_, vt_ngt_, vt_nall_, vt_s1_, vt_s2_, vt_s3_,
@@ -48,7 +68,7 @@ private:
     DevBuf d_fasta_, refc_, blkpre_, scan_tmp_, ctl_, start_, reflen_, alt0_, altoff_, altchars_, pair0_, pa0_, alleles_,
            ends_, flag_, gidx_, grp_r0_, g_gs_, g_spanlen_, g_cs_, g_nraw_, g_rawchars_, g_ndist_, g_bitwords_, g_eds_,
            g_seds_, g_common_, g_cur_, raw0_, rawc0_, bit0_, rawlen_, rawoff_, canon_, hapchars_, carried_, d_eds_, d_seds_,
-           d_one_;
+           d_one_, d_slice_, slice_ctl_;
 };
 
 } // namespace edsx

@@ -21,6 +21,7 @@ int main(int argc, char** argv)
         opts.add("output", 'o', true, false, "Output EDS file (default: <input>.eds)");
         opts.add("sources", 's', true, false, "Output source file (default: <output>.seds)");
         opts.add("context-length", 'l', true, false, "Create l-EDS with minimum context length (0 = regular EDS)");
+        opts.add("gpus", 'g', true, false, "Spread the records over this many GPUs of the node by reference position (RCCL exchanges; default 1)");
         opts.parse(argc, argv);
         if (opts.has("help")) {
             std::cout << "vcf2eds - Transform VCF (Variant Call Format) to EDS\n\n" << opts.usage() << "\n"
@@ -29,7 +30,10 @@ int main(int argc, char** argv)
                          "  String (EDS) with sample-level source tracking. Each sample in the VCF\n"
                          "  is tracked as a separate path in the source file.\n\n"
                          "SUPPORTED VARIANTS:\n"
-                         "  SNPs, small indels, <DEL>, <INS>, multi-allelic sites\n\n";
+                         "  SNPs, small indels, <DEL>, <INS>, multi-allelic sites\n\n"
+                         "EXAMPLES:\n"
+                         "  vcf2eds -i variants.vcf -r ref.fa            # variants.eds + variants.seds\n"
+                         "  vcf2eds -i variants.vcf -r ref.fa --gpus 8   # position ranges on GPUs 0..7, over RCCL\n\n";
             tool::print_performance(timer);
             return 0;
         }
@@ -39,6 +43,8 @@ int main(int argc, char** argv)
         const std::filesystem::path output_file = opts.get("output");
         const std::filesystem::path sources_file = opts.get("sources");
         const Length context_length = static_cast<Length>(opts.get_unsigned("context-length", 0));
+        const unsigned long ngpu = opts.has("gpus") ? opts.get_unsigned("gpus", 1) : 0;
+        if (opts.has("gpus") && (ngpu == 0 || ngpu > 64)) throw std::runtime_error("--gpus must be between 1 and 64");
 
         if (input_file.extension() != ".vcf") {
             std::cerr << "Error: Input file must be a VCF file (.vcf)\n";
@@ -65,15 +71,37 @@ int main(int argc, char** argv)
         std::cout << "  Reference: " << reference_file << "\n";
 
         VCFStats stats;
-        edsx_ctx* ctx = detail::context();
         detail::Buf eds_out, seds_out;
         edsx_vcf_stats cst{};
-        const int rc = edsx_vcf_transform(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
-                                          &eds_out.b, &seds_out.b, &cst);
-        stats.total_variants = cst.total_variants; stats.processed_variants = cst.processed_variants;
-        stats.skipped_malformed = cst.skipped_malformed; stats.skipped_unsupported_sv = cst.skipped_unsupported_sv;
-        stats.variant_groups = cst.variant_groups;
-        if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+        auto take_stats = [&] {
+            stats.total_variants = cst.total_variants; stats.processed_variants = cst.processed_variants;
+            stats.skipped_malformed = cst.skipped_malformed; stats.skipped_unsupported_sv = cst.skipped_unsupported_sv;
+            stats.variant_groups = cst.variant_groups;
+        };
+        if (ngpu) {
+            // N rank threads inside the library, one per GPU (devices 0 .. N-1): reference-position ranges, RCCL exchanges
+            std::vector<int> devs(ngpu);
+            for (unsigned long i = 0; i < ngpu; i++) devs[i] = static_cast<int>(i);
+            edsx_multi* mg = nullptr;
+            if (edsx_multi_create(devs.data(), static_cast<int>(ngpu), 1, &mg) != EDSX_OK)
+                throw std::runtime_error("cannot use " + std::to_string(ngpu) + " GPUs (gfx950 devices 0.." + std::to_string(ngpu - 1) + " with RCCL)");
+            const int rc = edsx_vcf_transform_multi(mg, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
+                                                    &eds_out.b, &seds_out.b, &cst);
+            const std::string what = rc != EDSX_OK ? edsx_multi_last_error(mg) : "";
+            edsx_vcf_multi_info info{};
+            edsx_multi_last_vcf(mg, &info);
+            edsx_multi_destroy(mg);
+            take_stats();
+            if (rc != EDSX_OK) throw std::runtime_error(what);
+            std::cout << "  GPUs: " << ngpu << (info.partitioned ? " (position ranges" + std::string(info.fasta_windowed ? ", FASTA windows" : "") + ")"
+                                                                 : std::string(ngpu > 1 ? " (not partitioned: one GPU transforms the file)" : "")) << "\n";
+        } else {
+            edsx_ctx* ctx = detail::context();
+            const int rc = edsx_vcf_transform(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
+                                              &eds_out.b, &seds_out.b, &cst);
+            take_stats();
+            if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+        }
 
         std::filesystem::path eds_path, seds_path;
         if (create_leds) {

@@ -228,6 +228,23 @@ int  edsx_msa_transform_multi(edsx_multi* m, const uint8_t* msa, size_t msa_size
 /* of the last edsx_msa_transform_multi: 1 if the columns were partitioned, the number of boundary chains stitched */
 int  edsx_multi_last_partition(const edsx_multi* m, int* partitioned, int* chains);
 
+/* vcf2eds over the handle's GPUs: the records are partitioned by reference position (cuts at group starts, record lines
+ * moved between ranks as runs of lines), every rank transforms its range with only its window of a regular FASTA on
+ * its device, and the pieces are put together in rank order.  Outputs, stats, return codes and error texts (read
+ * through edsx_multi_last_error) equal those of edsx_vcf_transform on the same input, for any number of ranks.
+ * context_len > 0: the first device runs the LINEAR merge on the assembled text, as edsx_vcf_transform does. */
+int  edsx_vcf_transform_multi(edsx_multi* m, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                              uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats);
+typedef struct {
+    int partitioned;            /* 0: rank 0 transformed the whole file (wrapped positions, < 2 ranks with records) */
+    int fasta_windowed;         /* 1: every rank uploaded only its window of the FASTA (a regular FASTA) */
+    uint64_t records_min, records_max;      /* sorted records per rank, over ranks that own records */
+    uint64_t moved_line_bytes;              /* record-line text that changed rank, all ranks together */
+    uint64_t fasta_h2d_bytes_max;           /* most FASTA bytes one rank copied to its device (metadata slice + window) */
+} edsx_vcf_multi_info;
+/* of the last edsx_vcf_transform_multi */
+int  edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out);
+
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
  * accumulated over all plan/emit calls since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
  * total_ms[i] / launches[i] is the average duration of kernel names[i].  Returns the entry count. */
