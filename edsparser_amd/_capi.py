@@ -31,6 +31,16 @@ class VcfMultiInfo(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("records_min", "records_max", "moved_line_bytes", "fasta_h2d_bytes_max")]
 
 
+class MergeMultiInfo(ctypes.Structure):
+    _fields_ = [("partitioned", ctypes.c_int), ("ranges", ctypes.c_int), ("fallback", ctypes.c_int)] + \
+               [(n, ctypes.c_uint64) for n in ("range_bytes_min", "range_bytes_max", "eds_h2d_bytes_max", "seds_h2d_bytes_max")]
+
+
+class EdsRangeScan(ctypes.Structure):
+    _fields_ = [("ok", ctypes.c_int), ("strings", ctypes.c_uint64), ("has_cut", ctypes.c_int),
+                ("sym_start", ctypes.c_uint64), ("sym_end", ctypes.c_uint64), ("strings_before", ctypes.c_uint64)]
+
+
 class EdsStatistics(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_uint64) for n in ("n_symbols", "n_chars", "n_strings", "num_degenerate_symbols",
                                                 "total_change_size", "num_common_chars", "num_empty_strings",
@@ -131,6 +141,14 @@ def load_library():
     lib.edsx_vcf_transform_multi.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                                              ctypes.c_size_t, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
     lib.edsx_multi_last_vcf.argtypes = [ctypes.c_void_p, P(VcfMultiInfo)]
+    lib.edsx_leds_merge_multi.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+                                          ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, P(_Buf), P(_Buf)]
+    lib.edsx_multi_last_merge.argtypes = [ctypes.c_void_p, P(MergeMultiInfo)]
+    lib.edsx_eds_scan_range.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                        ctypes.c_uint32, P(EdsRangeScan)]
+    lib.edsx_seds_scan_range.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_int), P(ctypes.c_uint64),
+                                         ctypes.c_void_p, ctypes.c_void_p]
     lib.edsx_genvcf.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, P(_Buf), P(_Buf)]
     lib.edsx_msa_synth_size_aligned.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32]
     lib.edsx_msa_synth_size_aligned.restype = ctypes.c_size_t
@@ -208,6 +226,30 @@ class MultiGpu:
         info = VcfMultiInfo()
         self._lib.edsx_multi_last_vcf(self._h, ctypes.byref(info))
         return {n: (bool if n in ("partitioned", "fasta_windowed") else int)(getattr(info, n)) for n, _ in VcfMultiInfo._fields_}
+
+    def leds_merge(self, eds, seds=None, context_len=1, compact=True):
+        """EDS (+ sEDS: LINEAR, else CARTESIAN) -> (leds, seds_out) by symbol ranges over the handle's GPUs; the same
+        outputs and errors as Context.leds_merge."""
+        o, so = _Buf(), _Buf()
+        eds = bytes(eds)
+        sb = bytes(seds) if seds is not None else None
+        rc = self._lib.edsx_leds_merge_multi(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0, context_len,
+                                             1 if compact else 0, ctypes.byref(o), ctypes.byref(so))
+        if rc != 0:
+            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
+        out = []
+        for b in (o, so):
+            out.append(ctypes.string_at(b.data, b.size) if b.size else b"")
+            self._lib.edsx_buf_free(ctypes.byref(b))
+        return out[0], out[1]
+
+    def last_merge(self):
+        """Of the last leds_merge: partitioned, ranges, fallback (0 partitioned; 1 one rank / l = 0; 2 text not plain;
+        3 no sentinel; 4 source sets do not match; 5 a sentinel was merged or a range failed), range_bytes_min / _max,
+        eds_h2d_bytes_max, seds_h2d_bytes_max."""
+        info = MergeMultiInfo()
+        self._lib.edsx_multi_last_merge(self._h, ctypes.byref(info))
+        return {n: (bool if n == "partitioned" else int)(getattr(info, n)) for n, _ in MergeMultiInfo._fields_}
 
 
 def synth_size(n_rows, n_cols, row_align=0):
@@ -331,6 +373,28 @@ class Context:
                                                     1 if tail_sentinel else 0, ctypes.byref(o), ctypes.byref(so),
                                                     ctypes.byref(hi), ctypes.byref(ti)))
         return self._take(o), self._take(so), bool(hi.value), bool(ti.value)
+
+    def eds_scan_range(self, eds, lo, hi, context_len):
+        """Device scan of .eds bytes [lo, hi): dict(ok, strings, cut) as multigpu.eds_scan_range, cut = None or
+        (sym_start, sym_end, strings in [lo, sym_start))."""
+        out = EdsRangeScan()
+        eds = bytes(eds)
+        self._check(self._lib.edsx_eds_scan_range(self._h, eds, len(eds), int(lo), int(hi), int(context_len), ctypes.byref(out)))
+        cut = (int(out.sym_start), int(out.sym_end), int(out.strings_before)) if out.has_cut else None
+        return {"ok": bool(out.ok), "strings": int(out.strings), "cut": cut}
+
+    def seds_scan_range(self, seds, lo, hi, ordinals=()):
+        """Device scan of .seds bytes [lo, hi) -> (ok, number of '{', [(start, end) of the k-th '{' ... '}' for k in
+        ordinals]); end = find('}', start) + 1 over the whole buffer."""
+        import numpy as np
+        seds = bytes(seds)
+        ords = np.ascontiguousarray(list(ordinals), dtype=np.uint64)
+        p0 = np.zeros(len(ords), dtype=np.uint64)
+        p1 = np.zeros(len(ords), dtype=np.uint64)
+        ok, braces = ctypes.c_int(), ctypes.c_uint64()
+        self._check(self._lib.edsx_seds_scan_range(self._h, seds, len(seds), int(lo), int(hi), ords.ctypes.data, len(ords),
+                                                   ctypes.byref(ok), ctypes.byref(braces), p0.ctypes.data, p1.ctypes.data))
+        return bool(ok.value), int(braces.value), [(int(a), int(b)) for a, b in zip(p0, p1)]
 
     # ---- position-range partition of the VCF path (multi-GPU, see multigpu.VcfSharder)
     def vcf_index(self, vcf):

@@ -4,6 +4,7 @@
 #include "genrandom.hpp"
 #include "genvcf.hpp"
 #include "merge_device.hpp"
+#include "merge_scan.hpp"
 #include "msa_device.hpp"
 #include "multi_gpu.hpp"
 #include "synth.hpp"
@@ -23,6 +24,7 @@ struct edsx_ctx {
     std::string err;
     MsaPipeline msa;
     MergePipeline merge;
+    RangeScanner scan;                       // edsx_eds_scan_range / edsx_seds_scan_range
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -313,6 +315,41 @@ int edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out)
     return EDSX_OK;
 }
 
+int edsx_leds_merge_multi(edsx_multi* m, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                          uint32_t context_len, int compact, edsx_buf* leds, edsx_buf* seds_out)
+{
+    if (leds) { leds->data = nullptr; leds->size = 0; }
+    if (seds_out) { seds_out->data = nullptr; seds_out->size = 0; }
+    edsx_multi_impl* mi = reinterpret_cast<edsx_multi_impl*>(m);
+    if (!mi) return EDSX_ERR_INVALID_PARAMETER;
+    try {
+        mi->err.clear();
+        if (!leds || !seds_out || (!eds && eds_size)) throw ParamError("null argument");
+        HostBytes out, sout;
+        mi->m->leds_merge_multi(eds, eds_size, seds, seds_size, context_len, compact != 0, out, sout);
+        leds->size = out.size; leds->data = out.release();
+        seds_out->size = sout.size; seds_out->data = sout.release();
+        return EDSX_OK;
+    } catch (const FormatError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
+    } catch (const ParamError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
+    } catch (const LimitError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
+    } catch (const DeviceError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
+    } catch (const std::bad_alloc&) { mi->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
+    } catch (const std::exception& ex) { mi->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+}
+int edsx_multi_last_merge(const edsx_multi* m, edsx_merge_multi_info* out)
+{
+    const edsx_multi_impl* mi = reinterpret_cast<const edsx_multi_impl*>(m);
+    if (!mi || !out) return EDSX_ERR_INVALID_PARAMETER;
+    const MergeMultiInfo& v = mi->m->last_merge();
+    out->partitioned = v.partitioned ? 1 : 0;
+    out->ranges = v.ranges;
+    out->fallback = v.fallback;
+    out->range_bytes_min = v.range_bytes_min; out->range_bytes_max = v.range_bytes_max;
+    out->eds_h2d_bytes_max = v.eds_h2d_bytes_max; out->seds_h2d_bytes_max = v.seds_h2d_bytes_max;
+    return EDSX_OK;
+}
+
 void edsx_set_timing(edsx_ctx* ctx, int enabled) { if (ctx) ctx->msa.set_timing(enabled != 0); }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -430,6 +467,42 @@ int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
         *tail_intact = sh.tail_intact ? 1 : 0;
         leds->size = out.size; leds->data = out.release();
         seds_out->size = sout.size; seds_out->data = sout.release();
+    });
+}
+
+int edsx_eds_scan_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t lo, uint64_t hi, uint32_t context_len,
+                        edsx_eds_range_scan* out)
+{
+    if (out) std::memset(out, 0, sizeof(*out));
+    return guarded(ctx, [&] {
+        if (!out || (!eds && eds_size)) throw ParamError("null argument");
+        static const uint8_t none = 0;
+        const uint8_t* p = eds ? eds : &none;
+        const EdsRangeScan s = ctx->scan.eds(p, eds_size, text_end(p, eds_size), lo, hi, context_len, nullptr);
+        out->ok = s.ok ? 1 : 0;
+        out->strings = s.strings;
+        out->has_cut = s.has_cut ? 1 : 0;
+        out->sym_start = s.sym_start; out->sym_end = s.sym_end; out->strings_before = s.strings_before;
+    });
+}
+
+int edsx_seds_scan_range(edsx_ctx* ctx, const uint8_t* seds, size_t seds_size, uint64_t lo, uint64_t hi, const uint64_t* ordinals,
+                         size_t n_ordinals, int* ok, uint64_t* braces, uint64_t* set_start, uint64_t* set_end)
+{
+    if (ok) *ok = 0;
+    if (braces) *braces = 0;
+    return guarded(ctx, [&] {
+        if (!ok || !braces || (!seds && seds_size) || (n_ordinals && (!ordinals || !set_start || !set_end)))
+            throw ParamError("null argument");
+        static const uint8_t none = 0;
+        static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
+        u64 b = 0;
+        const bool good = ctx->scan.seds_count(seds ? seds : &none, seds_size, lo, hi, b, nullptr);
+        *ok = good ? 1 : 0;
+        *braces = b;
+        if (good && n_ordinals)
+            ctx->scan.seds_locate(reinterpret_cast<const u64*>(ordinals), n_ordinals, reinterpret_cast<u64*>(set_start),
+                                  reinterpret_cast<u64*>(set_end), nullptr);
     });
 }
 

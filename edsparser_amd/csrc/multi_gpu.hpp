@@ -15,6 +15,7 @@
 #include "msa_device.hpp"
 #include "rank_barrier.hpp"
 #include "merge_device.hpp"
+#include "merge_scan.hpp"
 #include "vcf_device.hpp"
 
 #include <memory>
@@ -70,6 +71,14 @@ struct VcfMultiInfo {
     u64 records_min = 0, records_max = 0, moved_line_bytes = 0, fasta_h2d_bytes_max = 0;
 };
 
+// of the last MultiMsa::leds_merge_multi (edsx_merge_multi_info)
+struct MergeMultiInfo {
+    bool partitioned = false;
+    int ranges = 0;
+    int fallback = 0;           // 0 partitioned; 1 one rank / l = 0; 2 text not plain; 3 no sentinel; 4 source sets; 5 merged / failed
+    u64 range_bytes_min = 0, range_bytes_max = 0, eds_h2d_bytes_max = 0, seds_h2d_bytes_max = 0;
+};
+
 class MultiMsa {
 public:
     MultiMsa(const std::vector<int>& devices, bool use_rccl);
@@ -88,12 +97,19 @@ public:
     // EDS text -> l-EDS: the LINEAR merge with defaults (compact) on the first device (vcf_transforms.cpp:735-755)
     void leds_merge(HostBytes& eds, HostBytes& seds, uint32_t context_len);
     const VcfMultiInfo& last_vcf() const { return vcf_info_; }
+    // EDS text -> l-EDS by symbol ranges (merge_multi.hip): the outputs and errors of MergePipeline::run on the whole text;
+    // seds == nullptr: CARTESIAN
+    void leds_merge_multi(const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, uint32_t context_len, bool compact,
+                          HostBytes& leds, HostBytes& seds_out);
+    const MergeMultiInfo& last_merge() const { return merge_info_; }
 private:
     struct Rank;
     struct VcfShared;
+    struct MergeShared;
     void run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& lay, HostBytes& eds, HostBytes& seds);
     void run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, HostBytes& eds, HostBytes& seds);
     void run_rank_vcf(int r, VcfShared& sh);
+    void run_rank_merge(int r, MergeShared& sh);
     std::vector<int> devices_;
     std::vector<std::unique_ptr<Rank>> ranks_;
     std::unique_ptr<Exchange> xch_;
@@ -104,6 +120,7 @@ private:
     // shared between the rank threads of one call
     std::vector<u64> piece_e_, piece_s_;
     VcfMultiInfo vcf_info_;
+    MergeMultiInfo merge_info_;
 };
 
 struct MultiMsa::Rank {
@@ -113,7 +130,8 @@ struct MultiMsa::Rank {
     std::vector<uint8_t> host_img;       // wrapped rows: the slab image is put together on the host
     std::string error;
     std::unique_ptr<VcfPipeline> vcf;    // vcf_transform: created on first use
-    std::unique_ptr<MergePipeline> merge;   // (rank 0, context length > 0)
+    std::unique_ptr<MergePipeline> merge;   // (rank 0, context length > 0; every rank in leds_merge_multi)
+    std::unique_ptr<RangeScanner> scan;     // leds_merge_multi: the device scans of this rank's slices
 };
 
 } // namespace edsx

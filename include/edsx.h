@@ -14,6 +14,9 @@
  *   edsx_vcf_transform   replaces parse_vcf_to_eds_streaming  (vcf_transforms.hpp:59-62, .cpp:677-729)
  *                        and      parse_vcf_to_leds_streaming (vcf_transforms.hpp:75-79, .cpp:735-755)
  *
+ * The same transforms spread over the GPUs of one node from one process (edsx_multi): edsx_msa_transform_multi
+ * (column slabs), edsx_vcf_transform_multi (reference-position ranges) and edsx_leds_merge_multi (symbol ranges).
+ *
  * Status codes mirror the reference's (unused) ErrorCode enum, src/cpp/lib/common.hpp:37-45.
  * The *_device calls take HBM pointers on the context's GPU and a hipStream_t (passed as void*),
  * so pipelines and the benchmark can keep data resident; they are what the host-buffer calls
@@ -134,6 +137,26 @@ int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
                           uint32_t context_len, int compact, int head_sentinel, int tail_sentinel,
                           edsx_buf* leds, edsx_buf* seds_out, int* head_intact, int* tail_intact);
 
+/* Device scans of one byte range of an .eds / .seds text: what the symbol-range partition learns about a rank's slice
+ * (edsparser_amd/multigpu.py, eds_scan_range / seds_scan_range, are the spec).  Each call copies only its window of the
+ * text to the device.
+ * .eds bytes [lo, hi) (hi <= eds_size; hi <= lo: an empty slice): ok = no whitespace, braces alternate from the state at
+ * lo, no comma outside braces, no '{' inside braces; strings = string starts in the slice ('{', ',' and the first byte
+ * of a bare run; 0 when not ok).  For lo > 0 only, has_cut: the first sentinel whose preceding '}' lies in [lo, hi),
+ * spelled COMPACT `}p{x,y}` or FULL `}{p}{x,y}` with p of at least max(context_len, 1) characters, searched in a window
+ * from the last '{' in front of lo up to min(end, hi + 65536 + 4 context_len) (end: the text without trailing
+ * whitespace); [sym_start, sym_end) are its bytes and strings_before the string starts in [lo, sym_start). */
+typedef struct { int ok; uint64_t strings; int has_cut; uint64_t sym_start, sym_end, strings_before; } edsx_eds_range_scan;
+int edsx_eds_scan_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t lo, uint64_t hi, uint32_t context_len,
+                        edsx_eds_range_scan* out);
+/* .seds bytes [lo, hi): *ok = no whitespace, *braces = the number of '{' (0 when not ok).  When ok, for every i <
+ * n_ordinals: [set_start[i], set_end[i]) = the bytes from the ordinals[i]-th '{' of the slice (counted from 0) to one
+ * past the first '}' behind it anywhere in the buffer (set_end 0: there is none).  An ordinal >= *braces is
+ * EDSX_ERR_INVALID_PARAMETER. */
+int edsx_seds_scan_range(edsx_ctx* ctx, const uint8_t* seds, size_t seds_size, uint64_t lo, uint64_t hi,
+                         const uint64_t* ordinals, size_t n_ordinals, int* ok, uint64_t* braces,
+                         uint64_t* set_start, uint64_t* set_end);
+
 /* ---- statistics and validation of an EDS / l-EDS (what edsparser-stats prints) ----
  * Replaces EDS::calculate_statistics / calculate_source_statistics (src/cpp/lib/formats/eds.cpp:361-470, :472-505,
  * struct EDS::Statistics eds.hpp:107-120) and is_leds (src/cpp/lib/transforms/eds_transforms.cpp:439-468): the text is
@@ -244,6 +267,27 @@ typedef struct {
 } edsx_vcf_multi_info;
 /* of the last edsx_vcf_transform_multi */
 int  edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out);
+
+/* eds2leds over the handle's GPUs: the symbol-range partition of edsx_leds_merge_range, run on the rank threads.  Every
+ * rank scans its slice of the .eds (and .seds) on its device with the kernels of edsx_eds_scan_range /
+ * edsx_seds_scan_range, the ranks exchange fixed-size records, cut the text at sentinels (the rule of
+ * edsparser_amd/multigpu.py, MergeSharder: the same input and number of ranks give the same ranges), locate the
+ * sentinels' source sets, and every range's owner merges eds[e0, e1) / seds[s0, s1) on its device; the pieces are put
+ * together in rank order.  A rank copies its scan window and its range to its device, never the whole text.  Rank 0
+ * merges the whole text instead with one rank or context_len 0, a slice that is not plain text, no sentinel, source sets
+ * that do not match, or a sentinel drawn into a merge / a failed range.  Outputs, return codes and error texts (read
+ * through edsx_multi_last_error) equal those of edsx_leds_merge on the same input, for any number of ranks. */
+int  edsx_leds_merge_multi(edsx_multi* m, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                           uint32_t context_len, int compact, edsx_buf* leds, edsx_buf* seds_out);
+typedef struct {
+    int partitioned, ranges;    /* ranges: symbol ranges merged (1 when not partitioned) */
+    int fallback;   /* 0 partitioned; 1 one rank / context_len 0; 2 text not plain; 3 no sentinel;
+                       4 source sets do not match; 5 a sentinel was merged or a range failed */
+    uint64_t range_bytes_min, range_bytes_max;          /* .eds bytes of the ranges (the whole text when not partitioned) */
+    uint64_t eds_h2d_bytes_max, seds_h2d_bytes_max;     /* most .eds / .seds bytes one rank copied to its device */
+} edsx_merge_multi_info;
+/* of the last edsx_leds_merge_multi */
+int  edsx_multi_last_merge(const edsx_multi* m, edsx_merge_multi_info* out);
 
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
  * accumulated over all plan/emit calls since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
