@@ -50,6 +50,11 @@ class EdsStatistics(ctypes.Structure):
                 [("avg_paths_per_string", ctypes.c_double), ("is_leds", ctypes.c_int)])
 
 
+class QueryInfo(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("n_symbols", "n_strings", "n_chars", "num_common_chars", "num_degenerate_strings")] +
+                [(n, ctypes.c_double) for n in ("tokenise_ms", "tables_ms", "kernel_ms", "download_ms")])
+
+
 class MsaInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("n_rows", "n_cols", "line_width", "n_variant_cols", "n_segments", "msa_bytes",
@@ -155,6 +160,11 @@ def load_library():
     lib.edsx_msa_synth_device_aligned.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64,
                                                   ctypes.c_uint32, ctypes.c_void_p, P(ctypes.c_size_t)]
+    lib.edsx_eds_genpatterns.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                         ctypes.c_uint64, P(_Buf), P(_Buf), P(_Buf), P(_Buf)]
+    lib.edsx_eds_check_positions.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                             ctypes.c_size_t] + [ctypes.c_void_p] * 6
+    lib.edsx_query_last_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
     _LIB = lib
     return lib
 
@@ -337,6 +347,52 @@ class Context:
         self._check(self._lib.edsx_eds_stats(self._h, eds, len(eds), seds, len(seds) if seds is not None else 0,
                                              context_len, ctypes.byref(st)))
         return {n: getattr(st, n) for n, _ in EdsStatistics._fields_}
+
+    # ---- queries (EDS::generate_patterns / EDS::check_position on the GPU)
+    def eds_genpatterns(self, eds, count, length, seed, witness=False):
+        """count patterns of `length` characters, one per line (bytes).  witness=True: (patterns, pos, off, deg) with the
+        start common position per pattern (numpy uint64, 2**64-1 for a wrapped pattern) and the chosen degenerate string
+        numbers as CSR (off uint64 count+1, deg int32)."""
+        import numpy as np
+        p, wp, wo, wd = _Buf(), _Buf(), _Buf(), _Buf()
+        eds = bytes(eds)
+        w = [ctypes.byref(b) for b in (wp, wo, wd)] if witness else [None, None, None]
+        self._check(self._lib.edsx_eds_genpatterns(self._h, eds, len(eds), int(count), int(length), int(seed) & (2**64 - 1),
+                                                   ctypes.byref(p), *w))
+        pats = self._take(p)
+        if not witness:
+            return pats
+        pos = np.frombuffer(self._take(wp), dtype=np.uint64)
+        off = np.frombuffer(self._take(wo), dtype=np.uint64)
+        deg = np.frombuffer(self._take(wd), dtype=np.int32)
+        return pats, pos, off, deg
+
+    def eds_check_positions(self, eds, positions, choice_off, choices, pattern_off, patterns, seds=None):
+        """EDS::check_position per query (CSR inputs, numpy-convertible) -> numpy int8: 1 true, 0 false,
+        -1 out_of_range, -2 invalid_argument."""
+        import numpy as np
+        eds = bytes(eds)
+        sb = bytes(seds) if seds is not None else None
+        pos = np.ascontiguousarray(positions, dtype=np.uint64)
+        coff = np.ascontiguousarray(choice_off, dtype=np.uint64)
+        ch = np.ascontiguousarray(choices, dtype=np.int32)
+        poff = np.ascontiguousarray(pattern_off, dtype=np.uint64)
+        pat = np.frombuffer(bytes(patterns), dtype=np.uint8) if not isinstance(patterns, np.ndarray) else \
+            np.ascontiguousarray(patterns, dtype=np.uint8)
+        n = len(pos)
+        if len(coff) != n + 1 or len(poff) != n + 1:
+            raise ValueError("choice_off and pattern_off need len(positions) + 1 entries")
+        out = np.empty(n, dtype=np.int8)
+        self._check(self._lib.edsx_eds_check_positions(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0, n,
+                                                       pos.ctypes.data, coff.ctypes.data, ch.ctypes.data, poff.ctypes.data,
+                                                       pat.ctypes.data, out.ctypes.data))
+        return out
+
+    def query_last_info(self):
+        """Counts and timing of the last eds_genpatterns / eds_check_positions call."""
+        q = QueryInfo()
+        self._check(self._lib.edsx_query_last_info(self._h, ctypes.byref(q)))
+        return {n: getattr(q, n) for n, _ in QueryInfo._fields_}
 
     def genrandomeds(self, total_bp, variability=0.10, min_alt=2, max_alt=4, var_len_max=10, snp_ratio=0.7,
                      alphabet="ACGT", min_context=0, seed=42):

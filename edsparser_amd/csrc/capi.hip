@@ -7,6 +7,7 @@
 #include "merge_scan.hpp"
 #include "msa_device.hpp"
 #include "multi_gpu.hpp"
+#include "query_device.hpp"
 #include "synth.hpp"
 #include "vcf_device.hpp"
 
@@ -25,6 +26,7 @@ struct edsx_ctx {
     MsaPipeline msa;
     MergePipeline merge;
     RangeScanner scan;                       // edsx_eds_scan_range / edsx_seds_scan_range
+    QueryPipeline query;                     // edsx_eds_genpatterns / edsx_eds_check_positions
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -468,6 +470,58 @@ int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
         leds->size = out.size; leds->data = out.release();
         seds_out->size = sout.size; seds_out->data = sout.release();
     });
+}
+
+int edsx_eds_genpatterns(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t count, uint32_t pattern_length,
+                         uint64_t seed, edsx_buf* patterns, edsx_buf* witness_pos, edsx_buf* witness_off, edsx_buf* witness_deg)
+{
+    for (edsx_buf* b : {patterns, witness_pos, witness_off, witness_deg}) if (b) { b->data = nullptr; b->size = 0; }
+    return guarded(ctx, [&] {
+        const int nw = (witness_pos != nullptr) + (witness_off != nullptr) + (witness_deg != nullptr);
+        if (!patterns || (!eds && eds_size) || (nw != 0 && nw != 3)) throw ParamError("null argument");
+        static const uint8_t none = 0;
+        HostBytes out;
+        std::vector<u64> wpos, woff;
+        std::vector<int32_t> wdeg;
+        ctx->query.genpatterns(ctx->merge, eds ? eds : &none, eds_size, count, pattern_length, seed, out, nw ? &wpos : nullptr,
+                               nw ? &woff : nullptr, nw ? &wdeg : nullptr, nullptr);
+        if (nw) {
+            take(witness_pos, 8 * wpos.size());
+            if (!wpos.empty()) std::memcpy(witness_pos->data, wpos.data(), 8 * wpos.size());
+            take(witness_off, 8 * woff.size());
+            std::memcpy(witness_off->data, woff.data(), 8 * woff.size());
+            take(witness_deg, 4 * wdeg.size());
+            if (!wdeg.empty()) std::memcpy(witness_deg->data, wdeg.data(), 4 * wdeg.size());
+        }
+        patterns->size = out.size; patterns->data = out.data;      // the download buffer itself
+        out.data = nullptr; out.size = 0;
+    });
+}
+
+int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                             size_t n, const uint64_t* common_pos, const uint64_t* choice_off, const int32_t* choices,
+                             const uint64_t* pattern_off, const uint8_t* patterns, int8_t* status_out)
+{
+    return guarded(ctx, [&] {
+        if ((!eds && eds_size) || (n && (!common_pos || !choice_off || !pattern_off || !status_out)) ||
+            (n && choice_off[n] && !choices) || (n && pattern_off[n] && !patterns))
+            throw ParamError("null argument");
+        static const uint8_t none = 0;
+        static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
+        ctx->query.check(ctx->merge, eds ? eds : &none, eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
+                         reinterpret_cast<const u64*>(choice_off), choices, reinterpret_cast<const u64*>(pattern_off), patterns,
+                         status_out, nullptr);
+    });
+}
+
+int edsx_query_last_info(const edsx_ctx* ctx, edsx_query_info* out)
+{
+    if (!ctx || !out) return EDSX_ERR_INVALID_PARAMETER;
+    const QueryInfo& q = ctx->query.info();
+    out->n_symbols = q.n_symbols; out->n_strings = q.n_strings; out->n_chars = q.n_chars;
+    out->num_common_chars = q.num_common_chars; out->num_degenerate_strings = q.num_degenerate_strings;
+    out->tokenise_ms = q.tokenise_ms; out->tables_ms = q.tables_ms; out->kernel_ms = q.kernel_ms; out->download_ms = q.download_ms;
+    return EDSX_OK;
 }
 
 int edsx_eds_scan_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t lo, uint64_t hi, uint32_t context_len,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "draw.hpp"
+
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -117,17 +119,7 @@ __device__ __forceinline__ u32 mbcnt(u64 mask)
 }
 __device__ __forceinline__ u64 ballot64(bool p) { return __ballot(p); }
 
-__device__ __forceinline__ u64 mix64(u64 x)
-{   // splitmix64 finaliser
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ u64 hash3(u64 seed, u64 a, u64 b)
-{
-    return mix64(seed ^ mix64(a ^ mix64(b + 0x632BE59BD9B4E019ull)));
-}
+// mix64 / hash3 (splitmix64): draw.hpp, shared with the host library
 
 // 16 bytes from an arbitrarily aligned address (gfx950 global loads tolerate misalignment;
 // hipcc emits one global_load_dwordx4 for this)

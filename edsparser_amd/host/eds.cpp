@@ -1,13 +1,16 @@
 // Host-side EDS container: parse / save / sources / pairwise merge.
 // Behaviour follows the reference's src/cpp/lib/formats/eds.cpp — parse :39-155, normalize
 // :831-881, parse_sources :268-355, save :600-631, save_sources :641-659, merge_adjacent
-// :1425-1695 — including its error texts, which callers and tests match on.
+// :1425-1695, generate_patterns :673-769, extract :771-825, check_position :953-1418 — including its error texts,
+// which callers and tests match on.
 #include "edsparser/formats/eds.hpp"
+#include "../csrc/draw.hpp"
 
 #include <algorithm>
 #include <cctype>
 #include <fstream>
 #include <iterator>
+#include <random>
 #include <sstream>
 #include <stdexcept>
 
@@ -146,6 +149,18 @@ void EDS::rebuild_metadata()
     }
     metadata_.avg_context_length = ndeg_free ? static_cast<double>(sum_ctx) / ndeg_free : 0.0;
     is_empty_ = (n_ == 0);
+    if (n_ > 0) {                                              // position checking tables (eds.cpp:438-469)
+        Position common = 0;
+        int deg = 0;
+        metadata_.cum_common_positions.push_back(0);
+        metadata_.cum_degenerate_counts.push_back(0);
+        for (size_t i = 0; i < n_; ++i) {
+            if (metadata_.is_degenerate[i]) deg += static_cast<int>(metadata_.symbol_sizes[i]);
+            else common += sets_[i][0].size();
+            metadata_.cum_common_positions.push_back(common);
+            metadata_.cum_degenerate_counts.push_back(deg);
+        }
+    }
     if (has_sources_) {
         std::set<int> all;
         size_t total = 0;
@@ -352,6 +367,198 @@ EDS EDS::merge_adjacent(size_t pos1, size_t pos2) const
         if (i != pos2) out.metadata_.base_positions.push_back(metadata_.base_positions[i]);
     out.rebuild_metadata();
     return out;
+}
+
+// ---- query side ------------------------------------------------------------------------------------------------
+
+void EDS::generate_patterns(std::ostream& os, size_t count, Length pattern_length) const
+{
+    std::random_device rd;
+    const uint64_t seed = (static_cast<uint64_t>(rd()) << 32) ^ rd();
+    generate_patterns(os, count, pattern_length, seed);
+}
+
+// The host twin of the device sampler (edsparser_amd/csrc/query_device.hip, k_pat_sample): draw k of pattern i is
+// edsx::pattern_draw(seed, i, k, bound), k = 0 the start, k = 1, 2, ... the strings in walk order and then in the wrap.
+void EDS::generate_patterns(std::ostream& os, size_t count, Length pattern_length, uint64_t seed) const
+{
+    if (is_empty_ || n_ == 0) throw std::runtime_error("Cannot generate patterns from empty EDS");
+    if (pattern_length == 0) throw std::invalid_argument("Pattern length must be greater than 0");
+    const auto& cc = metadata_.cum_common_positions;
+    const Position C = metadata_.num_common_chars;
+    String pattern;
+    for (size_t i = 0; i < count; ++i) {
+        pattern.clear();
+        uint64_t k = 0;
+        size_t cur = 0;
+        Position offset = 0;
+        if (C > 0) {                                           // upper_bound always lands on a common symbol
+            const Position p = edsx::pattern_draw(seed, i, k, C);
+            cur = static_cast<size_t>(std::upper_bound(cc.begin(), cc.end(), p) - cc.begin()) - 1;
+            offset = p - cc[cur];
+        }
+        k = 1;
+        bool first = true;
+        while (pattern.size() < pattern_length && cur < n_) {
+            const StringSet& set = sets_[cur];
+            if (set.empty()) { ++cur; first = false; continue; }          // (:713; the parser never makes one)
+            const String& s = set[edsx::pattern_draw(seed, i, k++, set.size())];
+            const size_t from = first ? offset : 0;
+            if (from < s.size()) pattern.append(s, from, std::min<size_t>(pattern_length - pattern.size(), s.size() - from));
+            first = false;
+            if (pattern.size() < pattern_length) ++cur;
+        }
+        while (pattern.size() < pattern_length) {              // wrap (:747): a uniform non-empty string of symbol len % n
+            const size_t w = pattern.size() % n_;
+            size_t nonempty = 0;
+            for (const String& s : sets_[w]) nonempty += !s.empty();
+            if (nonempty == 0)
+                throw std::runtime_error("Cannot generate pattern " + std::to_string(i) + ": the wrap-around reaches symbol " +
+                                         std::to_string(w) + ", which has no non-empty string");
+            size_t j = edsx::pattern_draw(seed, i, k++, nonempty);
+            for (const String& s : sets_[w]) {
+                if (s.empty()) continue;
+                if (j-- == 0) { pattern.append(s, 0, std::min<size_t>(pattern_length - pattern.size(), s.size())); break; }
+            }
+        }
+        os << pattern << '\n';
+    }
+}
+
+String EDS::extract(Position pos, Length len, const std::vector<int>& changes) const
+{
+    if (is_empty_ || n_ == 0) throw std::runtime_error("Cannot extract from empty EDS");
+    if (pos >= n_) throw std::out_of_range("Start position exceeds EDS length");
+    if (len == 0) return "";
+    const Position end_pos = std::min<Position>(pos + len, n_);
+    const size_t expected = end_pos - pos;
+    if (changes.size() != expected)
+        throw std::invalid_argument("changes vector size (" + std::to_string(changes.size()) + ") must match range length (" +
+                                    std::to_string(expected) + ")");
+    String result;
+    for (size_t i = 0; i < expected; ++i) {
+        const Position cur = pos + i;
+        const int c = changes[i];
+        const StringSet& set = sets_[cur];
+        if (c < 0 || static_cast<size_t>(c) >= set.size())
+            throw std::out_of_range("Change index " + std::to_string(c) + " at position " + std::to_string(cur) +
+                                    " is out of range (set size: " + std::to_string(set.size()) + ")");
+        result.append(set[c]);
+    }
+    return result;
+}
+
+// Pinned where the reference reads past its tables: common_pos >= num_common_chars is `false` (checked before the
+// search), a string number >= the number of degenerate strings is std::out_of_range.
+bool EDS::check_position(Position common_pos, const std::vector<int>& degenerate_strings, const String& pattern) const
+{
+    if (is_empty_ || n_ == 0) return false;
+    if (pattern.empty()) return true;
+    if (common_pos >= metadata_.num_common_chars) return false;
+    Position offset = 0;
+    const size_t start = find_symbol_at_common_position(common_pos, offset);
+    size_t expected_deg = 0;                                   // the warning of :977-999 (first-string lengths)
+    Length counted = 0;
+    for (size_t i = start; i < n_ && counted < pattern.size(); ++i) {
+        if (metadata_.is_degenerate[i]) expected_deg++;
+        Length len = metadata_.string_lengths[metadata_.cum_set_sizes[i]];
+        if (i == start) len = len > offset ? static_cast<Length>(len - offset) : 0;
+        counted += len;
+    }
+    if (degenerate_strings.size() > expected_deg)
+        std::cerr << "Warning: More degenerate strings provided (" << degenerate_strings.size() << ") than needed ("
+                  << expected_deg << "). Extra strings will be ignored.\n";
+    const Length plen = static_cast<Length>(pattern.size());
+    if (has_sources_ && calculate_path_intersection(start, offset, degenerate_strings, plen).empty()) return false;
+    const String rec = reconstruct_from_memory(start, offset, degenerate_strings, plen);
+    return rec.size() >= pattern.size() && rec == pattern;
+}
+
+size_t EDS::find_symbol_at_common_position(Position common_pos, Position& offset_out) const
+{
+    const auto& cc = metadata_.cum_common_positions;
+    const auto it = std::upper_bound(cc.begin(), cc.end(), common_pos);
+    if (it == cc.begin()) throw std::out_of_range("Common position " + std::to_string(common_pos) + " is before EDS start");
+    const size_t sym = static_cast<size_t>(it - cc.begin()) - 1;
+    if (sym >= n_ || metadata_.is_degenerate[sym])
+        throw std::out_of_range("Common position " + std::to_string(common_pos) + " points to degenerate symbol " +
+                                std::to_string(sym));
+    offset_out = common_pos - cc[sym];
+    const Length len = metadata_.string_lengths[metadata_.cum_set_sizes[sym]];
+    if (offset_out >= len)
+        throw std::out_of_range("Offset " + std::to_string(offset_out) + " exceeds symbol " + std::to_string(sym) + " length " +
+                                std::to_string(len));
+    return sym;
+}
+
+std::pair<size_t, size_t> EDS::decode_degenerate_string_number(int abs_string_num) const
+{
+    if (abs_string_num < 0)
+        throw std::invalid_argument("Degenerate string number must be non-negative, got: " + std::to_string(abs_string_num));
+    const auto& cd = metadata_.cum_degenerate_counts;
+    if (abs_string_num >= cd.back())
+        throw std::out_of_range("Invalid degenerate string number: " + std::to_string(abs_string_num) + " (the EDS has " +
+                                std::to_string(cd.back()) + " degenerate strings)");
+    const size_t sym = static_cast<size_t>(std::upper_bound(cd.begin(), cd.end(), abs_string_num) - cd.begin()) - 1;
+    return {sym, static_cast<size_t>(abs_string_num - cd[sym])};   // a degenerate symbol: cd[sym + 1] > abs_string_num
+}
+
+String EDS::reconstruct_from_memory(size_t start_symbol, Position offset_in_symbol, const std::vector<int>& degenerate_strings,
+                                    Length pattern_length) const
+{
+    String result;
+    size_t deg_idx = 0;
+    for (size_t sym = start_symbol; sym < n_ && result.size() < pattern_length; ++sym) {
+        const String* str;
+        size_t from = 0;
+        if (metadata_.is_degenerate[sym]) {
+            if (deg_idx >= degenerate_strings.size())
+                throw std::invalid_argument("Not enough degenerate strings provided (need at least " + std::to_string(deg_idx + 1) +
+                                            ", got " + std::to_string(degenerate_strings.size()) + ")");
+            const int num = degenerate_strings[deg_idx];
+            const auto [expected_symbol, local] = decode_degenerate_string_number(num);
+            if (expected_symbol != sym)
+                throw std::invalid_argument("Degenerate string " + std::to_string(num) + " belongs to symbol " +
+                                            std::to_string(expected_symbol) + ", but expected for symbol " + std::to_string(sym));
+            str = &sets_[sym][local];
+            deg_idx++;
+        } else {
+            str = &sets_[sym][0];
+            if (sym == start_symbol) from = offset_in_symbol;    // < its length (find_symbol_at_common_position)
+        }
+        result.append(*str, from, std::min<size_t>(str->size() - from, pattern_length - result.size()));
+    }
+    return result;
+}
+
+// :1300-1418; a set containing 0 is universal
+std::set<int> EDS::calculate_path_intersection(size_t start_symbol, Position offset_in_symbol,
+                                               const std::vector<int>& degenerate_strings, Length pattern_length) const
+{
+    std::set<int> acc;
+    bool first = true;
+    size_t deg_idx = 0;
+    Length counted = 0;
+    for (size_t sym = start_symbol; sym < n_ && counted < pattern_length; ++sym) {
+        size_t sid = metadata_.cum_set_sizes[sym];
+        Length len = metadata_.string_lengths[sid];
+        if (metadata_.is_degenerate[sym]) {
+            if (deg_idx >= degenerate_strings.size())
+                throw std::invalid_argument("Not enough degenerate strings for path intersection calculation");
+            const auto [expected_symbol, local] = decode_degenerate_string_number(degenerate_strings[deg_idx]);
+            if (expected_symbol != sym) throw std::invalid_argument("Degenerate string mismatch in path intersection calculation");
+            sid += local;
+            len = metadata_.string_lengths[sid];
+            deg_idx++;
+        } else if (sym == start_symbol) {
+            len -= static_cast<Length>(offset_in_symbol);
+        }
+        acc = first ? sources_[sid] : source_intersection(acc, sources_[sid]);
+        first = false;
+        if (acc.empty()) return {};
+        counted += std::min<Length>(len, pattern_length - counted);
+    }
+    return acc;
 }
 
 } // namespace edsparser

@@ -1,8 +1,9 @@
 // edsparser/formats/eds.hpp — in-memory EDS container (hot subset of the reference's class,
 // src/cpp/lib/formats/eds.hpp:26-169): parse / save / sources / pairwise merge / metadata.
-// Statistics / get_statistics / print_statistics / print as eds.hpp:107-129.  The query-side utilities of the
-// reference (pattern sampling, extract, check_position, METADATA_ONLY streaming) are outside the transform
-// hot path and are not provided.
+// Statistics / get_statistics / print_statistics / print as eds.hpp:107-129.  The query side - generate_patterns,
+// extract, check_position (eds.hpp:139-147) - as the reference, with the behaviour pinned where it reads past its
+// tables; every EDS is held in FULL mode (METADATA_ONLY streaming is not provided).  The same queries run on the GPU
+// through edsx_eds_genpatterns / edsx_eds_check_positions (include/edsx.h).
 #ifndef EDSPARSER_EDS_HPP
 #define EDSPARSER_EDS_HPP
 
@@ -11,6 +12,7 @@
 #include <iostream>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace edsparser {
@@ -58,6 +60,8 @@ public:
         size_t num_degenerate_symbols = 0, num_common_chars = 0, total_change_size = 0, num_empty_strings = 0;
         size_t num_paths = 0, max_paths_per_string = 0;
         double avg_paths_per_string = 0.0;
+        std::vector<Position> cum_common_positions;   // n+1: common characters in front of symbol i (empty for an empty EDS)
+        std::vector<int> cum_degenerate_counts;       // n+1: degenerate strings in front of symbol i
     };
     const Metadata& get_metadata() const { return metadata_; }
 
@@ -98,7 +102,26 @@ public:
     std::streampos get_base_position(Position pos) const { return metadata_.base_positions[pos]; }
     Length get_string_length(size_t string_id) const { return metadata_.string_lengths[string_id]; }
 
+    // Query side (reference eds.cpp:673-1418).
+    // `count` patterns of `pattern_length` characters, one per line: a uniform start among the common characters, one
+    // uniform string per symbol, wrapping to symbol (length % n) when the EDS ends first.  Seeded from std::random_device.
+    void generate_patterns(std::ostream& os, size_t count, Length pattern_length) const;
+    // The same with a fixed seed: deterministic, and byte-equal to edsx_eds_genpatterns for the same seed.
+    void generate_patterns(std::ostream& os, size_t count, Length pattern_length, uint64_t seed) const;
+    // Strings of symbols [pos, pos + len) (clipped at the end), changes[i] picking the string of symbol pos + i.
+    String extract(Position pos, Length len, const std::vector<int>& changes) const;
+    // Does `pattern` occur at common position `common_pos` with these degenerate strings (numbered over all
+    // degenerate symbols) chosen in walk order?  With sources the chosen strings must share a path.
+    bool check_position(Position common_pos, const std::vector<int>& degenerate_strings, const String& pattern) const;
+
 private:
+    size_t find_symbol_at_common_position(Position common_pos, Position& offset_out) const;
+    std::pair<size_t, size_t> decode_degenerate_string_number(int abs_string_num) const;
+    String reconstruct_from_memory(size_t start_symbol, Position offset_in_symbol, const std::vector<int>& degenerate_strings,
+                                   Length pattern_length) const;
+    std::set<int> calculate_path_intersection(size_t start_symbol, Position offset_in_symbol,
+                                              const std::vector<int>& degenerate_strings, Length pattern_length) const;
+
     void parse(const std::string& text);
     void parse_sources(const std::string& text);
     void rebuild_metadata();

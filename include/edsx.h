@@ -174,6 +174,34 @@ typedef struct {
 int edsx_eds_stats(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                    uint32_t context_len, edsx_eds_statistics* out);
 
+/* ---- queries: pattern sampling and position checks (EDS::generate_patterns / EDS::check_position) ----
+ * The text is tokenised as for edsx_leds_merge; parse errors as there.
+ * edsx_eds_genpatterns: count patterns of pattern_length characters, each followed by '\n' (count * (pattern_length + 1)
+ * bytes), the bytes of EDS::generate_patterns(os, count, pattern_length, seed).  Draw k of pattern i is
+ * hash3(seed, i, k) (k = 0 the start among the common characters, k = 1, 2, ... the strings in walk order, then the
+ * wrap), bounded by the high 64 bits of r * bound.  An empty EDS, pattern_length 0, and a wrap-around that reaches a
+ * symbol without a non-empty string are EDSX_ERR_INVALID_PARAMETER; count 0 gives an empty buffer.  Witnesses (all three
+ * NULL, or all three set): witness_pos = the start common position of every pattern (uint64; UINT64_MAX when the pattern
+ * wrapped or the EDS has no common character), witness_off (uint64, count + 1) / witness_deg (int32) = the degenerate
+ * string numbers each pattern chose, as CSR (none for a UINT64_MAX pattern).  EDS::check_position(pos, choices, pattern)
+ * holds for every other pattern when no sources are given. */
+int edsx_eds_genpatterns(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t count, uint32_t pattern_length,
+                         uint64_t seed, edsx_buf* patterns, edsx_buf* witness_pos, edsx_buf* witness_off, edsx_buf* witness_deg);
+/* n queries as CSR: query q asks EDS::check_position(common_pos[q], choices[choice_off[q] .. choice_off[q+1]),
+ * patterns[pattern_off[q] .. pattern_off[q+1])) of the .eds (+ .seds: the chosen strings must share a path; seds NULL:
+ * no sources).  status_out[q]: 1 true, 0 false, -1 std::out_of_range, -2 std::invalid_argument (also for offsets that
+ * decrease or pass choice_off[n] / pattern_off[n]). */
+int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                             size_t n, const uint64_t* common_pos, const uint64_t* choice_off, const int32_t* choices,
+                             const uint64_t* pattern_off, const uint8_t* patterns, int8_t* status_out);
+/* Of the last edsx_eds_genpatterns / edsx_eds_check_positions on this context: the EDS's counts and where the time
+ * went (tokenise: host clock around the upload and tokeniser; tables / kernels: device events; download: host clock). */
+typedef struct {
+    uint64_t n_symbols, n_strings, n_chars, num_common_chars, num_degenerate_strings;
+    double tokenise_ms, tables_ms, kernel_ms, download_ms;
+} edsx_query_info;
+int edsx_query_last_info(const edsx_ctx* ctx, edsx_query_info* out);
+
 /* ---- synthetic inputs: genrandomeds-shaped .eds + .seds generated in HBM ----
  * Flags and shape of src/cpp/tools/genrandomeds.cpp:383-405 / :221-352 (reference uniform over `alphabet`, single-position
  * variant sites with min_alt..max_alt alternatives, snp_ratio SNPs, else insertions of 1..var_len_max characters /
