@@ -26,6 +26,17 @@ class VcfStats(ctypes.Structure):
                  "skipped_unsupported_sv", "variant_groups")]
 
 
+class Contig(ctypes.Structure):
+    """One FASTA record of a VcfSession (edsx_contig)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("name_off", "name_len", "rec_start", "rec_end", "seq_start", "line_width",
+                                                "seq_size", "vcf_records", "duplicate")]
+
+
+class VcfSessionStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("records_total", "records_without_token", "records_unknown_contig",
+                                                "vcf_h2d_bytes", "fasta_h2d_bytes")] + [("classified_on_device", ctypes.c_int)]
+
+
 class VcfMultiInfo(ctypes.Structure):
     _fields_ = [("partitioned", ctypes.c_int), ("fasta_windowed", ctypes.c_int)] + \
                [(n, ctypes.c_uint64) for n in ("records_min", "records_max", "moved_line_bytes", "fasta_h2d_bytes_max")]
@@ -112,6 +123,17 @@ def load_library():
                                       P(_Buf), P(_Buf), P(ctypes.c_uint64)]
     lib.edsx_leds_tokenised_on_device.argtypes = [ctypes.c_void_p]
     lib.edsx_vcf_tokenised_on_device.argtypes = [ctypes.c_void_p]
+    lib.edsx_vcf_session_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                          P(ctypes.c_void_p)]
+    lib.edsx_vcf_session_contigs.argtypes = [ctypes.c_void_p, P(P(Contig)), P(ctypes.c_size_t)]
+    lib.edsx_vcf_session_find.argtypes = [ctypes.c_void_p, ctypes.c_char_p, P(ctypes.c_size_t)]
+    lib.edsx_vcf_session_transform.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
+    lib.edsx_vcf_session_info.argtypes = [ctypes.c_void_p, P(VcfSessionStats)]
+    lib.edsx_vcf_session_unknown_contigs.argtypes = [ctypes.c_void_p, P(_Buf)]
+    lib.edsx_vcf_session_close.argtypes = [ctypes.c_void_p]
+    lib.edsx_vcf_session_close.restype = None
+    lib.edsx_vcf_transform_contig.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                              ctypes.c_char_p, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
     lib.edsx_leds_merge_range.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                                           ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           P(_Buf), P(_Buf), P(ctypes.c_int), P(ctypes.c_int)]
@@ -404,12 +426,23 @@ class Context:
                                                 ctypes.byref(n)))
         return self._take(e), self._take(s), n.value
 
-    def vcf_transform(self, vcf, fasta, context_len=0):
+    def vcf_transform(self, vcf, fasta, context_len=0, contig=None):
+        """contig=None: the first FASTA record, CHROM ignored (the reference's rule).  contig=name: the record lines whose
+        first token is `name` over the first FASTA record of that name (edsx_vcf_transform_contig)."""
         e, s, st = _Buf(), _Buf(), VcfStats()
         vcf, fasta = bytes(vcf), bytes(fasta)
-        self._check(self._lib.edsx_vcf_transform(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
-                                                 ctypes.byref(e), ctypes.byref(s), ctypes.byref(st)))
+        if contig is None:
+            rc = self._lib.edsx_vcf_transform(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
+                                              ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
+        else:
+            name = contig.encode() if isinstance(contig, str) else bytes(contig)
+            rc = self._lib.edsx_vcf_transform_contig(self._h, vcf, len(vcf), fasta, len(fasta), name, context_len,
+                                                     ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
+        self._check(rc)
         return self._take(e), self._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+
+    def vcf_session(self, vcf, fasta):
+        return VcfSession(self, vcf, fasta)
 
     def vcf_tokenised_on_device(self):
         return bool(self._lib.edsx_vcf_tokenised_on_device(self._h))
@@ -547,3 +580,69 @@ class Context:
             self._check(self._lib.edsx_msa_synth_device(self._h, d_out, capacity, n_rows, col0, n_cols,
                                                         variant_fraction, seed, stream, ctypes.byref(w)))
         return int(w.value)
+
+
+class VcfSession:
+    """A multi-contig VCF and a multi-record FASTA kept in HBM (edsx_vcf_session_*): the FASTA record index, the contig of
+    every record line, and one transform per contig without another upload.  vcf=b"": the FASTA index alone."""
+
+    def __init__(self, ctx, vcf, fasta):
+        self._ctx, self._lib = ctx, ctx._lib
+        self._vcf, self._fasta = bytes(vcf), bytes(fasta)          # the library reads them until close()
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.edsx_vcf_session_open(ctx._h, self._vcf, len(self._vcf), self._fasta, len(self._fasta),
+                                                   ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.edsx_vcf_session_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def contigs(self):
+        """FASTA records in file order: dicts of the edsx_contig fields plus "name" (bytes)."""
+        p, n = ctypes.POINTER(Contig)(), ctypes.c_size_t()
+        self._ctx._check(self._lib.edsx_vcf_session_contigs(self._h, ctypes.byref(p), ctypes.byref(n)))
+        out = []
+        for i in range(n.value):
+            d = {f: int(getattr(p[i], f)) for f, _ in Contig._fields_}
+            d["name"] = self._fasta[d["name_off"]:d["name_off"] + d["name_len"]]
+            out.append(d)
+        return out
+
+    def find(self, name):
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        i = ctypes.c_size_t()
+        self._ctx._check(self._lib.edsx_vcf_session_find(self._h, name, ctypes.byref(i)))
+        return i.value
+
+    def transform(self, contig, context_len=0):
+        """contig: a record index, or a name (its first record).  (eds, seds, stats) as Context.vcf_transform."""
+        index = contig if isinstance(contig, int) else self.find(contig)
+        e, s, st = _Buf(), _Buf(), VcfStats()
+        self._ctx._check(self._lib.edsx_vcf_session_transform(self._h, index, context_len, ctypes.byref(e), ctypes.byref(s),
+                                                              ctypes.byref(st)))
+        return self._ctx._take(e), self._ctx._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+
+    def info(self):
+        st = VcfSessionStats()
+        self._ctx._check(self._lib.edsx_vcf_session_info(self._h, ctypes.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in VcfSessionStats._fields_}
+
+    def unknown_contigs(self):
+        """[(name, record lines)] of the contigs the VCF names and the FASTA lacks."""
+        b = _Buf()
+        self._ctx._check(self._lib.edsx_vcf_session_unknown_contigs(self._h, ctypes.byref(b)))
+        return [(ln.rsplit(b"\t", 1)[0], int(ln.rsplit(b"\t", 1)[1])) for ln in self._ctx._take(b).split(b"\n") if ln]

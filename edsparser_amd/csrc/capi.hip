@@ -9,8 +9,10 @@
 #include "multi_gpu.hpp"
 #include "query_device.hpp"
 #include "synth.hpp"
+#include "vcf_contig.hpp"
 #include "vcf_device.hpp"
 
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -597,6 +599,129 @@ int edsx_vcf_transform(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const
         eds->size = e.size; eds->data = e.release();           // the download buffers themselves
         seds->size = s.size; seds->data = s.release();
     });
+}
+
+// ---- contig sessions (vcf_contig.hip)
+struct edsx_vcf_session {
+    edsx_ctx* ctx;
+    VcfSession s;
+    edsx_vcf_session(edsx_ctx* c, const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n)
+        : ctx(c), s(vcf, vcf_n, fasta, fasta_n) {}
+};
+static_assert(sizeof(edsx_contig) == sizeof(ContigRec) && offsetof(edsx_contig, duplicate) == offsetof(ContigRec, duplicate),
+              "edsx_contig is ContigRec");
+
+int edsx_vcf_session_open(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                          edsx_vcf_session** out)
+{
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        if (!out || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
+        static const uint8_t none = 0;
+        std::unique_ptr<edsx_vcf_session> s(new edsx_vcf_session(ctx, vcf ? vcf : &none, vcf_size, fasta ? fasta : &none, fasta_size));
+        s->s.open(nullptr);
+        *out = s.release();
+    });
+}
+
+int edsx_vcf_session_contigs(const edsx_vcf_session* s, const edsx_contig** records, size_t* n)
+{
+    if (!s || !records || !n) return EDSX_ERR_INVALID_PARAMETER;
+    *records = reinterpret_cast<const edsx_contig*>(s->s.contigs().data());
+    *n = s->s.contigs().size();
+    return EDSX_OK;
+}
+
+int edsx_vcf_session_find(const edsx_vcf_session* s, const char* name, size_t* index)
+{
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!name || !index) throw ParamError("null argument");
+        if (!s->s.find(name, *index)) throw ParamError("Contig '" + std::string(name) + "' not found in reference FASTA");
+    });
+}
+
+int edsx_vcf_session_transform(edsx_vcf_session* s, size_t index, uint32_t context_len, edsx_buf* eds, edsx_buf* seds,
+                               edsx_vcf_stats* stats)
+{
+    if (eds) { eds->data = nullptr; eds->size = 0; }
+    if (seds) { seds->data = nullptr; seds->size = 0; }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    edsx_ctx* ctx = s->ctx;
+    return guarded(ctx, [&] {
+        if (!eds || !seds) throw ParamError("null argument");
+        HostBytes e, q;
+        VcfCounters c;
+        try {
+            s->s.transform(ctx->vcf, index, e, q, c, nullptr);
+        } catch (...) {
+            if (stats) {   // as edsx_vcf_transform: the counters of the parse survive a later error
+                stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
+                stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
+            }
+            throw;
+        }
+        if (stats) {
+            stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
+            stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
+            stats->variant_groups = c.variant_groups;
+        }
+        if (context_len > 0) {
+            HostBytes lo, so;
+            ctx->merge.run(e.data, e.size, q.data, q.size, context_len, true, lo, so, nullptr);
+            eds->size = lo.size; eds->data = lo.release();
+            seds->size = so.size; seds->data = so.release();
+            return;
+        }
+        eds->size = e.size; eds->data = e.release();
+        seds->size = q.size; seds->data = q.release();
+    });
+}
+
+int edsx_vcf_session_info(const edsx_vcf_session* s, edsx_vcf_session_stats* out)
+{
+    if (!s || !out) return EDSX_ERR_INVALID_PARAMETER;
+    out->records_total = s->s.records_total; out->records_without_token = s->s.records_without_token;
+    out->records_unknown_contig = s->s.records_unknown;
+    out->vcf_h2d_bytes = s->s.vcf_h2d; out->fasta_h2d_bytes = s->s.fasta_h2d;
+    out->classified_on_device = s->s.classified_on_device ? 1 : 0;
+    return EDSX_OK;
+}
+
+int edsx_vcf_session_unknown_contigs(const edsx_vcf_session* s, edsx_buf* text)
+{
+    if (text) { text->data = nullptr; text->size = 0; }
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!text) throw ParamError("null argument");
+        const std::string& t = s->s.unknown_contigs();
+        take(text, t.size());
+        if (!t.empty()) std::memcpy(text->data, t.data(), t.size());
+    });
+}
+
+void edsx_vcf_session_close(edsx_vcf_session* s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    delete s;
+}
+
+int edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                              const char* contig, uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
+{
+    if (eds) { eds->data = nullptr; eds->size = 0; }
+    if (seds) { seds->data = nullptr; seds->size = 0; }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    edsx_vcf_session* s = nullptr;
+    int rc = edsx_vcf_session_open(ctx, vcf, vcf_size, fasta, fasta_size, &s);
+    if (rc != EDSX_OK) return rc;
+    size_t index = 0;
+    rc = edsx_vcf_session_find(s, contig, &index);
+    if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
+    edsx_vcf_session_close(s);                                   // (ctx->err stays: closing reports nothing)
+    return rc;
 }
 
 namespace {

@@ -1,0 +1,452 @@
+// vcf_contig.hip — contig selection in front of the VCF -> EDS pipeline (vcf_device.hip).
+//
+// "Contig c of (V, F)" is defined by reduction to the transform that exists: F_c is the first FASTA record named c,
+// V_c is V without the record lines whose first token is not c, and the result is edsx_vcf_transform(V_c, F_c).
+// The reference reads the first FASTA record only and never looks at CHROM (vcf_transforms.cpp:51-86, :232-326), so
+// users of multi-contig files had to split both on the host.  Here both texts go to HBM once and two passes run over them:
+//
+//   FASTA record index   k_fi_count / k_fi_fill: header starts ('>' at byte 0 or behind '\n') with the geometry of the
+//                        record-line passes (a wave owns 1 KB, 16-byte lane loads), plus the bytes of every block that
+//                        are not '\n'; k_fi_records: a thread per record derives name span, first sequence line and
+//                        seq_size from the scanned block counts — no walk longer than a block or a header line.
+//   contig of each line  k_vc_classify: a thread per record line hashes its first tab field (FNV-1a, through ByteWindow),
+//                        looks the hash up in the sorted name table and compares the bytes; the stable radix sort of
+//                        vcf_text_kernels.hpp regroups the line starts by record index, file order kept inside a contig.
+//
+// A transform then hands the pipeline one slice of the regrouped line starts and one record of the resident FASTA.
+// Lines whose first tab field is empty or holds whitespace are where the reference's tab split and its whitespace
+// fallback (:262-279) can disagree about the first token: such a file (and any with '\r') is classified on the host.
+#include "vcf_contig.hpp"
+#include "vcf_text_kernels.hpp"
+
+#include <chrono>
+
+namespace edsx {
+
+namespace {
+
+constexpr u64 FNV_OFFSET = 1469598103934665603ull, FNV_PRIME = 1099511628211ull;
+
+inline bool host_isspace(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // what operator>> skips ("C" locale)
+
+} // namespace
+
+// ---- FASTA record index ----------------------------------------------------------------------------------
+// bit i: byte i0 + i is a '>' that starts a line; nn: bytes of the chunk that are not '\n'
+__device__ __forceinline__ u32 fi_header_mask(const uint8_t* __restrict__ f, u64 n, u64 i0, u32& nn)
+{
+    nn = 0;
+    if (i0 >= n) return 0;
+    const uint4 v = *reinterpret_cast<const uint4*>(f + i0);              // (256-byte aligned buffer, 16 bytes of slack)
+    const u32 valid = n - i0 >= 16 ? 0xffffu : (1u << (n - i0)) - 1u;
+    const u32 nl = chunk_eq16b(v, 0x0a0a0a0au), gt = chunk_eq16b(v, 0x3e3e3e3eu);
+    const u32 prev_nl = ((nl << 1) | (i0 == 0 || f[i0 - 1] == '\n' ? 1u : 0u)) & 0xffffu;
+    nn = (u32)__builtin_popcount(~nl & valid);
+    return gt & prev_nl & valid;
+}
+static __global__ void __launch_bounds__(256) k_fi_count(const uint8_t* __restrict__ f, u64 n, u64* __restrict__ hdr, u64* __restrict__ nonnl)
+{
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    const u32 lane = threadIdx.x & 63;
+    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
+        u32 nn;
+        u32 c = (u32)__builtin_popcount(fi_header_mask(f, n, b * VT_BLOCK + lane * 16u, nn));
+        for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); nn += __shfl_xor(nn, o, 64); }
+        if (lane == 0) { hdr[b] = c; nonnl[b] = nn; }
+    }
+}
+static __global__ void __launch_bounds__(256) k_fi_fill(const uint8_t* __restrict__ f, u64 n, const u64* __restrict__ base, u64 nhdr,
+                                                        u64* __restrict__ hstart)
+{
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    const u32 lane = threadIdx.x & 63;
+    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
+        const u64 i0 = b * VT_BLOCK + lane * 16u;
+        u32 nn;
+        u32 m = fi_header_mask(f, n, i0, nn);
+        const u32 c = (u32)__builtin_popcount(m);
+        u32 incl = c;
+        for (int o = 1; o < 64; o <<= 1) { const u32 x = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += x; }
+        u64 at = base[b] + (incl - c);
+        while (m) { if (at < nhdr) hstart[at] = i0 + (u32)__builtin_ctz(m); at++; m &= m - 1; }
+    }
+}
+
+// nnpre[b] = bytes that are not '\n' in front of block b (b <= nblk; nnpre[nblk] = all of them)
+struct FiBlocks { const uint8_t* f; u64 n; const u64* nnpre; u64 nblk; };
+__device__ __forceinline__ u64 fi_newlines_before(const FiBlocks& k, u64 b)
+{
+    const u64 bytes = b * VT_BLOCK < k.n ? b * VT_BLOCK : k.n;
+    return bytes - k.nnpre[b];
+}
+// the first '\n' in [from, limit), or limit (limit <= n): the rest of from's block byte by byte, then a binary search over
+// the block counts for the next block that holds a newline, then that block
+__device__ u64 fi_next_newline(const FiBlocks& k, u64 from, u64 limit)
+{
+    if (from >= limit) return limit;
+    const u64 b = from / VT_BLOCK;
+    const u64 e = (b + 1) * VT_BLOCK < limit ? (b + 1) * VT_BLOCK : limit;
+    for (u64 i = from; i < e; i++) if (k.f[i] == '\n') return i;
+    if (e >= limit) return limit;
+    const u64 have = fi_newlines_before(k, b + 1);
+    u64 lo = b + 1, hi = (limit + VT_BLOCK - 1) / VT_BLOCK;                 // blocks [lo, hi) overlap [e, limit); hi <= nblk
+    const u64 end = hi;
+    while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (fi_newlines_before(k, mid + 1) > have) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= end) return limit;
+    const u64 e2 = (lo + 1) * VT_BLOCK < limit ? (lo + 1) * VT_BLOCK : limit;
+    for (u64 i = lo * VT_BLOCK; i < e2; i++) if (k.f[i] == '\n') return i;
+    return limit;
+}
+// bytes of [0, x) that are not '\n' (x <= n)
+__device__ u64 fi_nonnl_before(const FiBlocks& k, u64 x)
+{
+    const u64 b = x / VT_BLOCK;
+    u64 c = k.nnpre[b];
+    for (u64 i = b * VT_BLOCK; i < x; i++) c += k.f[i] != '\n';
+    return c;
+}
+static __global__ void k_fi_records(FiBlocks k, const u64* __restrict__ hstart, u64 nhdr, ContigRec* __restrict__ out)
+{
+    for (u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x; r < nhdr; r += (u64)gridDim.x * blockDim.x) {
+        const u64 rs = hstart[r], re = r + 1 < nhdr ? hstart[r + 1] : k.n;
+        const u64 hl = fi_next_newline(k, rs, re);                          // end of the header line
+        u64 ne = rs + 1;
+        while (ne < hl && k.f[ne] != ' ') ne++;
+        const u64 ss = hl < re ? hl + 1 : re;
+        ContigRec c;
+        c.name_off = rs + 1; c.name_len = ne - (rs + 1);
+        c.rec_start = rs; c.rec_end = re;
+        c.seq_start = ss; c.line_width = fi_next_newline(k, ss, re) - ss;
+        c.seq_size = fi_nonnl_before(k, re) - fi_nonnl_before(k, ss);
+        c.vcf_records = 0; c.duplicate = 0;
+        out[r] = c;
+    }
+}
+
+// ---- contig of every record line ---------------------------------------------------------------------------
+// names: the records that are not duplicates, sorted by the FNV-1a hash of their name
+struct VcTable { const u64* hash; const u32* rec; u32 T; const ContigRec* recs; const uint8_t* fasta; u64 nrecs; };
+struct VcCtl { u64 n, total, undecidable, oob; };
+
+static __global__ void k_vc_classify(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ lstart, u64 nrec, VcTable t,
+                                     u64* __restrict__ keys, VcCtl* ctl)
+{
+    bool und = false;
+    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
+        ByteWindow win(raw, n);
+        const u64 lo = lstart[j];
+        u64 i = lo, h = FNV_OFFSET;
+        bool ws = false;
+        for (; i < n; i++) {
+            const uint8_t ch = win[i];
+            if (ch == '\t' || ch == '\n') break;
+            ws |= ch == ' ' || ch == '\r' || ch == '\v' || ch == '\f';
+            h = (h ^ ch) * FNV_PRIME;
+        }
+        const u64 len = i - lo;
+        u64 key = t.nrecs;                                                  // no such contig
+        if (len == 0 || ws) und = true;                                     // tab rule and whitespace rule may differ: host
+        else {
+            u32 a = 0, b = t.T;
+            while (a < b) { const u32 m = a + (b - a) / 2; if (t.hash[m] < h) a = m + 1; else b = m; }
+            for (; a < t.T && t.hash[a] == h && key == t.nrecs; a++) {      // the hash finds, the bytes decide
+                const ContigRec& c = t.recs[t.rec[a]];
+                if (c.name_len != len) continue;
+                bool eq = true;
+                for (u64 x = 0; x < len && eq; x++) eq = win[lo + x] == t.fasta[c.name_off + x];
+                if (eq) key = t.rec[a];
+            }
+        }
+        if (win.oob) ctl->oob = win.oob;
+        keys[j] = key;
+    }
+    if (und) ctl->undecidable = 1;
+}
+// line starts in regrouped order, and the first line of every contig that has one (first[] is preset to ~0)
+static __global__ void k_vc_regroup(const u64* __restrict__ keys, const u32* __restrict__ order, const u64* __restrict__ lstart, u64 nrec,
+                                    u64* __restrict__ lsorted, u64* __restrict__ first)
+{
+    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
+        lsorted[j] = lstart[order[j]];
+        if (j == 0 || keys[j] != keys[j - 1]) first[keys[j]] = j;
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------
+namespace {
+
+u64 fnv1a(const uint8_t* p, size_t n)
+{
+    u64 h = FNV_OFFSET;
+    for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * FNV_PRIME;
+    return h;
+}
+
+// first token of a record line [p, p + n): the first maximal run of bytes that are not whitespace
+bool first_token(const uint8_t* p, size_t n, size_t& lo, size_t& len)
+{
+    size_t i = 0;
+    while (i < n && host_isspace(p[i])) i++;
+    size_t j = i;
+    while (j < n && !host_isspace(p[j])) j++;
+    lo = i; len = j - i;
+    return j > i;
+}
+
+} // namespace
+
+void VcfSession::index_fasta(hipStream_t st)
+{
+    const u64 n = fasta_n_;
+    if (n == 0 || fasta_[0] != '>') throw FormatError("Invalid FASTA format: expected header line starting with '>'");
+    d_fasta_.ensure(n + 16);
+    EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta_, n, hipMemcpyHostToDevice, st));
+    fasta_h2d += n;
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    DevBuf hdr, nonnl, tmp, ctl, hstart;
+    hdr.ensure(8 * (nblk + 2)); nonnl.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((nblk + 2) / SCAN_TILE + 4)); ctl.ensure(8 * 8);
+    u64 hctl[8] = {nblk, 0, 0, 0, 0, 0, 0, 0};
+    EDSX_HIP(hipMemcpyAsync(ctl.ptr, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
+    const uint8_t* f = d_fasta_.as<uint8_t>();
+    TraceSpan span(st, "fasta record index", n);
+    hipLaunchKernelGGL(k_fi_count, dim3(2048), dim3(256), 0, st, f, n, hdr.as<u64>(), nonnl.as<u64>());
+    exclusive_scan_u64(hdr.as<u64>(), hdr.as<u64>(), ctl.as<u64>() + 0, ctl.as<u64>() + 1, tmp.as<u64>(), st);
+    exclusive_scan_u64(nonnl.as<u64>(), nonnl.as<u64>(), ctl.as<u64>() + 0, nonnl.as<u64>() + nblk, tmp.as<u64>(), st);
+    EDSX_HIP(hipMemcpyAsync(hctl, ctl.ptr, sizeof(hctl), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    const u64 nhdr = hctl[1];                                               // >= 1: byte 0 is a '>'
+    if (nhdr == 0 || nhdr >= 0xffffffffull) throw DeviceError("FASTA record index: " + std::to_string(nhdr) + " records");
+    hstart.ensure(8 * (nhdr + 1));
+    d_recs_.ensure(sizeof(ContigRec) * (nhdr + 1));
+    hipLaunchKernelGGL(k_fi_fill, dim3(2048), dim3(256), 0, st, f, n, hdr.as<u64>(), nhdr, hstart.as<u64>());
+    hipLaunchKernelGGL(k_fi_records, dim3((unsigned)std::min<u64>((nhdr + 255) / 256, 1024)), dim3(256), 0, st, FiBlocks{f, n, nonnl.as<u64>(), nblk},
+                       hstart.as<u64>(), nhdr, d_recs_.as<ContigRec>());
+    span.end();
+    recs_.resize(nhdr);
+    EDSX_HIP(hipMemcpyAsync(recs_.data(), d_recs_.ptr, sizeof(ContigRec) * nhdr, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    for (size_t r = 0; r < recs_.size(); r++) {
+        ContigRec& c = recs_[r];
+        if (c.rec_start >= c.rec_end || c.rec_end > n || c.name_off + c.name_len > c.rec_end || c.seq_start > c.rec_end)
+            throw DeviceError("FASTA record index: record " + std::to_string(r) + " out of bounds");
+        const bool fresh = by_name_.emplace(std::string(reinterpret_cast<const char*>(fasta_ + c.name_off), c.name_len), r).second;
+        c.duplicate = fresh ? 0 : 1;
+    }
+}
+
+bool VcfSession::classify_device(hipStream_t st)
+{
+    { const char* e = getenv("EDSX_HOST_TOKENIZER"); if (e && atoi(e)) return false; }
+    const u64 n = vcf_n_;
+    if (!device_scratch_fits(6 * n)) return false;
+    d_vcf_.ensure(n + 16);
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    DevBuf idx, tmp, ctlb, lstart, keys, keys2, ord1, ord2, table, first, thash, trec;
+    idx.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((n + 2) / SCAN_TILE + 4)); ctlb.ensure(8 * 32);
+    VtCtl* ctl = ctlb.as<VtCtl>();
+    VcCtl* vctl = reinterpret_cast<VcCtl*>(ctlb.as<u64>() + 16);
+    VtCtl h{};
+    h.n = nblk;
+    EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemcpyAsync(d_vcf_.ptr, vcf_, n, hipMemcpyHostToDevice, st));
+    vcf_h2d += n;
+    const uint8_t* raw = d_vcf_.as<uint8_t>();
+    TraceSpan lines(st, "vcf line starts", 2 * n);     // (count pass + fill pass: the text is read twice)
+    hipLaunchKernelGGL(k_vt_line_count, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), ctl);
+    exclusive_scan_u64(idx.as<u64>(), idx.as<u64>(), &ctl->n, &ctl->nrec, tmp.as<u64>(), st);
+    EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    if (h.bad || h.nrec >= 0xffffffffull) return false;                     // '\r' somewhere, or too many lines
+    const u64 nr = h.nrec, K = recs_.size();
+    first_.assign(K + 2, ~0ull);
+    if (nr == 0) { lines.end(); records_total = 0; return true; }
+    lstart.ensure(8 * (nr + 1));
+    hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), lstart.as<u64>());
+    lines.end();
+
+    // name table: one entry per distinct name, sorted by hash
+    std::vector<std::pair<u64, u32>> tab;
+    tab.reserve(by_name_.size());
+    for (size_t r = 0; r < K; r++)
+        if (!recs_[r].duplicate) tab.push_back({fnv1a(fasta_ + recs_[r].name_off, recs_[r].name_len), (u32)r});
+    std::sort(tab.begin(), tab.end());
+    std::vector<u64> hh(tab.size());
+    std::vector<u32> hr(tab.size());
+    for (size_t i = 0; i < tab.size(); i++) { hh[i] = tab[i].first; hr[i] = tab[i].second; }
+    thash.ensure(8 * (tab.size() + 1)); trec.ensure(4 * (tab.size() + 1));
+    EDSX_HIP(hipMemcpyAsync(thash.ptr, hh.data(), 8 * hh.size(), hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemcpyAsync(trec.ptr, hr.data(), 4 * hr.size(), hipMemcpyHostToDevice, st));
+    VcCtl vz{};
+    EDSX_HIP(hipMemcpyAsync(vctl, &vz, sizeof(vz), hipMemcpyHostToDevice, st));
+    keys.ensure(8 * (nr + 2));
+    const VcTable t{thash.as<u64>(), trec.as<u32>(), (u32)tab.size(), d_recs_.as<ContigRec>(), d_fasta_.as<uint8_t>(), K};
+    TraceSpan cls(st, "contig classification", n);
+    hipLaunchKernelGGL(k_vc_classify, dim3(2048), dim3(256), 0, st, raw, n, lstart.as<u64>(), nr, t, keys.as<u64>(), vctl);
+    cls.end();
+    EDSX_HIP(hipMemcpyAsync(&vz, vctl, sizeof(vz), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));                                      // (hh, hr are uploaded)
+    if (vz.oob) throw DeviceError("contig classification: byte index " + std::to_string(vz.oob & ((1ull << 62) - 1)) +
+                                  " outside the text of " + std::to_string(n) + " bytes");
+    if (vz.undecidable) return false;
+
+    // stable regrouping by record index (K = no such contig, last): one 8-bit pass per byte of K
+    u32 passes = 1;
+    while (passes < 4 && (K >> (8 * passes))) passes++;
+    const u64 ntiles = (nr + RS_TILE - 1) / RS_TILE, nbins = 256 * ntiles;
+    keys2.ensure(8 * (nr + 2)); ord1.ensure(4 * (nr + 2)); ord2.ensure(4 * (nr + 2)); table.ensure(8 * (nbins + 2));
+    tmp.ensure(8 * (nbins / SCAN_TILE + 4));
+    first.ensure(8 * (K + 2));
+    lsorted_.ensure(8 * (nr + 2));
+    EDSX_HIP(hipMemcpyAsync(&vctl->n, &nbins, 8, hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemsetAsync(first.ptr, 0xff, 8 * (K + 2), st));
+    const unsigned grid = (unsigned)std::min<u64>(ntiles, 1u << 16);
+    TraceSpan srt(st, "regrouping (radix sort)", 0);
+    // keys -> (keys2, ord1) -> (keys, ord2) -> (keys2, ord1) ...
+    const u64* kin = keys.as<u64>();
+    const u32* vin = nullptr;
+    for (u32 p = 0; p < passes; p++) {
+        u64* kout = (p & 1) ? keys.as<u64>() : keys2.as<u64>();
+        u32* vout = (p & 1) ? ord2.as<u32>() : ord1.as<u32>();
+        hipLaunchKernelGGL(k_rs_hist, dim3(grid), dim3(64), 0, st, kin, nr, 8 * p, ntiles, table.as<u64>());
+        exclusive_scan_u64(table.as<u64>(), table.as<u64>(), &vctl->n, &vctl->total, tmp.as<u64>(), st);
+        hipLaunchKernelGGL(k_rs_scatter, dim3(grid), dim3(64), 0, st, kin, vin, nr, 8 * p, ntiles, table.as<u64>(), kout, vout);
+        kin = kout; vin = vout;
+    }
+    hipLaunchKernelGGL(k_vc_regroup, dim3(2048), dim3(256), 0, st, kin, vin, lstart.as<u64>(), nr, lsorted_.as<u64>(), first.as<u64>());
+    srt.end();
+    EDSX_HIP(hipMemcpyAsync(first_.data(), first.ptr, 8 * (K + 1), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    // counts: a contig's lines end where the next contig that has lines begins
+    u64 next = nr;
+    for (size_t r = K + 1; r-- > 0;) {
+        if (first_[r] == ~0ull) continue;
+        if (first_[r] >= next) throw DeviceError("contig regrouping: first lines out of order");
+        const u64 cnt = next - first_[r];
+        if (r < K) recs_[r].vcf_records = cnt; else records_unknown = cnt;
+        next = first_[r];
+    }
+    if (next != 0) throw DeviceError("contig regrouping: lines without a contig");
+    records_total = nr;
+    if (records_unknown) {                                                   // their names, for the caller's warnings
+        std::vector<u64> ls(records_unknown);
+        EDSX_HIP(hipMemcpy(ls.data(), lsorted_.as<u64>() + first_[K], 8 * records_unknown, hipMemcpyDeviceToHost));
+        std::unordered_map<std::string, size_t> at;
+        std::vector<std::pair<std::string, u64>> names;
+        for (u64 lo : ls) {
+            size_t e = lo;
+            while (e < n && vcf_[e] != '\t' && vcf_[e] != '\n') e++;
+            const auto ins = at.emplace(std::string(reinterpret_cast<const char*>(vcf_ + lo), e - lo), names.size());
+            if (ins.second) names.push_back({ins.first->first, 0});
+            names[ins.first->second].second++;
+        }
+        for (const auto& nm : names) unknown_text_ += nm.first + "\t" + std::to_string(nm.second) + "\n";
+    }
+    return true;
+}
+
+void VcfSession::classify_host()
+{
+    for (ContigRec& c : recs_) c.vcf_records = 0;
+    records_total = records_without_token = records_unknown = 0;
+    unknown_text_.clear();
+    std::unordered_map<std::string, size_t> at;
+    std::vector<std::pair<std::string, u64>> names;
+    std::string key;
+    for (size_t pos = 0; pos < vcf_n_;) {
+        const uint8_t* nl = static_cast<const uint8_t*>(memchr(vcf_ + pos, '\n', vcf_n_ - pos));
+        const size_t end = nl ? static_cast<size_t>(nl - vcf_) : vcf_n_;
+        if (end > pos && vcf_[pos] != '#') {
+            records_total++;
+            size_t lo, len;
+            if (!first_token(vcf_ + pos, end - pos, lo, len)) records_without_token++;
+            else {
+                key.assign(reinterpret_cast<const char*>(vcf_ + pos + lo), len);
+                const auto it = by_name_.find(key);
+                if (it != by_name_.end()) recs_[it->second].vcf_records++;
+                else {
+                    records_unknown++;
+                    const auto ins = at.emplace(key, names.size());
+                    if (ins.second) names.push_back({key, 0});
+                    names[ins.first->second].second++;
+                }
+            }
+        }
+        pos = nl ? end + 1 : vcf_n_;
+    }
+    for (const auto& nm : names) unknown_text_ += nm.first + "\t" + std::to_string(nm.second) + "\n";
+}
+
+void VcfSession::open(hipStream_t st)
+{
+    index_fasta(st);
+    classified_on_device = false;
+    if (vcf_n_ == 0) return;
+    classified_on_device = classify_device(st);
+    if (!classified_on_device) {
+        d_vcf_.release(); lsorted_.release();
+        classify_host();
+    }
+}
+
+bool VcfSession::find(const std::string& name, size_t& index) const
+{
+    const auto it = by_name_.find(name);
+    if (it == by_name_.end()) return false;
+    index = it->second;
+    return true;
+}
+
+// V_c: every line that is empty, starts with '#', or is a record line whose first token is the record's name
+void VcfSession::host_text_of(size_t index, std::vector<uint8_t>& out) const
+{
+    const ContigRec& c = recs_[index];
+    const uint8_t* name = fasta_ + c.name_off;
+    out.clear();
+    for (size_t pos = 0; pos < vcf_n_;) {
+        const uint8_t* nl = static_cast<const uint8_t*>(memchr(vcf_ + pos, '\n', vcf_n_ - pos));
+        const size_t end = nl ? static_cast<size_t>(nl - vcf_) : vcf_n_;
+        bool keep = end == pos || vcf_[pos] == '#';
+        if (!keep) {
+            size_t lo, len;
+            keep = first_token(vcf_ + pos, end - pos, lo, len) && len == c.name_len && memcmp(vcf_ + pos + lo, name, len) == 0;
+        }
+        const size_t upto = nl ? end + 1 : vcf_n_;
+        if (keep) out.insert(out.end(), vcf_ + pos, vcf_ + upto);
+        pos = upto;
+    }
+}
+
+void VcfSession::transform(VcfPipeline& pipe, size_t index, HostBytes& eds, HostBytes& seds, VcfCounters& stats, hipStream_t st)
+{
+    if (index >= recs_.size()) throw ParamError("contig index " + std::to_string(index) + " out of range");
+    const ContigRec& c = recs_[index];
+    if (c.duplicate)
+        throw ParamError("Contig '" + std::string(reinterpret_cast<const char*>(fasta_ + c.name_off), c.name_len) +
+                         "': record " + std::to_string(index) + " repeats the name of an earlier FASTA record");
+    VcfResident res;
+    res.d_fasta = d_fasta_.as<uint8_t>() + c.rec_start;
+    res.seq_size = c.seq_size;
+    const uint8_t* fa = fasta_ + c.rec_start;
+    const size_t fa_n = c.rec_end - c.rec_start;
+    static const uint8_t none = 0;
+    if (classified_on_device) {
+        res.d_vcf = d_vcf_.as<uint8_t>(); res.vcf_n = vcf_n_;
+        res.nrec = c.vcf_records;
+        res.d_lstart = c.vcf_records ? lsorted_.as<u64>() + first_[index] : lsorted_.as<u64>();
+        if (pipe.run(&none, 0, fa, fa_n, eds, seds, stats, st, VcfRange(), &res)) return;
+        res.d_vcf = nullptr; res.d_lstart = nullptr; res.nrec = 0;           // the tokeniser refuses these lines: host text
+    }
+    std::vector<uint8_t> text;
+    host_text_of(index, text);
+    try {
+        pipe.run(text.empty() ? &none : text.data(), text.size(), fa, fa_n, eds, seds, stats, st, VcfRange(), &res);
+    } catch (...) { vcf_h2d += pipe.vcf_h2d_bytes(); throw; }
+    vcf_h2d += pipe.vcf_h2d_bytes();
+}
+
+} // namespace edsx

@@ -1,0 +1,57 @@
+// vcf_contig.hpp — contig selection for vcf2eds: a multi-record FASTA and a multi-contig VCF stay in HBM, a FASTA record
+// index and a per-line contig classification are built in front of the pipeline that exists (see vcf_contig.hip).
+#pragma once
+
+#include "vcf_device.hpp"
+
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+namespace edsx {
+
+// one FASTA record (the layout of edsx_contig, include/edsx.h)
+struct ContigRec {
+    u64 name_off, name_len;        // name bytes inside the FASTA: behind '>' up to the first ' ' or the end of the header line
+    u64 rec_start, rec_end;        // the record: from its '>' up to the next '>' at a line start (or the end of the file)
+    u64 seq_start, line_width;     // first sequence line (vcf_transforms.cpp:59-67); seq_start == rec_end: no such line
+    u64 seq_size;                  // bytes of [seq_start, rec_end) that are not '\n' (:69-84)
+    u64 vcf_records;               // record lines of the VCF whose first token is this name
+    u64 duplicate;                 // 1: an earlier record has the same name
+};
+
+class VcfSession {
+public:
+    // both buffers stay the caller's and outlive the session
+    VcfSession(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n)
+        : vcf_(vcf), vcf_n_(vcf_n), fasta_(fasta), fasta_n_(fasta_n) {}
+    void open(hipStream_t st);
+
+    const std::vector<ContigRec>& contigs() const { return recs_; }
+    bool find(const std::string& name, size_t& index) const;       // first record of that name
+    // edsx_vcf_transform(V_c, F_c, 0) for record `index`, from the resident inputs where the device accepts them
+    void transform(VcfPipeline& pipe, size_t index, HostBytes& eds, HostBytes& seds, VcfCounters& stats, hipStream_t st);
+    // contigs the VCF names and the FASTA lacks, with their record lines, in order of first appearance per path:
+    // "name\tcount\n" each
+    const std::string& unknown_contigs() const { return unknown_text_; }
+
+    u64 records_total = 0, records_without_token = 0, records_unknown = 0, vcf_h2d = 0, fasta_h2d = 0;
+    bool classified_on_device = false;
+
+private:
+    void index_fasta(hipStream_t st);
+    bool classify_device(hipStream_t st);
+    void classify_host();
+    void host_text_of(size_t index, std::vector<uint8_t>& out) const;
+
+    const uint8_t* vcf_; size_t vcf_n_;
+    const uint8_t* fasta_; size_t fasta_n_;
+    std::vector<ContigRec> recs_;
+    std::unordered_map<std::string, size_t> by_name_;              // name -> first record
+    std::vector<u64> first_;                                       // per record: its first line in lsorted_ (device path)
+    std::string unknown_text_;
+    DevBuf d_fasta_, d_vcf_, lsorted_, d_recs_;
+};
+
+} // namespace edsx

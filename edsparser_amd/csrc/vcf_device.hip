@@ -19,7 +19,7 @@
 //                   hapchars, canonical (deduplicated) index per raw haplotype, carried[hap][sample]
 //                   bit matrix.
 #include "vcf_device.hpp"
-
+#include "vcf_text_kernels.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -484,29 +484,12 @@ __global__ void k_tail(VcfDev d, u64 cur, u64 clen, uint8_t* eo, uint8_t* so)
 // that are "." or all digits (<= 9), no '\r'.  Anything else — the whitespace-separated fallback of :262-279,
 // malformed lines, unsupported structural variants (their warnings are in file order), signs or junk that
 // std::stoull/stoi would swallow, POS 0 — raises `bad`, and the host tokeniser takes the whole file.
-struct VtCtl { u64 n, bad, nrec, max_samples, t_alt, t_altc, t_pair, t_all, oob; };
 
 struct VtSink {                      // fill pass: where record j's pieces go
     u64* altoff; u64 altc_base; uint8_t* altchars; u64* pa0; u64 all_base; int* alleles;
 };
 struct VtCounts { u64 pos; u64 reflen, nalt, altc, ngt, nall; };
 
-// The bytes of the VCF text through 8-byte aligned loads.  A thread walks its line from left to right, so seven of
-// eight byte reads come out of the register window instead of a one-byte load each (k_vt_count 0.80 -> 0.65 ms,
-// k_vt_fill 0.96 -> 0.75 ms per 10^6 records, round 2).  Bounds: the text buffer starts 256-byte aligned (hipMalloc) and
-// is allocated with at least 16 bytes of slack behind its n bytes (vt_raw_.ensure(n + 16)), so the aligned word that
-// holds a byte i < n - the only bytes ever asked for - ends at most 7 bytes behind n, inside the allocation.
-struct ByteWindow {
-    const u64* words; u64 nbytes; u64 at = ~0ull; u64 v = 0; u64 oob = 0;
-    __device__ __forceinline__ ByteWindow(const uint8_t* raw, u64 n) : words(reinterpret_cast<const u64*>(raw)), nbytes(n) {}
-    __device__ __forceinline__ uint8_t operator[](u64 i)
-    {
-        if (i >= nbytes) { oob = i | (1ull << 63); return (uint8_t)'\n'; }   // never asked for by a correct walk: reported, not read
-        const u64 wi = i >> 3;
-        if (wi != at) { at = wi; v = words[wi]; }
-        return (uint8_t)(v >> ((i & 7u) * 8u));
-    }
-};
 
 template <bool FILL>
 __device__ bool vt_parse(ByteWindow& raw, u64 lo, u64 hi, VtCounts& c, const VtSink& k)
@@ -572,54 +555,6 @@ __device__ bool vt_parse(ByteWindow& raw, u64 lo, u64 hi, VtCounts& c, const VtS
     return f >= 5;
 }
 
-// Record-line starts without a flag and an index word per input BYTE (that scratch, 16 B per byte, sent VCFs of more than
-// a few GB to the host tokeniser): a wave owns 1024 bytes of the text (16 per lane); pass 1 counts the line starts of
-// every such block, a scan over the BLOCK counts (8 B per KB of text) numbers them, pass 2 finds them again and writes
-// their positions.  A byte starts a record line iff it follows a newline (or is the first byte) and is neither a
-// newline nor '#'.
-constexpr u64 VT_BLOCK = 1024;
-__device__ __forceinline__ u32 chunk_eq16b(const uint4& a, uint32_t cccc)      // bit i: byte i equals c
-{
-    return eq_byte4(a.x, cccc) | (eq_byte4(a.y, cccc) << 4) | (eq_byte4(a.z, cccc) << 8) | (eq_byte4(a.w, cccc) << 12);
-}
-__device__ __forceinline__ u32 vt_line_start_mask(const uint8_t* __restrict__ raw, u64 n, u64 i0, bool& saw_cr)
-{
-    if (i0 >= n) return 0;
-    const uint4 v = *reinterpret_cast<const uint4*>(raw + i0);            // (the text buffer is 256-byte aligned, 16 bytes of slack)
-    const u32 nl = chunk_eq16b(v, 0x0a0a0a0au), hash = chunk_eq16b(v, 0x23232323u);
-    if (chunk_eq16b(v, 0x0d0d0d0du) & (n - i0 >= 16 ? 0xffffu : (1u << (n - i0)) - 1u)) saw_cr = true;
-    const u32 prev_nl = ((nl << 1) | (i0 == 0 || raw[i0 - 1] == '\n' ? 1u : 0u)) & 0xffffu;
-    u32 m = prev_nl & ~nl & ~hash;
-    if (n - i0 < 16) m &= (1u << (n - i0)) - 1u;
-    return m;
-}
-__global__ void __launch_bounds__(256) k_vt_line_count(const uint8_t* __restrict__ raw, u64 n, u64* __restrict__ cnt, VtCtl* ctl)
-{
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
-    const u32 lane = threadIdx.x & 63;
-    bool cr = false;
-    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
-        u32 c = (u32)__builtin_popcount(vt_line_start_mask(raw, n, b * VT_BLOCK + lane * 16u, cr));
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0) cnt[b] = c;
-    }
-    if (cr) ctl->bad = 1;
-}
-__global__ void __launch_bounds__(256) k_vt_line_fill(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ base, u64* __restrict__ lstart)
-{
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
-    const u32 lane = threadIdx.x & 63;
-    bool cr = false;
-    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
-        const u64 i0 = b * VT_BLOCK + lane * 16u;
-        u32 m = vt_line_start_mask(raw, n, i0, cr);
-        const u32 c = (u32)__builtin_popcount(m);
-        u32 incl = c;
-        for (int o = 1; o < 64; o <<= 1) { const u32 x = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += x; }
-        u64 at = base[b] + (incl - c);
-        while (m) { lstart[at++] = i0 + (u32)__builtin_ctz(m); m &= m - 1; }
-    }
-}
 __device__ __forceinline__ u64 vt_line_end(ByteWindow& raw, u64 lo, u64 n)
 {
     u64 hi = lo;
@@ -653,62 +588,6 @@ __global__ void k_vt_ascending(const u64* __restrict__ pos, u64 nrec, VtCtl* ctl
     bool un = false;
     for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j + 1 < nrec; j += (u64)gridDim.x * blockDim.x) un |= pos[j] >= pos[j + 1];
     if (un) ctl->t_alt = 1;                                      // scratch until the offset scans overwrite it
-}
-// ---- LSD radix sort of (u64 key, u32 value) pairs: eight stable passes of eight bits (unsorted VCFs with distinct
-// positions only; the usual VCF ascends and skips it).  A wave owns a tile of RS_TILE consecutive elements: pass 1 counts
-// its digits into a bin-major table (bin * ntiles + tile), one exclusive scan over the table gives every (bin, tile) its
-// first output position, pass 2 walks the tile 64 elements at a time - lanes with the same digit find each other with
-// one ballot per digit bit, their rank among them keeps the order stable - and moves the running positions in LDS.
-constexpr u32 RS_TILE = 2048;
-__global__ void __launch_bounds__(64) k_rs_hist(const u64* __restrict__ keys, u64 n, u32 shift, u64 ntiles, u64* __restrict__ table)
-{
-    __shared__ u32 hist[256];
-    const u32 lane = threadIdx.x;
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        for (u32 b = lane; b < 256; b += 64) hist[b] = 0;
-        __syncthreads();
-        const u64 base = tile * RS_TILE;
-        for (u32 o = lane; o < RS_TILE; o += 64)
-            if (base + o < n) atomicAdd(&hist[(u32)(keys[base + o] >> shift) & 0xffu], 1u);
-        __syncthreads();
-        for (u32 b = lane; b < 256; b += 64) table[(u64)b * ntiles + tile] = hist[b];
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(64) k_rs_scatter(const u64* __restrict__ keys, const u32* __restrict__ vals, u64 n, u32 shift,
-                                                   u64 ntiles, const u64* __restrict__ table, u64* __restrict__ keys_out,
-                                                   u32* __restrict__ vals_out)
-{
-    __shared__ u64 at[256];                                    // next output position of every digit of this tile
-    const u32 lane = threadIdx.x;
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        for (u32 b = lane; b < 256; b += 64) at[b] = table[(u64)b * ntiles + tile];
-        __syncthreads();
-        const u64 base = tile * RS_TILE;
-        for (u32 o = 0; o < RS_TILE && base + o < n; o += 64) {
-            const u64 i = base + o + lane;
-            const bool valid = i < n;
-            const u64 key = valid ? keys[i] : 0;
-            const u32 val = valid ? (vals ? vals[i] : (u32)i) : 0u;         // vals == nullptr: the element's index (first pass)
-            const u32 d = (u32)(key >> shift) & 0xffu;
-            u64 same = ballot64(valid);                                      // lanes with this lane's digit
-#pragma unroll
-            for (int b = 0; b < 8; b++) {
-                const u64 m = ballot64(valid && ((d >> b) & 1u));
-                same &= ((d >> b) & 1u) ? m : ~m;
-            }
-            const u32 rank = mbcnt(same);
-            if (valid) {
-                const u64 pos = at[d] + rank;
-                keys_out[pos] = key;
-                vals_out[pos] = val;
-            }
-            __syncthreads();                                                 // (one wave: every lane has read at[] before it moves)
-            if (valid && rank == 0) at[d] += (u64)__builtin_popcountll(same);
-            __syncthreads();
-        }
-        __syncthreads();
-    }
 }
 // counts in sorted order (inputs of the four offset scans)
 __global__ void k_vt_gather(VtRec r, const u32* __restrict__ order, u64 nrec, u64* __restrict__ a, u64* __restrict__ b,
@@ -977,6 +856,7 @@ bool VcfPipeline::tokenize_device(const uint8_t* vcf, size_t n, bool presorted, 
     h.n = nblk;                                                // element count of the block scan
     EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
     EDSX_HIP(hipMemcpyAsync(vt_raw_.ptr, vcf, n, hipMemcpyHostToDevice, st));
+    vcf_h2d_ = n;
     const uint8_t* raw = vt_raw_.as<uint8_t>();
     hipLaunchKernelGGL(k_vt_line_count, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_idx_.as<u64>(), ctl);
     exclusive_scan_u64(vt_idx_.as<u64>(), vt_idx_.as<u64>(), &ctl->n, &ctl->nrec, scan_tmp_.as<u64>(), st);
@@ -984,13 +864,33 @@ bool VcfPipeline::tokenize_device(const uint8_t* vcf, size_t n, bool presorted, 
     EDSX_HIP(hipStreamSynchronize(st));
     if (h.bad || h.nrec >= 0xffffffffull) return false;
     const u64 nr = h.nrec;
+    if (nr) {
+        vt_lstart_.ensure(8 * (nr + 1));
+        hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_idx_.as<u64>(), vt_lstart_.as<u64>());
+    }
+    return tokenize_lines(raw, n, vt_lstart_.as<u64>(), nr, presorted, st, nrec, max_samples, stats);
+}
+
+// The tokeniser proper: text that is in HBM (n bytes, 256-byte aligned, 16 bytes of slack behind them) and the starts of
+// the nr record lines to take from it, in file order.  tokenize_device hands over the whole file it has just uploaded, a
+// contig session (vcf_contig.hip) one contig's slice of its regrouped line starts.
+bool VcfPipeline::tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u64 nr, bool presorted, hipStream_t st, u64& nrec,
+                                 u64& max_samples, VcfCounters& stats)
+{
+    nrec = 0; max_samples = 0;
     stats.total_variants = stats.processed_variants = nr;
     if (nr == 0) return true;
-    vt_lstart_.ensure(8 * (nr + 1));
-    hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_idx_.as<u64>(), vt_lstart_.as<u64>());
+    if (nr >= 0xffffffffull) return false;
+    scan_tmp_.ensure(8 * ((nr + 2) / SCAN_TILE + 4));
+    ctl_.ensure(8 * 32);
+    VtCtl* ctl = reinterpret_cast<VtCtl*>(ctl_.as<u64>() + 16);
+    VtCtl h{};
+    EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
     for (DevBuf* b : {&vt_pos_, &vt_reflen_, &vt_nalt_, &vt_altc_, &vt_ngt_, &vt_nall_, &vt_s1_, &vt_s2_, &vt_s3_, &vt_s4_}) b->ensure(8 * (nr + 2));
     VtRec rec{vt_pos_.as<u64>(), vt_reflen_.as<u64>(), vt_nalt_.as<u64>(), vt_altc_.as<u64>(), vt_ngt_.as<u64>(), vt_nall_.as<u64>(), nullptr};
-    hipLaunchKernelGGL(k_vt_count, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_lstart_.as<u64>(), nr, rec, ctl);
+    TraceSpan count_span(st, "tokeniser count pass", 0);
+    hipLaunchKernelGGL(k_vt_count, dim3(2048), dim3(256), 0, st, raw, (u64)n, lstart, nr, rec, ctl);
+    count_span.end();
     hipLaunchKernelGGL(k_vt_ascending, dim3(1024), dim3(256), 0, st, vt_pos_.as<u64>(), nr, ctl);
     EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
@@ -1060,7 +960,7 @@ bool VcfPipeline::tokenize_device(const uint8_t* vcf, size_t n, bool presorted, 
     altoff_.ensure(8 * (h.t_alt + 2)); altchars_.ensure(h.t_altc + 16); pa0_.ensure(8 * (h.t_pair + 2)); alleles_.ensure(4 * (h.t_all + 4));
     VtOut o{start_.as<u64>(), reflen_.as<u64>(), alt0_.as<u64>(), altoff_.as<u64>(), altchars_.as<uint8_t>(), pair0_.as<u64>(),
             pa0_.as<u64>(), alleles_.as<int>(), vt_s2_.as<u64>(), vt_s4_.as<u64>()};
-    hipLaunchKernelGGL(k_vt_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_lstart_.as<u64>(), d_order, nr, o, ctl);
+    hipLaunchKernelGGL(k_vt_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, lstart, d_order, nr, o, ctl);
     EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
@@ -1152,8 +1052,8 @@ FaSlice VcfPipeline::fasta_slice(const uint8_t* fasta, u64 a, u64 b, u64 seq_sta
     return r;
 }
 
-void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n, HostBytes& eds,
-                      HostBytes& seds, VcfCounters& stats, hipStream_t st, const VcfRange& range)
+bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n, HostBytes& eds,
+                      HostBytes& seds, VcfCounters& stats, hipStream_t st, const VcfRange& range, const VcfResident* res)
 {
     // EDSX_TRACE=1: wall-clock of the host-visible stages on stderr (every mark follows a stream synchronisation)
     static const bool trace = [] { const char* e = getenv("EDSX_TRACE"); return e && atoi(e); }();
@@ -1165,20 +1065,27 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         t_last = now;
     };
     stats = VcfCounters();
-    fasta_h2d_ = 0;
+    fasta_h2d_ = 0; vcf_h2d_ = 0;
     // ---- FASTA metadata (:51-86)
     u64 seq_start, lw, seq_size, rest_from = 0;
     fasta_head(fasta, fasta_n, seq_start, lw, rest_from);
     seq_size = lw;                                             // + the later lines, counted on the device (below)
     const FastaMeta* meta = range.fasta;
+    FastaMeta res_meta;
+    const bool fasta_resident = res && res->d_fasta;
+    if (fasta_resident) { res_meta.seq_size = res->seq_size; res_meta.regular = false; meta = &res_meta; }   // (the index counted it)
     mark("fasta metadata");
     // ---- VCF records (:690-712) and the unstable sort (:715-718)
     std::vector<VcfPart> parts;
     std::vector<u64> part_base;                              // first global record index of every part
     std::vector<std::pair<u64, u32>> order;                  // (pos, global index in file order), sorted by pos
     u64 dev_nrec = 0, dev_max_samples = 0;
-    const bool on_device = tokenize_device(vcf, vcf_n, range.presorted, st, dev_nrec, dev_max_samples, stats);
+    const bool lines_resident = res && res->d_vcf;
+    const bool on_device = lines_resident ? tokenize_lines(res->d_vcf, res->vcf_n, res->d_lstart, res->nrec, range.presorted, st,
+                                                           dev_nrec, dev_max_samples, stats)
+                                          : tokenize_device(vcf, vcf_n, range.presorted, st, dev_nrec, dev_max_samples, stats);
     tokenised_on_device_ = on_device;
+    if (lines_resident && !on_device) { stats = VcfCounters(); return false; }   // the caller builds the text on the host
     mark(on_device ? "device tokenise" : "device tokenise attempt");
     if (!on_device) {
         stats = VcfCounters();
@@ -1221,9 +1128,12 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         up1 = std::max(up0, std::min<u64>(off(p1) + 16, fasta_n));
     }
     const u64 up_n = up1 - up0, cbase = window ? up0 : seq_start;
-    d_fasta_.ensure(up_n + 16);
-    if (up_n) EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta + up0, up_n, hipMemcpyHostToDevice, st));
-    fasta_h2d_ = up_n;
+    if (!fasta_resident) {
+        d_fasta_.ensure(up_n + 16);
+        if (up_n) EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta + up0, up_n, hipMemcpyHostToDevice, st));
+        fasta_h2d_ = up_n;
+    }
+    const uint8_t* const dfa = fasta_resident ? res->d_fasta : d_fasta_.as<uint8_t>();
     const u64 body = window ? up_n : fasta_n > seq_start ? fasta_n - seq_start : 0;
     const u64 nblk = (body + 255) / 256;
     ctl_.ensure(8 * 32);
@@ -1236,15 +1146,15 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     hctl[12] = fasta_n;                                      // record end (atomicMin), [13] bytes of the later lines
     EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
     if (!meta && rest_from < fasta_n) {
-        hipLaunchKernelGGL(k_fa_record_end, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), (u64)fasta_n, rest_from, ctl + 12);
-        hipLaunchKernelGGL(k_fa_seq_bytes, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), rest_from, ctl + 12, ctl + 13);
+        hipLaunchKernelGGL(k_fa_record_end, dim3(1024), dim3(256), 0, st, dfa, (u64)fasta_n, rest_from, ctl + 12);
+        hipLaunchKernelGGL(k_fa_seq_bytes, dim3(1024), dim3(256), 0, st, dfa, rest_from, ctl + 12, ctl + 13);
     }
     if (nblk) {
         // (window: the buffer is the window, compacted from its first byte)
         const u64 kn = window ? up_n : fasta_n, ks = window ? 0 : seq_start;
-        hipLaunchKernelGGL(k_fa_count, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), kn, ks, blkpre_.as<u64>(), nblk);
+        hipLaunchKernelGGL(k_fa_count, dim3(1024), dim3(256), 0, st, dfa, kn, ks, blkpre_.as<u64>(), nblk);
         exclusive_scan_u64(blkpre_.as<u64>(), blkpre_.as<u64>(), ctl + 0, ctl + 1, scan_tmp_.as<u64>(), st);
-        hipLaunchKernelGGL(k_fa_compact, dim3(1024), dim3(256), 0, st, d_fasta_.as<uint8_t>(), kn, ks, blkpre_.as<u64>(), nblk,
+        hipLaunchKernelGGL(k_fa_compact, dim3(1024), dim3(256), 0, st, dfa, kn, ks, blkpre_.as<u64>(), nblk,
                            refc_.as<uint8_t>());
     }
     EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
@@ -1254,7 +1164,7 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     mark("fasta upload, metadata, compaction");
 
     VcfDev d{};
-    d.fasta = d_fasta_.as<uint8_t>() + (cbase - up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
+    d.fasta = dfa + (cbase - up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
     d.refc = refc_.as<uint8_t>(); d.refc_n = refc_n; d.blkpre = blkpre_.as<u64>();
     d.cbase = cbase; d.wend = up1; d.oob = window ? ctl + 20 : nullptr;          // (ctl[20] is zero from the upload above)
     auto window_check = [&](u64 v) {
@@ -1436,6 +1346,7 @@ void VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     window_check(oob);
     stats.variant_groups = ngrp;                             // :724-726
     mark("emit + download");
+    return true;
 }
 
 } // namespace edsx

@@ -1,0 +1,135 @@
+// vcf_text_kernels.hpp — device pieces that every pass over VCF text shares: the byte window, the record-line starts
+// and the stable LSD radix sort.  Used by the tokeniser (vcf_device.hip) and by the contig session (vcf_contig.hip);
+// the kernels are static, every translation unit that includes this gets its own copy.
+#pragma once
+
+#include "dev_util.hpp"
+
+namespace edsx {
+
+struct VtCtl { u64 n, bad, nrec, max_samples, t_alt, t_altc, t_pair, t_all, oob; };
+
+// The bytes of the VCF text through 8-byte aligned loads.  A thread walks its line from left to right, so seven of
+// eight byte reads come out of the register window instead of a one-byte load each (k_vt_count 0.80 -> 0.65 ms,
+// k_vt_fill 0.96 -> 0.75 ms per 10^6 records, round 2).  Bounds: the text buffer starts 256-byte aligned (hipMalloc) and
+// is allocated with at least 16 bytes of slack behind its n bytes (vt_raw_.ensure(n + 16)), so the aligned word that
+// holds a byte i < n - the only bytes ever asked for - ends at most 7 bytes behind n, inside the allocation.
+struct ByteWindow {
+    const u64* words; u64 nbytes; u64 at = ~0ull; u64 v = 0; u64 oob = 0;
+    __device__ __forceinline__ ByteWindow(const uint8_t* raw, u64 n) : words(reinterpret_cast<const u64*>(raw)), nbytes(n) {}
+    __device__ __forceinline__ uint8_t operator[](u64 i)
+    {
+        if (i >= nbytes) { oob = i | (1ull << 63); return (uint8_t)'\n'; }   // never asked for by a correct walk: reported, not read
+        const u64 wi = i >> 3;
+        if (wi != at) { at = wi; v = words[wi]; }
+        return (uint8_t)(v >> ((i & 7u) * 8u));
+    }
+};
+
+// Record-line starts without a flag and an index word per input BYTE (that scratch, 16 B per byte, sent VCFs of more than
+// a few GB to the host tokeniser): a wave owns 1024 bytes of the text (16 per lane); pass 1 counts the line starts of
+// every such block, a scan over the BLOCK counts (8 B per KB of text) numbers them, pass 2 finds them again and writes
+// their positions.  A byte starts a record line iff it follows a newline (or is the first byte) and is neither a
+// newline nor '#'.
+constexpr u64 VT_BLOCK = 1024;
+__device__ __forceinline__ u32 chunk_eq16b(const uint4& a, uint32_t cccc)      // bit i: byte i equals c
+{
+    return eq_byte4(a.x, cccc) | (eq_byte4(a.y, cccc) << 4) | (eq_byte4(a.z, cccc) << 8) | (eq_byte4(a.w, cccc) << 12);
+}
+__device__ __forceinline__ u32 vt_line_start_mask(const uint8_t* __restrict__ raw, u64 n, u64 i0, bool& saw_cr)
+{
+    if (i0 >= n) return 0;
+    const uint4 v = *reinterpret_cast<const uint4*>(raw + i0);            // (the text buffer is 256-byte aligned, 16 bytes of slack)
+    const u32 nl = chunk_eq16b(v, 0x0a0a0a0au), hash = chunk_eq16b(v, 0x23232323u);
+    if (chunk_eq16b(v, 0x0d0d0d0du) & (n - i0 >= 16 ? 0xffffu : (1u << (n - i0)) - 1u)) saw_cr = true;
+    const u32 prev_nl = ((nl << 1) | (i0 == 0 || raw[i0 - 1] == '\n' ? 1u : 0u)) & 0xffffu;
+    u32 m = prev_nl & ~nl & ~hash;
+    if (n - i0 < 16) m &= (1u << (n - i0)) - 1u;
+    return m;
+}
+static __global__ void __launch_bounds__(256) k_vt_line_count(const uint8_t* __restrict__ raw, u64 n, u64* __restrict__ cnt, VtCtl* ctl)
+{
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    const u32 lane = threadIdx.x & 63;
+    bool cr = false;
+    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
+        u32 c = (u32)__builtin_popcount(vt_line_start_mask(raw, n, b * VT_BLOCK + lane * 16u, cr));
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) cnt[b] = c;
+    }
+    if (cr) ctl->bad = 1;
+}
+static __global__ void __launch_bounds__(256) k_vt_line_fill(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ base, u64* __restrict__ lstart)
+{
+    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    const u32 lane = threadIdx.x & 63;
+    bool cr = false;
+    for (u64 b = (blockIdx.x * (u64)blockDim.x + threadIdx.x) >> 6; b < nblk; b += ((u64)gridDim.x * blockDim.x) >> 6) {
+        const u64 i0 = b * VT_BLOCK + lane * 16u;
+        u32 m = vt_line_start_mask(raw, n, i0, cr);
+        const u32 c = (u32)__builtin_popcount(m);
+        u32 incl = c;
+        for (int o = 1; o < 64; o <<= 1) { const u32 x = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += x; }
+        u64 at = base[b] + (incl - c);
+        while (m) { lstart[at++] = i0 + (u32)__builtin_ctz(m); m &= m - 1; }
+    }
+}
+
+// ---- LSD radix sort of (u64 key, u32 value) pairs: eight stable passes of eight bits (unsorted VCFs with distinct
+// positions only; the usual VCF ascends and skips it).  A wave owns a tile of RS_TILE consecutive elements: pass 1 counts
+// its digits into a bin-major table (bin * ntiles + tile), one exclusive scan over the table gives every (bin, tile) its
+// first output position, pass 2 walks the tile 64 elements at a time - lanes with the same digit find each other with
+// one ballot per digit bit, their rank among them keeps the order stable - and moves the running positions in LDS.
+constexpr u32 RS_TILE = 2048;
+static __global__ void __launch_bounds__(64) k_rs_hist(const u64* __restrict__ keys, u64 n, u32 shift, u64 ntiles, u64* __restrict__ table)
+{
+    __shared__ u32 hist[256];
+    const u32 lane = threadIdx.x;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        for (u32 b = lane; b < 256; b += 64) hist[b] = 0;
+        __syncthreads();
+        const u64 base = tile * RS_TILE;
+        for (u32 o = lane; o < RS_TILE; o += 64)
+            if (base + o < n) atomicAdd(&hist[(u32)(keys[base + o] >> shift) & 0xffu], 1u);
+        __syncthreads();
+        for (u32 b = lane; b < 256; b += 64) table[(u64)b * ntiles + tile] = hist[b];
+        __syncthreads();
+    }
+}
+static __global__ void __launch_bounds__(64) k_rs_scatter(const u64* __restrict__ keys, const u32* __restrict__ vals, u64 n, u32 shift,
+                                                   u64 ntiles, const u64* __restrict__ table, u64* __restrict__ keys_out,
+                                                   u32* __restrict__ vals_out)
+{
+    __shared__ u64 at[256];                                    // next output position of every digit of this tile
+    const u32 lane = threadIdx.x;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        for (u32 b = lane; b < 256; b += 64) at[b] = table[(u64)b * ntiles + tile];
+        __syncthreads();
+        const u64 base = tile * RS_TILE;
+        for (u32 o = 0; o < RS_TILE && base + o < n; o += 64) {
+            const u64 i = base + o + lane;
+            const bool valid = i < n;
+            const u64 key = valid ? keys[i] : 0;
+            const u32 val = valid ? (vals ? vals[i] : (u32)i) : 0u;         // vals == nullptr: the element's index (first pass)
+            const u32 d = (u32)(key >> shift) & 0xffu;
+            u64 same = ballot64(valid);                                      // lanes with this lane's digit
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                const u64 m = ballot64(valid && ((d >> b) & 1u));
+                same &= ((d >> b) & 1u) ? m : ~m;
+            }
+            const u32 rank = mbcnt(same);
+            if (valid) {
+                const u64 pos = at[d] + rank;
+                keys_out[pos] = key;
+                vals_out[pos] = val;
+            }
+            __syncthreads();                                                 // (one wave: every lane has read at[] before it moves)
+            if (valid && rank == 0) at[d] += (u64)__builtin_popcountll(same);
+            __syncthreads();
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace edsx

@@ -9,6 +9,100 @@
 
 using namespace edsparser;
 
+namespace {
+
+void print_statistics(const VCFStats& stats)
+{
+    std::cout << "Variant Processing Statistics:\n";
+    std::cout << "  Total variants read:        " << stats.total_variants << "\n";
+    std::cout << "  Successfully processed:     " << stats.processed_variants << "\n";
+    std::cout << "  Skipped (malformed):        " << stats.skipped_malformed << "\n";
+    std::cout << "  Skipped (unsupported SV):   " << stats.skipped_unsupported_sv << "\n";
+    std::cout << "  Total skipped:              " << stats.total_skipped() << "\n";
+    std::cout << "  Variant groups created:     " << stats.variant_groups << "\n";
+    if (stats.total_variants > 0) {
+        const double rate = (100.0 * stats.processed_variants) / stats.total_variants;
+        std::cout << "  Success rate:               " << std::fixed << std::setprecision(1) << rate << "%\n";
+    }
+    std::cout << "\n";
+}
+
+VCFStats to_stats(const edsx_vcf_stats& c)
+{
+    VCFStats s;
+    s.total_variants = c.total_variants; s.processed_variants = c.processed_variants;
+    s.skipped_malformed = c.skipped_malformed; s.skipped_unsupported_sv = c.skipped_unsupported_sv;
+    s.variant_groups = c.variant_groups;
+    return s;
+}
+
+struct Session {                                   // edsx_vcf_session, closed on every way out
+    edsx_vcf_session* h = nullptr;
+    ~Session() { edsx_vcf_session_close(h); }
+};
+
+// --all-chroms: one session, one pair of files per FASTA record that the VCF has record lines for.  false: a contig failed.
+bool transform_all_contigs(const tool::MappedFile& vcf_in, const tool::MappedFile& fasta_in, const std::filesystem::path& input_file,
+                           const std::filesystem::path& out_dir, Length context_length)
+{
+    edsx_ctx* ctx = detail::context();
+    Session ses;
+    int rc = edsx_vcf_session_open(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), &ses.h);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    const edsx_contig* recs = nullptr;
+    size_t nrecs = 0;
+    edsx_vcf_session_contigs(ses.h, &recs, &nrecs);
+    {
+        detail::Buf unknown;
+        rc = edsx_vcf_session_unknown_contigs(ses.h, &unknown.b);
+        if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+        std::istringstream lines(unknown.str());
+        for (std::string ln; std::getline(lines, ln);) {
+            const size_t tab = ln.rfind('\t');
+            std::cerr << "Warning: contig '" << ln.substr(0, tab) << "' has " << ln.substr(tab + 1)
+                      << " VCF record line(s) and no record in the reference FASTA\n";
+        }
+    }
+    std::filesystem::create_directories(out_dir);
+    const std::string stem = input_file.stem().string();
+    std::vector<std::pair<std::string, VCFStats>> done;
+    bool all_ok = true;
+    for (size_t i = 0; i < nrecs; i++) {
+        if (recs[i].duplicate || recs[i].vcf_records == 0) continue;
+        const std::string name(reinterpret_cast<const char*>(fasta_in.data() + recs[i].name_off), recs[i].name_len);
+        try {
+            if (name.empty() || name == "." || name == ".." || name.find('/') != std::string::npos || name.find('\0') != std::string::npos)
+                throw std::runtime_error("contig name cannot be used in a file name");
+            detail::Buf eds, seds;
+            edsx_vcf_stats cst{};
+            rc = edsx_vcf_session_transform(ses.h, i, context_length, &eds.b, &seds.b, &cst);
+            if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+            const std::string base = context_length > 0 ? stem + "." + name + "_l" + std::to_string(context_length) : stem + "." + name;
+            const std::filesystem::path eds_path = out_dir / (base + (context_length > 0 ? ".leds" : ".eds"));
+            const std::filesystem::path seds_path = out_dir / (base + ".seds");
+            tool::write_bytes(eds_path, eds.b.data, eds.b.size, "output");
+            tool::write_bytes(seds_path, seds.b.data, seds.b.size, "sources");
+            std::cout << "  Contig " << name << ": " << eds_path << ", " << seds_path << "\n";
+            done.push_back({name, to_stats(cst)});
+        } catch (const std::exception& e) {
+            std::cerr << "Error [" << name << "]: " << e.what() << "\n";
+            all_ok = false;
+        }
+    }
+    std::cout << "Transformation complete!\n\n";
+    for (const auto& d : done) {
+        std::cout << "Contig " << d.first << "\n";
+        print_statistics(d.second);
+    }
+    edsx_vcf_session_stats info{};
+    edsx_vcf_session_info(ses.h, &info);
+    std::cout << "VCF record lines: " << info.records_total << " total, " << info.records_without_token << " without a token, "
+              << info.records_unknown_contig << " of contigs the reference lacks\n\n";
+    return all_ok;
+}
+
+} // namespace
+
 int main(int argc, char** argv)
 {
     Timer timer;
@@ -21,6 +115,9 @@ int main(int argc, char** argv)
         opts.add("output", 'o', true, false, "Output EDS file (default: <input>.eds)");
         opts.add("sources", 's', true, false, "Output source file (default: <output>.seds)");
         opts.add("context-length", 'l', true, false, "Create l-EDS with minimum context length (0 = regular EDS)");
+        opts.add("chrom", 'c', true, false, "Transform one contig: the VCF records whose CHROM is NAME over the FASTA record NAME");
+        opts.add("all-chroms", 0, false, false, "Transform every contig of the reference that has VCF records: <stem>.<contig>.eds/.seds each");
+        opts.add("output-dir", 0, true, false, "Directory of the --all-chroms outputs (default: the input's directory)");
         opts.add("gpus", 'g', true, false, "Spread the records over this many GPUs of the node by reference position (RCCL exchanges; default 1)");
         opts.parse(argc, argv);
         if (opts.has("help")) {
@@ -33,7 +130,12 @@ int main(int argc, char** argv)
                          "  SNPs, small indels, <DEL>, <INS>, multi-allelic sites\n\n"
                          "EXAMPLES:\n"
                          "  vcf2eds -i variants.vcf -r ref.fa            # variants.eds + variants.seds\n"
-                         "  vcf2eds -i variants.vcf -r ref.fa --gpus 8   # position ranges on GPUs 0..7, over RCCL\n\n";
+                         "  vcf2eds -i variants.vcf -r ref.fa --gpus 8   # position ranges on GPUs 0..7, over RCCL\n"
+                         "  vcf2eds -i wgs.vcf -r hg38.fa --chrom chr21  # one contig of a multi-contig VCF and FASTA\n"
+                         "  vcf2eds -i wgs.vcf -r hg38.fa --all-chroms --output-dir out   # out/wgs.<contig>.eds + .seds\n\n"
+                         "CONTIGS:\n"
+                         "  Without --chrom / --all-chroms the first FASTA record is the reference and CHROM is\n"
+                         "  ignored, as the reference tool does.\n\n";
             tool::print_performance(timer);
             return 0;
         }
@@ -45,6 +147,15 @@ int main(int argc, char** argv)
         const Length context_length = static_cast<Length>(opts.get_unsigned("context-length", 0));
         const unsigned long ngpu = opts.has("gpus") ? opts.get_unsigned("gpus", 1) : 0;
         if (opts.has("gpus") && (ngpu == 0 || ngpu > 64)) throw std::runtime_error("--gpus must be between 1 and 64");
+        const bool all_chroms = opts.has("all-chroms"), one_chrom = opts.has("chrom");
+        const std::string chrom = opts.get("chrom");
+        if (all_chroms && one_chrom) throw std::runtime_error("--chrom and --all-chroms exclude each other");
+        if (all_chroms && (opts.has("output") || opts.has("sources")))
+            throw std::runtime_error("--all-chroms names its outputs itself (<stem>.<contig>.eds): use --output-dir, not -o / -s");
+        if (opts.has("output-dir") && !all_chroms) throw std::runtime_error("--output-dir needs --all-chroms");
+        if ((all_chroms || one_chrom) && opts.has("gpus"))
+            throw std::runtime_error("--chrom / --all-chroms cannot be combined with --gpus: contigs are transformed on one GPU");
+        if (one_chrom && chrom.empty()) throw std::runtime_error("--chrom needs a contig name");
 
         if (input_file.extension() != ".vcf") {
             std::cerr << "Error: Input file must be a VCF file (.vcf)\n";
@@ -69,6 +180,14 @@ int main(int argc, char** argv)
         }
         std::cout << "  Input: " << input_file << "\n";
         std::cout << "  Reference: " << reference_file << "\n";
+        if (one_chrom) std::cout << "  Contig: " << chrom << "\n";
+        if (all_chroms) {
+            std::cout << "  Contigs: every reference record with VCF records\n";
+            const std::filesystem::path dir = opts.has("output-dir") ? std::filesystem::path(opts.get("output-dir")) : input_file.parent_path();
+            const bool ok = transform_all_contigs(vcf_in, fasta_in, input_file, dir.empty() ? std::filesystem::path(".") : dir, context_length);
+            tool::print_performance(timer);
+            return ok ? 0 : 1;
+        }
 
         VCFStats stats;
         detail::Buf eds_out, seds_out;
@@ -97,8 +216,10 @@ int main(int argc, char** argv)
                                                                  : std::string(ngpu > 1 ? " (not partitioned: one GPU transforms the file)" : "")) << "\n";
         } else {
             edsx_ctx* ctx = detail::context();
-            const int rc = edsx_vcf_transform(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
-                                              &eds_out.b, &seds_out.b, &cst);
+            const int rc = one_chrom ? edsx_vcf_transform_contig(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(),
+                                                                 chrom.c_str(), context_length, &eds_out.b, &seds_out.b, &cst)
+                                     : edsx_vcf_transform(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
+                                                          &eds_out.b, &seds_out.b, &cst);
             take_stats();
             if (rc != EDSX_OK) detail::throw_status(rc, ctx);
         }
@@ -119,18 +240,7 @@ int main(int argc, char** argv)
         std::cout << "  Output: " << eds_path << "\n";
         std::cout << "  Sources: " << seds_path << "\n";
         std::cout << "\n";
-        std::cout << "Variant Processing Statistics:\n";
-        std::cout << "  Total variants read:        " << stats.total_variants << "\n";
-        std::cout << "  Successfully processed:     " << stats.processed_variants << "\n";
-        std::cout << "  Skipped (malformed):        " << stats.skipped_malformed << "\n";
-        std::cout << "  Skipped (unsupported SV):   " << stats.skipped_unsupported_sv << "\n";
-        std::cout << "  Total skipped:              " << stats.total_skipped() << "\n";
-        std::cout << "  Variant groups created:     " << stats.variant_groups << "\n";
-        if (stats.total_variants > 0) {
-            const double rate = (100.0 * stats.processed_variants) / stats.total_variants;
-            std::cout << "  Success rate:               " << std::fixed << std::setprecision(1) << rate << "%\n";
-        }
-        std::cout << "\n";
+        print_statistics(stats);
         tool::print_performance(timer);
         return 0;
     } catch (const std::exception& e) {

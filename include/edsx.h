@@ -97,10 +97,54 @@ int edsx_vcf_transform(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size,
                        const uint8_t* fasta, size_t fasta_size, uint32_t context_len,
                        edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats);
 
-/* 1 when the last edsx_vcf_transform / _range call on this context tokenised the VCF text on the GPU (plain files:
+/* 1 when the last edsx_vcf_transform / _range / session transform call on this context tokenised the VCF text on the GPU (plain files:
  * tab-separated lines without empty fields, POS all digits, no symbolic ALT other than <DEL>/<INS>, alleles "." or
  * digits, no '\r', no POS 0), 0 when the host tokeniser took the file (everything else). */
 int edsx_vcf_tokenised_on_device(const edsx_ctx* ctx);
+
+/* ---- contig selection: multi-contig VCF + multi-record FASTA ----
+ * The reference reads the first FASTA record only and never compares its name with CHROM (vcf_transforms.cpp:51-86),
+ * and edsx_vcf_transform reproduces that.  A session keeps both texts in HBM and transforms one contig at a time.
+ * "Contig c of (V, F)" is defined by reduction to edsx_vcf_transform:
+ *   F_c = the bytes of the first FASTA record named c.  A record starts at a '>' that is byte 0 of the file or follows
+ *         '\n' and ends in front of the next such '>' (or at the end of the file); its name is the header line behind
+ *         '>' up to the first ' ' (or the whole line).
+ *   V_c = V without the record lines (lines that are neither empty nor start with '#') whose first token - the first
+ *         maximal run of non-whitespace bytes - is not c.  A record line without a token belongs to no contig.
+ *   result = what edsx_vcf_transform(V_c, F_c, context_len) returns: texts, counters, status code and error text.
+ * Plain inputs are indexed, classified and tokenised on the device from the resident texts; a VCF with '\r', or with a
+ * record line whose first tab field is empty or holds whitespace, is classified on the host, and a contig whose lines the
+ * device tokeniser refuses is handed over as host text (outputs equal either way; EDSX_HOST_TOKENIZER=1 forces it). */
+typedef struct { uint64_t name_off, name_len,      /* name bytes inside the FASTA */
+                 rec_start, rec_end,               /* the record's bytes */
+                 seq_start, line_width, seq_size,  /* first sequence line and size as parse_fasta_metadata finds them */
+                 vcf_records,                      /* record lines of the VCF whose first token is this name */
+                 duplicate; } edsx_contig;         /* 1: an earlier record has the same name (never selected) */
+typedef struct { uint64_t records_total, records_without_token, records_unknown_contig,
+                 vcf_h2d_bytes, fasta_h2d_bytes;   /* raw input bytes copied to the device since open */
+                 int classified_on_device; } edsx_vcf_session_stats;
+typedef struct edsx_vcf_session edsx_vcf_session;
+
+/* Both buffers stay the caller's and must outlive the session.  vcf_size == 0: the session is the FASTA index alone.
+ * A FASTA that does not begin with '>' fails as edsx_vcf_transform does.  Errors of every session call are read with
+ * edsx_last_error(ctx); the context must outlive the session. */
+int  edsx_vcf_session_open(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                           edsx_vcf_session** out);
+/* the FASTA records in file order; the array lives as long as the session */
+int  edsx_vcf_session_contigs(const edsx_vcf_session* s, const edsx_contig** records, size_t* n);
+/* index of the first record of that name; none: EDSX_ERR_INVALID_PARAMETER,
+ * "Contig '<name>' not found in reference FASTA" */
+int  edsx_vcf_session_find(const edsx_vcf_session* s, const char* name, size_t* index);
+int  edsx_vcf_session_transform(edsx_vcf_session* s, size_t index, uint32_t context_len,
+                                edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats);
+int  edsx_vcf_session_info(const edsx_vcf_session* s, edsx_vcf_session_stats* out);
+/* contigs the VCF names and the FASTA lacks: "<name>\t<record lines>\n" each, in order of first appearance */
+int  edsx_vcf_session_unknown_contigs(const edsx_vcf_session* s, edsx_buf* text);
+void edsx_vcf_session_close(edsx_vcf_session* s);
+/* open + find + transform + close */
+int  edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                               const char* contig, uint32_t context_len, edsx_buf* eds, edsx_buf* seds,
+                               edsx_vcf_stats* stats);
 
 /* ---- multi-GPU VCF: partition by reference position ----
  * Groups of overlapping records (vcf_transforms.cpp:482-534) never span a cut placed at a group start, so
