@@ -66,6 +66,16 @@ class QueryInfo(ctypes.Structure):
                 [(n, ctypes.c_double) for n in ("tokenise_ms", "tables_ms", "kernel_ms", "download_ms")])
 
 
+class PathsInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_symbols", "n_strings", "n_chars", "num_paths", "n_choice_symbols")] + \
+               [("tokenised_on_device", ctypes.c_int)]
+
+
+class PathsTiming(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("tokenise_ms", "choose_ms", "scan_ms", "copy_ms", "download_ms")] + \
+               [("bytes_written", ctypes.c_uint64)]
+
+
 class MsaInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("n_rows", "n_cols", "line_width", "n_variant_cols", "n_segments", "msa_bytes",
@@ -187,6 +197,18 @@ def load_library():
     lib.edsx_eds_check_positions.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                              ctypes.c_size_t] + [ctypes.c_void_p] * 6
     lib.edsx_query_last_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
+    lib.edsx_paths_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                    P(ctypes.c_void_p)]
+    lib.edsx_paths_info.argtypes = [ctypes.c_void_p, P(PathsInfo)]
+    lib.edsx_paths_lengths.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    lib.edsx_paths_spell.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p,
+                                     ctypes.c_uint64, P(_Buf), ctypes.c_void_p]
+    lib.edsx_paths_last_timing.argtypes = [ctypes.c_void_p, P(PathsTiming)]
+    lib.edsx_paths_close.argtypes = [ctypes.c_void_p]
+    lib.edsx_paths_close.restype = None
+    lib.edsx_eds_spell_paths.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                         ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p, ctypes.c_uint64,
+                                         P(_Buf), ctypes.c_void_p]
     _LIB = lib
     return lib
 
@@ -444,6 +466,27 @@ class Context:
     def vcf_session(self, vcf, fasta):
         return VcfSession(self, vcf, fasta)
 
+    # ---- path spelling (eds2fasta)
+    def paths_open(self, eds, seds):
+        """A PathSession: the EDS + sEDS tokenised in HBM, for .info / .lengths / .spell."""
+        return PathSession(self, eds, seds)
+
+    def eds_spell_paths(self, eds, seds, paths=None, line_width=60, names=None, prefix=None):
+        """One-shot edsx_eds_spell_paths -> (fasta bytes, missing counts as numpy uint64)."""
+        import numpy as np
+        eds = bytes(eds)
+        sb = bytes(seds) if seds is not None else None
+        ids, nm, n_out = _path_args(paths, names)
+        if paths is None or len(ids) == 0:                       # all paths: P records, learnt from the text
+            n_out = max([int(x) for x in _re_ids(sb)] + [0]) if sb else 0
+        miss = np.zeros(max(n_out, 1), dtype=np.uint64)
+        f = _Buf()
+        self._check(self._lib.edsx_eds_spell_paths(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0,
+                                                   ids.ctypes.data if len(ids) else None, len(ids), nm,
+                                                   prefix.encode() if prefix is not None else None, int(line_width),
+                                                   ctypes.byref(f), miss.ctypes.data))
+        return self._take(f), miss[:n_out]
+
     def vcf_tokenised_on_device(self):
         return bool(self._lib.edsx_vcf_tokenised_on_device(self._h))
 
@@ -580,6 +623,102 @@ class Context:
             self._check(self._lib.edsx_msa_synth_device(self._h, d_out, capacity, n_rows, col0, n_cols,
                                                         variant_fraction, seed, stream, ctypes.byref(w)))
         return int(w.value)
+
+
+def _re_ids(seds):
+    import re
+    return re.findall(rb"\d+", seds)
+
+
+def _path_args(paths, names):
+    """(ids as numpy uint64, names as a char* array or None, number of records; 0 ids = all paths)"""
+    import numpy as np
+    ids = np.ascontiguousarray([] if paths is None else list(paths), dtype=np.uint64)
+    nm = None
+    if names is not None:
+        if len(names) != len(ids) or len(ids) == 0:
+            raise ValueError("names need one entry per explicitly requested path")
+        nm = (ctypes.c_char_p * len(ids))(*[x.encode() if isinstance(x, str) else bytes(x) for x in names])
+    return ids, nm, len(ids)
+
+
+class PathSession:
+    """An EDS with sources kept tokenised in HBM (edsx_paths_*): the sequence of every path as FASTA.  The session owns its
+    device tables: other calls on the context do not invalidate it."""
+
+    def __init__(self, ctx, eds, seds):
+        self._ctx, self._lib = ctx, ctx._lib
+        eds = bytes(eds)
+        sb = bytes(seds) if seds is not None else None
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.edsx_paths_open(ctx._h, eds, len(eds), sb, len(sb) if sb is not None else 0, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.edsx_paths_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def info(self):
+        i = PathsInfo()
+        self._ctx._check(self._lib.edsx_paths_info(self._h, ctypes.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in PathsInfo._fields_}
+
+    @property
+    def timing(self):
+        """Of the last lengths / spell: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
+        t = PathsTiming()
+        self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
+        return {n: getattr(t, n) for n, _ in PathsTiming._fields_}
+
+    def _ids(self, paths):
+        import numpy as np
+        if paths is None:
+            return np.arange(1, self.info["num_paths"] + 1, dtype=np.uint64)
+        return np.ascontiguousarray(list(paths), dtype=np.uint64)
+
+    def lengths(self, paths=None):
+        """(length, missing) as numpy uint64, one entry per requested path (None: all paths 1..P)."""
+        import numpy as np
+        ids = self._ids(paths)
+        ln, ms = np.zeros(len(ids), dtype=np.uint64), np.zeros(len(ids), dtype=np.uint64)
+        if len(ids):
+            self._ctx._check(self._lib.edsx_paths_lengths(self._h, ids.ctypes.data, len(ids), ln.ctypes.data, ms.ctypes.data))
+        return ln, ms
+
+    def spell(self, paths=None, line_width=60, names=None, prefix=None, as_numpy=False):
+        """(fasta, missing): FASTA of the requested paths in request order (None or empty: all paths 1..P), bytes - or,
+        as_numpy=True, a numpy uint8 array (texts above 2 GiB without another copy) - and the missing counts (numpy
+        uint64)."""
+        import numpy as np
+        ids, nm, n_out = _path_args(paths, names)
+        if len(ids) == 0:
+            n_out = self.info["num_paths"]
+        miss = np.zeros(max(n_out, 1), dtype=np.uint64)
+        f = _Buf()
+        self._ctx._check(self._lib.edsx_paths_spell(self._h, ids.ctypes.data if len(ids) else None, len(ids), nm,
+                                                    prefix.encode() if prefix is not None else None, int(line_width),
+                                                    ctypes.byref(f), miss.ctypes.data))
+        if as_numpy:
+            out = np.empty(f.size, dtype=np.uint8)
+            if f.size:
+                ctypes.memmove(out.ctypes.data, f.data, f.size)
+            self._lib.edsx_buf_free(ctypes.byref(f))
+            return out, miss[:n_out]
+        return self._ctx._take(f), miss[:n_out]
 
 
 class VcfSession:

@@ -7,6 +7,7 @@
 #include "merge_scan.hpp"
 #include "msa_device.hpp"
 #include "multi_gpu.hpp"
+#include "path_device.hpp"
 #include "query_device.hpp"
 #include "synth.hpp"
 #include "vcf_contig.hpp"
@@ -721,6 +722,94 @@ int edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size
     rc = edsx_vcf_session_find(s, contig, &index);
     if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
     edsx_vcf_session_close(s);                                   // (ctx->err stays: closing reports nothing)
+    return rc;
+}
+
+// ---- path sessions (path_device.hip)
+struct edsx_paths_session {
+    edsx_ctx* ctx;
+    PathPipeline p;
+};
+
+int edsx_paths_open(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                    edsx_paths_session** out)
+{
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        if (!out || (!eds && eds_size)) throw ParamError("null argument");
+        static const uint8_t none = 0;
+        std::unique_ptr<edsx_paths_session> s(new edsx_paths_session{ctx, {}});
+        s->p.open(eds ? eds : &none, eds_size, seds, seds_size, nullptr);
+        *out = s.release();
+    });
+}
+
+int edsx_paths_info(const edsx_paths_session* s, edsx_paths_info_t* out)
+{
+    if (!s || !out) return EDSX_ERR_INVALID_PARAMETER;
+    const PathInfo& i = s->p.info();
+    out->n_symbols = i.n_symbols; out->n_strings = i.n_strings; out->n_chars = i.n_chars; out->num_paths = i.num_paths;
+    out->n_choice_symbols = i.n_choice_symbols; out->tokenised_on_device = i.tokenised_on_device ? 1 : 0;
+    return EDSX_OK;
+}
+
+int edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, uint64_t* length, uint64_t* missing)
+{
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (n && (!ids || !length)) throw ParamError("null argument");
+        static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
+        s->p.lengths(reinterpret_cast<const u64*>(ids), n, reinterpret_cast<u64*>(length), reinterpret_cast<u64*>(missing), nullptr);
+    });
+}
+
+int edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                     uint64_t line_width, edsx_buf* fasta, uint64_t* missing)
+{
+    if (fasta) { fasta->data = nullptr; fasta->size = 0; }
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!fasta || (n && !ids)) throw ParamError("null argument");
+        std::vector<u64> all;
+        if (n == 0) {                                            // every path
+            if (names) throw ParamError("names need an explicit list of path ids");
+            all.resize(s->p.info().num_paths);
+            for (size_t k = 0; k < all.size(); k++) all[k] = k + 1;
+        }
+        if (names) for (size_t k = 0; k < n; k++) if (!names[k]) throw ParamError("null argument");
+        HostBytes out;
+        s->p.spell(n ? reinterpret_cast<const u64*>(ids) : all.data(), n ? n : all.size(), names, prefix, line_width, out,
+                   reinterpret_cast<u64*>(missing), nullptr);
+        fasta->size = out.size; fasta->data = out.release();     // the download buffer itself
+    });
+}
+
+int edsx_paths_last_timing(const edsx_paths_session* s, edsx_paths_timing* out)
+{
+    if (!s || !out) return EDSX_ERR_INVALID_PARAMETER;
+    const PathTiming& t = s->p.timing();
+    out->tokenise_ms = t.tokenise_ms; out->choose_ms = t.choose_ms; out->scan_ms = t.scan_ms; out->copy_ms = t.copy_ms;
+    out->download_ms = t.download_ms; out->bytes_written = t.bytes_written;
+    return EDSX_OK;
+}
+
+void edsx_paths_close(edsx_paths_session* s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    delete s;
+}
+
+int edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                         const uint64_t* ids, size_t n, const char* const* names, const char* prefix, uint64_t line_width,
+                         edsx_buf* fasta, uint64_t* missing)
+{
+    if (fasta) { fasta->data = nullptr; fasta->size = 0; }
+    edsx_paths_session* s = nullptr;
+    int rc = edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s);
+    if (rc != EDSX_OK) return rc;
+    rc = edsx_paths_spell(s, ids, n, names, prefix, line_width, fasta, missing);
+    edsx_paths_close(s);                                         // (ctx->err stays: closing reports nothing)
     return rc;
 }
 

@@ -1,0 +1,469 @@
+// path_device.hip — spell the sequence of every path of an EDS with sources on gfx950 (eds2fasta).
+//
+// The chosen string of path p at symbol i is the first string of the symbol, in file order, whose source set holds p
+// or 0; the sequence of p is the concatenation over the symbols, and a symbol without such a string adds one to
+// missing[p].  The kernels read what MergePipeline::prepare leaves in HBM (per symbol: size, first string,
+// single-string length; per string: str_off into the character pool, its path bitset of W words, bit 0 = universal).
+//
+//   open      k_path_flags   a symbol is FIXED when its one string is universal: every path takes it, so one shared
+//                            exclusive scan (cum_fixed) gives its share of every path's offsets; all other symbols
+//                            are CHOICE symbols, numbered by a second scan (rank) and listed by k_path_cidx
+//             k_path_or      OR of all sets: P is its highest bit
+//   per batch of K paths (K from free HBM: the tables are K x n_choice, never P x n)
+//             k_path_choose  one lane per (path, choice symbol): the chosen string and its length, missing counts
+//             one exclusive scan over the K rows laid end to end (row k's offsets are differences to its first entry)
+//             k_path_copy    one workgroup per (16 KiB of a path's FASTA body, path), paths fastest, so the K
+//                            workgroups that need the same stretch of the character pool run next to each other and
+//                            the pool comes from HBM about once per batch.  A workgroup finds its first symbol by a
+//                            256-way search, keeps the offsets and pool bases of its (up to 3072) symbols in LDS, and
+//                            every lane writes 16 bytes of OUTPUT at a time: the line feeds of the FASTA wrapping are
+//                            put in on the way (output byte o of a body holds sequence character
+//                            o - o / (line_width + 1)), one 16-byte load where the 16 bytes come out of one string,
+//                            and always one 16-byte store.
+#include "path_device.hpp"
+
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+
+namespace edsx {
+
+namespace {
+
+constexpr u64 NONE = ~0ull;
+constexpr int CP_THREADS = 256;
+constexpr u32 CP_TILE = 16384;       // output bytes per workgroup step: 4 chunks of 16 bytes per lane
+constexpr u32 CP_SYMS = 3072;        // symbols whose offsets and pool bases are kept in LDS per step (36 KiB)
+
+__global__ void k_path_flags(const u64* __restrict__ size, const u64* __restrict__ ent_off, const u64* __restrict__ len1,
+                             const u64* __restrict__ bits, u32 W, u64 n, u64* __restrict__ fx, u64* __restrict__ ch)
+{
+    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const bool fixed = size[i] == 1 && (bits[ent_off[i] * W] & 1);
+        fx[i] = fixed ? len1[i] : 0;
+        ch[i] = fixed ? 0 : 1;
+    }
+}
+
+__global__ void k_path_cidx(const u64* __restrict__ rank, u64 n, u64* __restrict__ cidx)
+{
+    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u64 r = rank[i];
+        if (rank[i + 1] != r) cidx[r] = i;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_path_or(const u64* __restrict__ bits, u32 W, u64 m, u64* __restrict__ orbits)
+{
+    const u64 t0 = blockIdx.x * (u64)blockDim.x + threadIdx.x, step = (u64)gridDim.x * blockDim.x;
+    for (u32 w = 0; w < W; w++) {
+        u64 o = 0;
+        for (u64 k = t0; k < m; k += step) o |= bits[k * W + w];
+        for (int sh = 32; sh > 0; sh >>= 1) o |= __shfl_xor(o, sh, 64);
+        if ((threadIdx.x & 63) == 0 && o) atomicOr((unsigned long long*)&orbits[w], (unsigned long long)o);
+    }
+}
+
+// csid / clen: K rows of nc entries; lanes run along a row, so the table writes and the reads of neighbouring symbols'
+// sets are contiguous
+__global__ void __launch_bounds__(256) k_path_choose(const u64* __restrict__ size, const u64* __restrict__ ent_off,
+                                                     const u64* __restrict__ str_off, const u64* __restrict__ bits, u32 W,
+                                                     const u64* __restrict__ cidx, u64 nc, const u64* __restrict__ ids, u64 K,
+                                                     u64* __restrict__ csid, u64* __restrict__ clen, u64* __restrict__ missing)
+{
+    const u64 total = K * nc;
+    for (u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x; t < total; t += (u64)gridDim.x * blockDim.x) {
+        const u64 k = t / nc, i = cidx[t - k * nc], p = ids[k];
+        const u64 e0 = ent_off[i], sz = size[i], w = p >> 6, bit = 1ull << (p & 63);
+        u64 sid = NONE;
+        for (u64 q = 0; q < sz; q++) {
+            const u64* b = bits + (e0 + q) * W;
+            if ((b[0] & 1) || (b[w] & bit)) { sid = e0 + q; break; }
+        }
+        csid[t] = sid;
+        clen[t] = sid == NONE ? 0 : str_off[sid + 1] - str_off[sid];
+        if (sid == NONE) atomicAdd((unsigned long long*)&missing[k], 1ull);
+    }
+}
+
+// S: the scanned rows (K * nc + 1 entries)
+__global__ void k_path_totals(const u64* __restrict__ S, u64 nc, u64 F, u64 K, u64* __restrict__ tot)
+{
+    const u64 k = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (k < K) tot[k] = F + (nc ? S[(k + 1) * nc] - S[k * nc] : 0);
+}
+
+__global__ void k_path_headers(const uint8_t* __restrict__ blob, const PathRec* __restrict__ rec, uint8_t* __restrict__ out)
+{
+    const PathRec r = rec[blockIdx.x];
+    const u64 len = r.body_off - r.rec_off;
+    for (u64 j = threadIdx.x; j < len; j += blockDim.x) out[r.rec_off + j] = blob[r.hdr_src + j];
+}
+
+struct CopyArgs {
+    const u64* ent_off; const u64* str_off; const uint8_t* chars;
+    const u64* cf; const u64* rank;            // n + 1 entries each
+    const u64* csid; const u64* S; u64 n, nc;  // choice tables (null when nc == 0)
+    const PathRec* rec; u64 nrec, max_tiles;
+    uint8_t* out;
+};
+
+// sequence offset of symbol i (0 <= i <= n) on the path of table row kb / nc
+__device__ __forceinline__ u64 sym_pos(const CopyArgs& a, u64 kb, u64 i)
+{
+    return a.cf[i] + (a.nc ? a.S[kb + a.rank[i]] - a.S[kb] : 0);
+}
+
+__device__ __forceinline__ void sym_load(const CopyArgs& a, u64 kb, u64 i, u64& pos, u64& s0, u64& len)
+{
+    const u64 r = a.rank[i];
+    const bool choice = a.rank[i + 1] != r;
+    pos = a.cf[i] + (a.nc ? a.S[kb + r] - a.S[kb] : 0);
+    const u64 sid = choice ? a.csid[kb + r] : a.ent_off[i];
+    if (sid == NONE) { s0 = 0; len = 0; return; }
+    s0 = a.str_off[sid];
+    len = a.str_off[sid + 1] - s0;
+}
+
+// largest i in [0, n) with sym_pos(i) <= q (sym_pos(0) = 0): the whole workgroup probes 256 points per round
+__device__ u64 block_find(const CopyArgs& a, u64 kb, u64 q)
+{
+    u64 lo = 0, hi = a.n;
+    while (hi - lo > 1) {
+        const u64 step = (hi - lo + CP_THREADS - 1) / CP_THREADS;
+        const u64 i = lo + threadIdx.x * step;
+        const int ok = i < hi && sym_pos(a, kb, i) <= q;
+        const int cnt = __syncthreads_count(ok);                 // the offsets ascend: the lanes that hold are a prefix
+        lo += (u64)(cnt - 1) * step;
+        hi = min(hi, lo + step);
+    }
+    return lo;
+}
+
+typedef unsigned __int128 u128;
+
+__global__ void __launch_bounds__(CP_THREADS) k_path_copy(CopyArgs a)
+{
+    // per step: for the symbols iA .. iA + cnt, where each begins on the path (relative to q0, saturated) and where
+    // its chosen string lies in the pool (pool offset minus path offset: character q of the path is chars[sbase + q])
+    __shared__ u32 spos[CP_SYMS + 1];
+    __shared__ u64 sbase[CP_SYMS];
+    const u64 work = a.max_tiles * a.nrec;
+    for (u64 wi = blockIdx.x; wi < work; wi += gridDim.x) {
+        const PathRec rc = a.rec[wi % a.nrec];
+        const u64 o0 = (wi / a.nrec) * CP_TILE;
+        if (o0 >= rc.body) continue;
+        const u64 o1 = min(rc.body, o0 + (u64)CP_TILE), per = rc.lw + 1, kb = rc.row * a.nc, last = rc.body - 1;
+        const u64 q0 = o0 - o0 / per, q1 = min(rc.L, o1 - o1 / per);      // this step spells characters [q0, q1)
+        u64 iA = 0, iB = 0;
+        u32 cnt = 0;
+        __syncthreads();                                                  // the last step's readers of the tables are through
+        if (q0 < q1) {
+            iA = block_find(a, kb, q0);
+            iB = block_find(a, kb, q1 - 1);
+            cnt = (u32)min((u64)CP_SYMS, iB - iA + 1);                    // (symbols behind the cached ones: from HBM)
+            for (u32 j = threadIdx.x; j <= cnt; j += CP_THREADS) {
+                u64 p, s0, len;
+                if (j < cnt) { sym_load(a, kb, iA + j, p, s0, len); sbase[j] = s0 - p; }
+                else p = sym_pos(a, kb, iA + j);
+                spos[j] = p <= q0 ? 0u : (u32)min(p - q0, 0xffffffffull);
+            }
+            __syncthreads();
+        }
+        auto find = [&](u64 q) -> u64 {                                    // symbol of character q, q0 <= q < q1
+            const u64 rel = q - q0;
+            if (rel < (u64)spos[cnt]) {
+                u32 lo = 0, hi = cnt;
+                while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if ((u64)spos[mid] <= rel) lo = mid; else hi = mid; }
+                return iA + lo;
+            }
+            u64 lo = iA + cnt, hi = iB + 1;
+            while (hi - lo > 1) { const u64 mid = lo + ((hi - lo) >> 1); if (sym_pos(a, kb, mid) <= q) lo = mid; else hi = mid; }
+            return lo;
+        };
+        auto sym = [&](u64 i, u64& end, u64& base) {                       // where symbol i's string ends on the path; its base
+            const u64 j = i - iA;
+            if (j < cnt) { end = q0 + spos[j + 1]; base = sbase[j]; return; }
+            u64 p, s0, len;
+            sym_load(a, kb, i, p, s0, len);
+            end = p + len; base = s0 - p;
+        };
+        for (u64 o = o0 + (u64)threadIdx.x * 16; o < o1; o += (u64)CP_THREADS * 16) {
+            const u32 nb = (u32)min((u64)16, o1 - o);
+            uint8_t* dst = a.out + rc.body_off + o;
+            u64 q = o - o / per;                                           // first character at or behind output byte o
+            const u64 nl1 = min((o / per + 1) * per - 1, last);            // first line feed at or behind o
+            u32 nn = 0;
+            if (nl1 < o + nb) {
+                nn = 1;
+                if (nl1 < last && min(nl1 + per, last) < o + nb) nn = 2;
+            }
+            if (nn == 1 && nb == 1) { dst[0] = '\n'; continue; }
+            u64 i = find(q), end, base;
+            sym(i, end, base);
+            if (nn <= 1 && q + (nb - nn) <= end) {                         // the chunk comes out of one string
+                const uint4 v = load16u(a.chars + (base + q));               // (the pool ends in 16 bytes of slack)
+                u128 x = ((u128)(((u64)v.w << 32) | v.z) << 64) | (((u64)v.y << 32) | v.x);
+                if (nn) {
+                    const u32 sh = 8u * (u32)(nl1 - o);
+                    const u128 mask = ((u128)1 << sh) - 1;
+                    x = (x & mask) | ((u128)'\n' << sh) | ((x & ~mask) << 8);
+                }
+                if (nb == 16) {
+                    const u64 lo = (u64)x, hi = (u64)(x >> 64);
+                    store16u(dst, make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)));
+                } else {
+                    for (u32 b = 0; b < nb; b++) dst[b] = (uint8_t)(x >> (8u * b));
+                }
+                continue;
+            }
+            u64 nl = nl1;                                                  // byte by byte across strings and short lines
+            u128 x = 0;
+            for (u32 b = 0; b < nb; b++) {
+                u32 c = '\n';
+                if (o + b == nl) nl = nl == last ? NONE : min(nl + per, last);
+                else {
+                    while (q >= end && i + 1 < a.n) { i++; sym(i, end, base); }
+                    c = q < end ? a.chars[(u64)(base + q)] : (u32)'?';
+                    q++;
+                }
+                x |= (u128)c << (8u * b);
+            }
+            if (nb == 16) {
+                const u64 lo = (u64)x, hi = (u64)(x >> 64);
+                store16u(dst, make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)));
+            } else {
+                for (u32 b = 0; b < nb; b++) dst[b] = (uint8_t)(x >> (8u * b));
+            }
+        }
+    }
+}
+
+double since_ms(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct EventPair {
+    hipEvent_t a, b;
+    EventPair() { EDSX_HIP(hipEventCreate(&a)); EDSX_HIP(hipEventCreate(&b)); }
+    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    float ms() const { float v = 0; EDSX_HIP(hipEventElapsedTime(&v, a, b)); return v; }
+};
+
+unsigned grid_for(u64 work) { return (unsigned)std::max<u64>(1, std::min<u64>((work + 255) / 256, 8192)); }
+
+u64 free_hbm()
+{
+    size_t free_b = 0, total_b = 0;
+    EDSX_HIP(hipMemGetInfo(&free_b, &total_b));
+    return free_b;
+}
+
+} // namespace
+
+void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, hipStream_t st)
+{
+    if (!seds) throw ParamError("Path spelling needs sources (.seds)");
+    info_ = PathInfo{};
+    timing_ = PathTiming{};
+    const auto t0 = std::chrono::steady_clock::now();
+    MergePipeline::Loaded L;
+    mp_.prepare(eds, eds_n, seds, seds_n, true, st, L);
+    n_ = L.n0; m_ = L.m; W_ = L.W; nc_ = 0; F_ = 0;
+    info_.tokenised_on_device = mp_.tokenised_on_device();
+    // what only the merge rounds and the tokenisers need goes back to the allocator: the session may live long
+    for (DevBuf* b : {&mp_.d_raw_, &mp_.tk_a_, &mp_.tk_b_, &mp_.tk_c_, &mp_.d_sym_first_, &mp_.left_, &mp_.right_, &mp_.elen_,
+                      &mp_.size_[1], &mp_.ent_off_[1], &mp_.len1_[1], &mp_.scan_tmp_})
+        b->release();
+    if (n_ == 0) { timing_.tokenise_ms = since_ms(t0); return; }              // empty EDS: P = 0
+    cum_fixed_.ensure(8 * (n_ + 1));
+    rank_.ensure(8 * (n_ + 1));
+    ctl_.ensure(8 * 8);
+    scan_tmp_.ensure(8 * 2 * (n_ / SCAN_TILE + 4));
+    tot_.ensure(8 * (size_t)W_);
+    u64 hn = n_;
+    EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &hn, 8, hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemsetAsync(tot_.ptr, 0, 8 * (size_t)W_, st));
+    u64 *cf = cum_fixed_.as<u64>(), *rk = rank_.as<u64>();
+    const u64* bits = mp_.bits_.as<u64>();
+    hipLaunchKernelGGL(k_path_flags, dim3(grid_for(n_)), dim3(256), 0, st, mp_.size_[0].as<u64>(), mp_.ent_off_[0].as<u64>(),
+                       mp_.len1_[0].as<u64>(), bits, W_, n_, cf, rk);
+    ScanSet<2> ss{{cf, rk}, {cf, rk}, {cf + n_, rk + n_}};
+    exclusive_scan_multi<2>(ss, ctl_.as<u64>(), scan_tmp_.as<u64>(), st);
+    hipLaunchKernelGGL(k_path_or, dim3(1024), dim3(256), 0, st, bits, W_, m_, tot_.as<u64>());
+    u64 h[3] = {0, 0, 0};
+    std::vector<u64> orb(W_, 0);
+    EDSX_HIP(hipMemcpyAsync(&h[0], cf + n_, 8, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(&h[1], rk + n_, 8, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(&h[2], mp_.d_str_off_.as<u64>() + m_, 8, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(orb.data(), tot_.ptr, 8 * (size_t)W_, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    F_ = h[0]; nc_ = h[1];
+    if (nc_) {
+        cidx_.ensure(8 * nc_);
+        hipLaunchKernelGGL(k_path_cidx, dim3(grid_for(n_)), dim3(256), 0, st, rk, n_, cidx_.as<u64>());
+        EDSX_HIP(hipStreamSynchronize(st));
+        EDSX_HIP(hipGetLastError());
+    }
+    u64 P = 0;
+    for (u32 w = 0; w < W_; w++)
+        if (orb[w]) P = 64ull * w + 63 - (u64)__builtin_clzll(orb[w]);
+    info_.n_symbols = n_; info_.n_strings = m_; info_.n_chars = h[2]; info_.num_paths = P; info_.n_choice_symbols = nc_;
+    timing_.tokenise_ms = since_ms(t0);
+}
+
+void PathPipeline::check_ids(const u64* ids, size_t n) const
+{
+    for (size_t k = 0; k < n; k++)
+        if (ids[k] == 0 || ids[k] > info_.num_paths)
+            throw ParamError("Path id " + std::to_string(ids[k]) + " out of range (1.." + std::to_string(info_.num_paths) + ")");
+}
+
+// EDSX_PATHS_BUDGET (bytes): stands in for the free HBM the batch sizes are taken from (the tests force several batches)
+u64 PathPipeline::budget_override()
+{
+    const char* e = getenv("EDSX_PATHS_BUDGET");
+    return e ? std::strtoull(e, nullptr, 10) : 0;
+}
+
+// paths per choice table: 16 bytes per (path, choice symbol) within a quarter of the free HBM
+u64 PathPipeline::table_batch(size_t n) const
+{
+    const u64 ov = budget_override(), budget = ov ? ov : free_hbm() / 4;
+    return std::max<u64>(1, std::min<u64>(n, budget / (16 * nc_ + 64)));
+}
+
+void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st)
+{
+    len.assign(K, 0); miss.assign(K, 0);
+    ids_.ensure(8 * K); miss_.ensure(8 * K); tot_.ensure(8 * K);
+    EDSX_HIP(hipMemcpyAsync(ids_.ptr, ids, 8 * K, hipMemcpyHostToDevice, st));
+    EDSX_HIP(hipMemsetAsync(miss_.ptr, 0, 8 * K, st));
+    EventPair ec, es;
+    const u64 cells = K * nc_;
+    if (nc_) {
+        csid_.ensure(8 * cells);
+        clen_.ensure(8 * (cells + 1));
+        scan_tmp_.ensure(8 * (cells / SCAN_TILE + 4));
+        ctl_.ensure(8 * 8);
+        EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &cells, 8, hipMemcpyHostToDevice, st));
+        EDSX_HIP(hipEventRecord(ec.a, st));
+        hipLaunchKernelGGL(k_path_choose, dim3(grid_for(cells)), dim3(256), 0, st, mp_.size_[0].as<u64>(), mp_.ent_off_[0].as<u64>(),
+                           mp_.d_str_off_.as<u64>(), mp_.bits_.as<u64>(), W_, cidx_.as<u64>(), nc_, ids_.as<u64>(), K,
+                           csid_.as<u64>(), clen_.as<u64>(), miss_.as<u64>());
+        EDSX_HIP(hipEventRecord(ec.b, st));
+        EDSX_HIP(hipEventRecord(es.a, st));
+        exclusive_scan_u64(clen_.as<u64>(), clen_.as<u64>(), ctl_.as<u64>(), clen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
+        EDSX_HIP(hipEventRecord(es.b, st));
+    }
+    hipLaunchKernelGGL(k_path_totals, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, clen_.as<u64>(), nc_, F_, K, tot_.as<u64>());
+    EDSX_HIP(hipMemcpyAsync(len.data(), tot_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(miss.data(), miss_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    if (nc_) { timing_.choose_ms += ec.ms(); timing_.scan_ms += es.ms(); }
+}
+
+void PathPipeline::lengths(const u64* ids, size_t n, u64* length, u64* missing, hipStream_t st)
+{
+    check_ids(ids, n);
+    const double tok = timing_.tokenise_ms;
+    timing_ = PathTiming{};
+    timing_.tokenise_ms = tok;
+    if (n == 0) return;
+    const u64 KT = table_batch(n);
+    std::vector<u64> len, miss;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const u64 K = std::min<u64>(KT, n - i0);
+        tables(ids + i0, K, len, miss, st);
+        std::memcpy(length + i0, len.data(), 8 * K);
+        if (missing) std::memcpy(missing + i0, miss.data(), 8 * K);
+    }
+}
+
+void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, HostBytes& out,
+                         u64* missing, hipStream_t st)
+{
+    check_ids(ids, n);
+    const double tok = timing_.tokenise_ms;
+    timing_ = PathTiming{};
+    timing_.tokenise_ms = tok;
+    out.take(0);
+    if (n == 0) return;
+    // header texts
+    std::string blob;
+    std::vector<u64> hoff(n + 1, 0);
+    const std::string pre = prefix ? prefix : "path";
+    for (size_t k = 0; k < n; k++) {
+        blob += '>';
+        if (names) blob += names[k]; else blob += pre + std::to_string(ids[k]);
+        blob += '\n';
+        hoff[k + 1] = blob.size();
+    }
+    // lengths of all requested paths; one table batch: its tables stay for the copy
+    const u64 KT = table_batch(n);
+    const bool single = KT >= n;
+    std::vector<u64> len(n), miss(n), bl, bm;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const u64 K = std::min<u64>(KT, n - i0);
+        tables(ids + i0, K, bl, bm, st);
+        std::memcpy(len.data() + i0, bl.data(), 8 * K);
+        std::memcpy(miss.data() + i0, bm.data(), 8 * K);
+    }
+    if (missing) std::memcpy(missing, miss.data(), 8 * n);
+    std::vector<PathRec> rec(n);
+    std::vector<u64> host_off(n + 1, 0);                        // record starts in the caller's buffer
+    for (size_t k = 0; k < n; k++) {
+        PathRec& r = rec[k];
+        r.L = len[k];
+        r.lw = (line_width == 0 || line_width > r.L) ? std::max<u64>(r.L, 1) : line_width;
+        r.body = r.L ? r.L + (r.L + r.lw - 1) / r.lw : 0;
+        r.hdr_src = hoff[k];
+        r.row = k % KT;
+        host_off[k + 1] = host_off[k] + (hoff[k + 1] - hoff[k]) + r.body;
+    }
+    const u64 total = host_off[n];
+    out.take(total);
+    timing_.bytes_written = total;
+    hdr_.ensure(blob.size());
+    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const size_t i1 = std::min<size_t>(n, i0 + KT);
+        if (!single) tables(ids + i0, i1 - i0, bl, bm, st);
+        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many records as the budget holds
+            size_t r1 = r0 + 1;
+            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
+            const u64 bytes = host_off[r1] - host_off[r0], nrec = r1 - r0;
+            u64 max_body = 0;
+            for (size_t k = r0; k < r1; k++) {
+                rec[k].rec_off = host_off[k] - host_off[r0];
+                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
+                max_body = std::max(max_body, rec[k].body);
+            }
+            out_.ensure(bytes + 16);                             // 16 bytes of slack behind the text, as every output buffer here
+            rec_.ensure(sizeof(PathRec) * nrec);
+            EDSX_HIP(hipMemcpyAsync(rec_.ptr, rec.data() + r0, sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
+            CopyArgs a{mp_.ent_off_[0].as<u64>(), mp_.d_str_off_.as<u64>(), mp_.d_chars_.as<uint8_t>(), cum_fixed_.as<u64>(),
+                       rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, nc_ ? clen_.as<u64>() : nullptr, n_, nc_,
+                       rec_.as<PathRec>(), nrec, (max_body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>()};
+            EventPair ev;
+            EDSX_HIP(hipEventRecord(ev.a, st));
+            hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
+            const u64 work = a.max_tiles * nrec;
+            if (work) hipLaunchKernelGGL(k_path_copy, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
+            EDSX_HIP(hipEventRecord(ev.b, st));
+            EDSX_HIP(hipStreamSynchronize(st));
+            EDSX_HIP(hipGetLastError());
+            timing_.copy_ms += ev.ms();
+            const auto t0 = std::chrono::steady_clock::now();
+            PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
+            timing_.download_ms += since_ms(t0);
+            r0 = r1;
+        }
+    }
+}
+
+} // namespace edsx

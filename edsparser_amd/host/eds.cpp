@@ -369,6 +369,39 @@ EDS EDS::merge_adjacent(size_t pos1, size_t pos2) const
     return out;
 }
 
+// ---- path spelling ---------------------------------------------------------------------------------------------
+
+int EDS::max_path_id() const
+{
+    int top = 0;
+    if (has_sources_ && n_ > 0)
+        for (const auto& ids : sources_)
+            if (!ids.empty()) top = std::max(top, *ids.rbegin());
+    return top;
+}
+
+String EDS::path_sequence(int path, size_t* missing) const
+{
+    if (!has_sources_) throw std::invalid_argument("Path spelling needs sources (.seds)");
+    const int top = max_path_id();
+    if (path < 1 || path > top)
+        throw std::invalid_argument("Path id " + std::to_string(path) + " out of range (1.." + std::to_string(top) + ")");
+    String out;
+    size_t miss = 0, sid = 0;
+    for (size_t i = 0; i < n_; ++i) {
+        const StringSet& set = sets_[i];
+        size_t j = 0;
+        for (; j < set.size(); ++j) {
+            const std::set<int>& ids = sources_[sid + j];
+            if (ids.count(path) || ids.count(0)) break;
+        }
+        if (j < set.size()) out += set[j]; else ++miss;
+        sid += set.size();
+    }
+    if (missing) *missing = miss;
+    return out;
+}
+
 // ---- query side ------------------------------------------------------------------------------------------------
 
 void EDS::generate_patterns(std::ostream& os, size_t count, Length pattern_length) const

@@ -36,6 +36,32 @@ void eds_to_leds_cartesian(std::istream& input, std::ostream& output, Length con
     run_merge(input, output, context_length, nullptr, nullptr, compact);
 }
 
+void eds_to_fasta(std::istream& eds_in, std::istream& seds_in, std::ostream& out, const std::vector<int>& paths,
+                  size_t line_width, const std::vector<std::string>* names, std::vector<size_t>* missing)
+{
+    if (names && names->size() != paths.size()) throw std::invalid_argument("eds_to_fasta: one name per requested path");
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    std::vector<const char*> np;
+    if (names) for (const auto& s : *names) np.push_back(s.c_str());
+    edsx_ctx* ctx = detail::context();
+    edsx_paths_session* s = nullptr;
+    int rc = edsx_paths_open(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                             reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), &s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    edsx_paths_info_t info;
+    edsx_paths_info(s, &info);
+    std::vector<uint64_t> miss(ids.empty() ? info.num_paths : ids.size());
+    detail::Buf fasta;
+    rc = edsx_paths_spell(s, ids.data(), ids.size(), names && !np.empty() ? np.data() : nullptr, nullptr, line_width, &fasta.b,
+                          miss.data());
+    edsx_paths_close(s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    out.write(reinterpret_cast<const char*>(fasta.b.data), static_cast<std::streamsize>(fasta.b.size));
+    if (missing) missing->assign(miss.begin(), miss.end());
+}
+
 bool is_leds(const EDS& eds, Length context_length)
 {
     if (context_length == 0) return true;

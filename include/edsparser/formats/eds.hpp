@@ -114,6 +114,13 @@ public:
     // degenerate symbols) chosen in walk order?  With sources the chosen strings must share a path.
     bool check_position(Position common_pos, const std::vector<int>& degenerate_strings, const String& pattern) const;
 
+    // Path spelling (the CPU counterpart of edsx_paths_spell).  max_path_id: the largest path id in the sources (0
+    // without sources or for an empty EDS).  path_sequence: per symbol the first string, in file order, whose source set
+    // holds `path` or 0, concatenated; *missing counts the symbols without one.  std::invalid_argument without sources
+    // ("Path spelling needs sources (.seds)") and for a path outside 1..max_path_id().
+    int max_path_id() const;
+    String path_sequence(int path, size_t* missing = nullptr) const;
+
 private:
     size_t find_symbol_at_common_position(Position common_pos, Position& offset_out) const;
     std::pair<size_t, size_t> decode_degenerate_string_number(int abs_string_num) const;

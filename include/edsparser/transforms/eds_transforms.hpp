@@ -7,6 +7,8 @@
 #include "../common.hpp"
 #include "../formats/eds.hpp"
 #include <iostream>
+#include <string>
+#include <vector>
 
 namespace edsparser {
 
@@ -22,6 +24,15 @@ void eds_to_leds_cartesian(std::istream& input, std::ostream& output, Length con
 // true iff no internal common block is shorter than context_length and no two degenerate
 // symbols are adjacent (host-side check on the container's metadata).
 bool is_leds(const EDS& eds, Length context_length);
+
+// eds2fasta: the sequence of the given paths (empty: all paths 1..P, P the largest id in the sources) of an EDS with
+// sources as FASTA, one record per requested path in request order, lines of line_width characters (0: one line).
+// Record k is named (*names)[k] when names is given, else "path<id>".  A path takes, per symbol, the first string whose
+// source set holds it or 0 (EDS::path_sequence); the spelling runs on the GPU (edsx_eds_spell_paths).  Returns the
+// number of symbols without a string per record when missing is given.  std::invalid_argument for a path outside 1..P.
+void eds_to_fasta(std::istream& eds, std::istream& seds, std::ostream& out, const std::vector<int>& paths = {},
+                  size_t line_width = 60, const std::vector<std::string>* names = nullptr,
+                  std::vector<size_t>* missing = nullptr);
 
 } // namespace edsparser
 

@@ -361,6 +361,45 @@ typedef struct {
 /* of the last edsx_leds_merge_multi */
 int  edsx_multi_last_merge(const edsx_multi* m, edsx_merge_multi_info* out);
 
+/* ---- eds2fasta: the sequence of every path of an EDS with sources (path_device.hip) ----
+ * The texts are parsed exactly as edsx_leds_merge parses them in LINEAR mode (same tokenisers, statuses and error
+ * texts).  P is the largest path id in the .seds (0 for an empty EDS).  The chosen string of path p (1 <= p <= P) at a
+ * symbol is the first string of the symbol, in file order, whose source set holds p or 0; the sequence of p is the
+ * concatenation over all symbols; a symbol without such a string contributes nothing and adds one to missing[p].
+ * A session keeps the tokenised EDS in HBM in tables of its own: other calls on the context do not invalidate it, and
+ * the input buffers may be released after edsx_paths_open.  seds == NULL: EDSX_ERR_INVALID_PARAMETER, "Path spelling
+ * needs sources (.seds)".  A path id of 0 or above P: EDSX_ERR_INVALID_PARAMETER, "Path id <p> out of range (1..<P>)".
+ * Errors are read through edsx_last_error of the context.
+ * (A .leds written with compact = 1 prints nothing for a single-string symbol whose string is empty; it then no longer
+ * matches its .seds in cardinality and is refused here as by edsx_leds_merge.  Write such files with compact = 0.) */
+typedef struct edsx_paths_session edsx_paths_session;
+typedef struct {
+    uint64_t n_symbols, n_strings, n_chars, num_paths /* P */, n_choice_symbols;
+    int tokenised_on_device;
+} edsx_paths_info_t;
+typedef struct {
+    double tokenise_ms, choose_ms, scan_ms, copy_ms, download_ms;   /* device events; download: host clock */
+    uint64_t bytes_written;                                         /* FASTA bytes of the last edsx_paths_spell */
+} edsx_paths_timing;
+int  edsx_paths_open(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                     edsx_paths_session** out);
+int  edsx_paths_info(const edsx_paths_session* s, edsx_paths_info_t* out);
+/* length[k] and missing[k] (may be NULL) of path ids[k]; duplicates allowed. */
+int  edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, uint64_t* length, uint64_t* missing);
+/* FASTA, one record per requested path in request order (n == 0: all paths 1..P): '>' name '\n', then the sequence in
+ * lines of line_width characters, each ended by '\n' (line_width == 0: one line; an empty sequence has no line).  The
+ * name is names[k] when names is given (n of them, n > 0), else prefix (NULL: "path") followed by the decimal id.
+ * missing (may be NULL): one count per record. */
+int  edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                      uint64_t line_width, edsx_buf* fasta, uint64_t* missing);
+/* of the last edsx_paths_lengths / edsx_paths_spell (tokenise_ms: of edsx_paths_open) */
+int  edsx_paths_last_timing(const edsx_paths_session* s, edsx_paths_timing* out);
+void edsx_paths_close(edsx_paths_session* s);
+/* open + spell + close */
+int  edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                          const uint64_t* ids, size_t n, const char* const* names, const char* prefix, uint64_t line_width,
+                          edsx_buf* fasta, uint64_t* missing);
+
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
  * accumulated over all plan/emit calls since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
  * total_ms[i] / launches[i] is the average duration of kernel names[i].  Returns the entry count. */
