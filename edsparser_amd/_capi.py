@@ -32,6 +32,16 @@ class Contig(ctypes.Structure):
                                                 "seq_size", "vcf_records", "duplicate")]
 
 
+class BgzfBlock(ctypes.Structure):
+    _fields_ = [("comp_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("comp_len", ctypes.c_uint32), ("isize", ctypes.c_uint32)]
+
+
+class GzInfo(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("inflated_on_device", ctypes.c_int)] + \
+               [(n, ctypes.c_uint64) for n in ("blocks", "comp_bytes", "text_bytes", "h2d_bytes", "text_d2h_bytes")] + \
+               [(n, ctypes.c_double) for n in ("index_ms", "inflate_ms", "crc_ms")]
+
+
 class VcfSessionStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("records_total", "records_without_token", "records_unknown_contig",
                                                 "vcf_h2d_bytes", "fasta_h2d_bytes")] + [("classified_on_device", ctypes.c_int)]
@@ -144,6 +154,15 @@ def load_library():
     lib.edsx_vcf_session_close.restype = None
     lib.edsx_vcf_transform_contig.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                               ctypes.c_char_p, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
+    lib.edsx_gz_probe.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
+    lib.edsx_bgzf_index.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(_Buf), P(ctypes.c_uint64)]
+    lib.edsx_gz_inflate.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, P(_Buf)]
+    lib.edsx_gz_last_info.argtypes = [ctypes.c_void_p, ctypes.c_int, P(GzInfo)]
+    lib.edsx_vcf_transform_z.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                         ctypes.c_char_p, ctypes.c_uint32, P(_Buf), P(_Buf), P(VcfStats)]
+    lib.edsx_vcf_session_open_z.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                            P(ctypes.c_void_p)]
+    lib.edsx_vcf_session_contig_name.argtypes = [ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), P(ctypes.c_size_t)]
     lib.edsx_leds_merge_range.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                                           ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           P(_Buf), P(_Buf), P(ctypes.c_int), P(ctypes.c_int)]
@@ -211,6 +230,30 @@ def load_library():
                                          P(_Buf), ctypes.c_void_p]
     _LIB = lib
     return lib
+
+
+def gz_probe(data):
+    """0 plain, 1 BGZF, 2 gzip (edsx_gz_probe: host only, never fails on garbage)."""
+    data = bytes(data)
+    kind = ctypes.c_int()
+    rc = load_library().edsx_gz_probe(data, len(data), ctypes.byref(kind))
+    if rc != 0:
+        raise EdsxError(rc, "edsx_gz_probe")
+    return kind.value
+
+
+def bgzf_index(data):
+    """([(comp_off, out_off, comp_len, isize)], text size) of a BGZF file (edsx_bgzf_index: host only)."""
+    data = bytes(data)
+    lib = load_library()
+    b, n = _Buf(), ctypes.c_uint64()
+    rc = lib.edsx_bgzf_index(data, len(data), ctypes.byref(b), ctypes.byref(n))
+    if rc != 0:
+        raise EdsxError(rc, "not a BGZF file")
+    raw = ctypes.string_at(b.data, b.size) if b.size else b""
+    lib.edsx_buf_free(ctypes.byref(b))
+    blocks = (BgzfBlock * (len(raw) // ctypes.sizeof(BgzfBlock))).from_buffer_copy(raw)
+    return [(int(x.comp_off), int(x.out_off), int(x.comp_len), int(x.isize)) for x in blocks], int(n.value)
 
 
 class MultiGpu:
@@ -340,7 +383,10 @@ class Context:
             raise EdsxError(rc, self._lib.edsx_last_error(self._h).decode(errors="replace"))
 
     def _take(self, b):
-        data = ctypes.string_at(b.data, b.size) if b.size else b""
+        if b.size < (1 << 31):
+            data = ctypes.string_at(b.data, b.size) if b.size else b""
+        else:                                                      # (string_at takes its size as a C int)
+            data = bytes((ctypes.c_char * b.size).from_address(b.data))
         self._lib.edsx_buf_free(ctypes.byref(b))
         return data
 
@@ -448,12 +494,30 @@ class Context:
                                                 ctypes.byref(n)))
         return self._take(e), self._take(s), n.value
 
-    def vcf_transform(self, vcf, fasta, context_len=0, contig=None):
+    def gz_inflate(self, data):
+        """inflate(data): BGZF on the device, any other gzip file on the host, plain bytes copied (edsx_gz_inflate)."""
+        data = bytes(data)
+        t = _Buf()
+        self._check(self._lib.edsx_gz_inflate(self._h, data, len(data), ctypes.byref(t)))
+        return self._take(t)
+
+    def gz_last_info(self, which=0):
+        """The compressed layer of the last gz_inflate / compressed=True call: which=0 the VCF (or the input), 1 the FASTA."""
+        info = GzInfo()
+        self._check(self._lib.edsx_gz_last_info(self._h, which, ctypes.byref(info)))
+        return {n: getattr(info, n) for n, _ in GzInfo._fields_}
+
+    def vcf_transform(self, vcf, fasta, context_len=0, contig=None, compressed=False):
         """contig=None: the first FASTA record, CHROM ignored (the reference's rule).  contig=name: the record lines whose
-        first token is `name` over the first FASTA record of that name (edsx_vcf_transform_contig)."""
+        first token is `name` over the first FASTA record of that name (edsx_vcf_transform_contig).
+        compressed=True: either input may be gzip or BGZF (edsx_vcf_transform_z); the result is that of the plain texts."""
         e, s, st = _Buf(), _Buf(), VcfStats()
         vcf, fasta = bytes(vcf), bytes(fasta)
-        if contig is None:
+        if compressed:
+            name = None if contig is None else contig.encode() if isinstance(contig, str) else bytes(contig)
+            rc = self._lib.edsx_vcf_transform_z(self._h, vcf, len(vcf), fasta, len(fasta), name, context_len,
+                                                ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
+        elif contig is None:
             rc = self._lib.edsx_vcf_transform(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
                                               ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
         else:
@@ -463,8 +527,8 @@ class Context:
         self._check(rc)
         return self._take(e), self._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
 
-    def vcf_session(self, vcf, fasta):
-        return VcfSession(self, vcf, fasta)
+    def vcf_session(self, vcf, fasta, compressed=False):
+        return VcfSession(self, vcf, fasta, compressed)
 
     # ---- path spelling (eds2fasta)
     def paths_open(self, eds, seds):
@@ -725,10 +789,16 @@ class VcfSession:
     """A multi-contig VCF and a multi-record FASTA kept in HBM (edsx_vcf_session_*): the FASTA record index, the contig of
     every record line, and one transform per contig without another upload.  vcf=b"": the FASTA index alone."""
 
-    def __init__(self, ctx, vcf, fasta):
+    def __init__(self, ctx, vcf, fasta, compressed=False):
         self._ctx, self._lib = ctx, ctx._lib
-        self._vcf, self._fasta = bytes(vcf), bytes(fasta)          # the library reads them until close()
+        self._compressed = compressed
         h = ctypes.c_void_p()
+        if compressed:                                             # gzip / BGZF inputs: the session owns what it needs
+            vcf, fasta = bytes(vcf), bytes(fasta)
+            ctx._check(self._lib.edsx_vcf_session_open_z(ctx._h, vcf, len(vcf), fasta, len(fasta), ctypes.byref(h)))
+            self._h = h
+            return
+        self._vcf, self._fasta = bytes(vcf), bytes(fasta)          # the library reads them until close()
         ctx._check(self._lib.edsx_vcf_session_open(ctx._h, self._vcf, len(self._vcf), self._fasta, len(self._fasta),
                                                    ctypes.byref(h)))
         self._h = h
@@ -757,7 +827,12 @@ class VcfSession:
         out = []
         for i in range(n.value):
             d = {f: int(getattr(p[i], f)) for f, _ in Contig._fields_}
-            d["name"] = self._fasta[d["name_off"]:d["name_off"] + d["name_len"]]
+            if self._compressed:                                   # (name_off points into the inflated FASTA)
+                q, ln = ctypes.c_char_p(), ctypes.c_size_t()
+                self._ctx._check(self._lib.edsx_vcf_session_contig_name(self._h, i, ctypes.byref(q), ctypes.byref(ln)))
+                d["name"] = ctypes.string_at(q, ln.value)
+            else:
+                d["name"] = self._fasta[d["name_off"]:d["name_off"] + d["name_len"]]
             out.append(d)
         return out
 

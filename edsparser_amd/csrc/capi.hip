@@ -1,6 +1,7 @@
 // capi.hip — the extern "C" boundary declared in include/edsx.h.  No exceptions cross it.
 #include "../../include/edsx.h"
 
+#include "bgzf_device.hpp"
 #include "genrandom.hpp"
 #include "genvcf.hpp"
 #include "merge_device.hpp"
@@ -38,6 +39,7 @@ struct edsx_ctx {
     std::unique_ptr<MsaPipeline> mini;       // column batches: the boundary segments are recomputed through a second pipeline
     DevBuf d_mini;
     int last_batches = 0;                    // of the last edsx_msa_transform / _batched: 1 = one piece
+    GzInfo gz[2];                            // compressed layer of the last *_z / edsx_gz_inflate call: VCF (or input), FASTA
 };
 
 namespace {
@@ -606,8 +608,18 @@ int edsx_vcf_transform(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const
 struct edsx_vcf_session {
     edsx_ctx* ctx;
     VcfSession s;
+    bool z = false;                          // opened on inflated inputs
+    GzInfo gz[2];                            // their compressed layer; every call of the session republishes it as the context's last info
     edsx_vcf_session(edsx_ctx* c, const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, size_t fasta_n)
         : ctx(c), s(vcf, vcf_n, fasta, fasta_n) {}
+    edsx_vcf_session(edsx_ctx* c, GzText& vcf, GzText& fasta, bool own, bool ignore_chrom) : ctx(c), s(vcf, fasta, own, ignore_chrom), z(true) {}
+    void count_downloads()
+    {
+        if (!z) return;
+        gz[0].text_d2h_bytes = s.vcf_d2h;
+        gz[1].text_d2h_bytes = s.fasta_d2h;
+        ctx->gz[0] = gz[0]; ctx->gz[1] = gz[1];
+    }
 };
 static_assert(sizeof(edsx_contig) == sizeof(ContigRec) && offsetof(edsx_contig, duplicate) == offsetof(ContigRec, duplicate),
               "edsx_contig is ContigRec");
@@ -656,7 +668,9 @@ int edsx_vcf_session_transform(edsx_vcf_session* s, size_t index, uint32_t conte
         VcfCounters c;
         try {
             s->s.transform(ctx->vcf, index, e, q, c, nullptr);
+            s->count_downloads();
         } catch (...) {
+            s->count_downloads();
             if (stats) {   // as edsx_vcf_transform: the counters of the parse survive a later error
                 stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
                 stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
@@ -722,6 +736,113 @@ int edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size
     rc = edsx_vcf_session_find(s, contig, &index);
     if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
     edsx_vcf_session_close(s);                                   // (ctx->err stays: closing reports nothing)
+    return rc;
+}
+
+// ---- compressed input (bgzf_device.hip, inflate.hpp)
+int edsx_gz_probe(const uint8_t* data, size_t size, int* kind)
+{
+    if (!kind || (!data && size)) return EDSX_ERR_INVALID_PARAMETER;
+    *kind = (int)gz::gz_probe(data, size);
+    return EDSX_OK;
+}
+
+int edsx_bgzf_index(const uint8_t* data, size_t size, edsx_buf* blocks, uint64_t* text_size)
+{
+    if (blocks) { blocks->data = nullptr; blocks->size = 0; }
+    if (text_size) *text_size = 0;
+    if (!blocks || !text_size || (!data && size)) return EDSX_ERR_INVALID_PARAMETER;
+    static_assert(sizeof(edsx_bgzf_block) == sizeof(gz::BgzfBlock) && offsetof(edsx_bgzf_block, isize) == offsetof(gz::BgzfBlock, isize),
+                  "edsx_bgzf_block is BgzfBlock");
+    try {
+        std::vector<gz::BgzfBlock> tab;
+        u64 n = 0;
+        if (gz::gz_walk(data, size, n, [&](const gz::BgzfBlock& b) { tab.push_back(b); }) != gz::GZ_BGZF) return EDSX_ERR_INVALID_FORMAT;
+        take(blocks, tab.size() * sizeof(gz::BgzfBlock));
+        if (!tab.empty()) std::memcpy(blocks->data, tab.data(), blocks->size);
+        *text_size = n;
+    } catch (...) { return EDSX_ERR_BUILD_FAILED; }
+    return EDSX_OK;
+}
+
+int edsx_gz_inflate(edsx_ctx* ctx, const uint8_t* data, size_t size, edsx_buf* text)
+{
+    if (text) { text->data = nullptr; text->size = 0; }
+    return guarded(ctx, [&] {
+        if (!text || (!data && size)) throw ParamError("null argument");
+        static const uint8_t none = 0;
+        ctx->gz[0] = GzInfo(); ctx->gz[1] = GzInfo();
+        GzText t;
+        gz_open(data ? data : &none, size, "input", t, ctx->gz[0], nullptr);
+        HostBytes out;
+        out.take(t.n);
+        if (t.on_device) PinnedDownload::copy(out.data, t.dev.ptr, t.n, nullptr);     // (the caller asked for the text: not a text_d2h of a transform)
+        else if (t.n) std::memcpy(out.data, t.on_host ? t.host.data() : t.plain, t.n);
+        text->size = out.size; text->data = out.release();
+    });
+}
+
+int edsx_gz_last_info(const edsx_ctx* ctx, int which, edsx_gz_info* out)
+{
+    if (!ctx || !out || which < 0 || which > 1) return EDSX_ERR_INVALID_PARAMETER;
+    static_assert(sizeof(edsx_gz_info) == sizeof(GzInfo), "edsx_gz_info is GzInfo");
+    std::memcpy(out, &ctx->gz[which], sizeof(*out));
+    return EDSX_OK;
+}
+
+namespace {
+
+// inflate both inputs (the VCF's errors first) and build the session on them
+edsx_vcf_session* open_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size, bool own, bool ignore_chrom)
+{
+    static const uint8_t none = 0;
+    ctx->gz[0] = GzInfo(); ctx->gz[1] = GzInfo();
+    GzText v, f;
+    gz_open(vcf ? vcf : &none, vcf_size, "VCF", v, ctx->gz[0], nullptr);
+    gz_open(fasta ? fasta : &none, fasta_size, "FASTA", f, ctx->gz[1], nullptr);
+    std::unique_ptr<edsx_vcf_session> s(new edsx_vcf_session(ctx, v, f, own, ignore_chrom));
+    s->gz[0] = ctx->gz[0]; s->gz[1] = ctx->gz[1];
+    try { s->s.open(nullptr); } catch (...) { s->count_downloads(); throw; }
+    s->count_downloads();
+    return s.release();
+}
+
+} // namespace
+
+int edsx_vcf_session_open_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                            edsx_vcf_session** out)
+{
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        if (!out || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
+        *out = open_z(ctx, vcf, vcf_size, fasta, fasta_size, true, false);
+    });
+}
+
+int edsx_vcf_session_contig_name(const edsx_vcf_session* s, size_t index, const char** name, size_t* len)
+{
+    if (!s || !name || !len || index >= s->s.contigs().size()) return EDSX_ERR_INVALID_PARAMETER;
+    const std::string& n = s->s.name(index);
+    *name = n.data(); *len = n.size();
+    return EDSX_OK;
+}
+
+int edsx_vcf_transform_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size, const char* contig,
+                         uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
+{
+    if (eds) { eds->data = nullptr; eds->size = 0; }
+    if (seds) { seds->data = nullptr; seds->size = 0; }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    edsx_vcf_session* s = nullptr;
+    int rc = guarded(ctx, [&] {
+        if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
+        s = open_z(ctx, vcf, vcf_size, fasta, fasta_size, false, contig == nullptr);
+    });
+    if (rc != EDSX_OK) return rc;
+    size_t index = 0;
+    if (contig) rc = edsx_vcf_session_find(s, contig, &index);
+    if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
+    edsx_vcf_session_close(s);
     return rc;
 }
 

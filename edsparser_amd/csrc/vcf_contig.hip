@@ -198,13 +198,52 @@ bool first_token(const uint8_t* p, size_t n, size_t& lo, size_t& len)
 
 } // namespace
 
+VcfSession::VcfSession(GzText& vcf, GzText& fasta, bool own, bool ignore_chrom) : vcf_(nullptr), vcf_n_(0), fasta_(nullptr), fasta_n_(0)
+{
+    static const uint8_t none = 0;
+    ignore_chrom_ = ignore_chrom;
+    auto take = [&](GzText& t, const uint8_t*& host, size_t& n, std::vector<uint8_t>& own_buf, DevBuf& dev, bool& resident) {
+        n = t.n;
+        if (t.on_device) { std::swap(dev.ptr, t.dev.ptr); std::swap(dev.cap, t.dev.cap); resident = true; host = nullptr; return; }
+        if (t.on_host) { own_buf.swap(t.host); host = own_buf.data(); }
+        else if (own) { own_buf.assign(t.plain, t.plain + t.n); host = own_buf.data(); }
+        else host = t.plain;
+        if (n == 0 || !host) host = &none;
+    };
+    take(vcf, vcf_, vcf_n_, own_vcf_, d_vcf_, vcf_resident_);
+    take(fasta, fasta_, fasta_n_, own_fasta_, d_fasta_, fasta_resident_);
+}
+
+const uint8_t* VcfSession::host_vcf()
+{
+    if (!vcf_) {
+        own_vcf_.resize(vcf_n_ + 1);
+        if (vcf_n_) PinnedDownload::copy(own_vcf_.data(), d_vcf_.ptr, vcf_n_, nullptr);
+        vcf_d2h += vcf_n_;
+        vcf_ = own_vcf_.data();
+    }
+    return vcf_;
+}
+
+void VcfSession::fetch_fasta(u64 off, u64 len, void* dst)
+{
+    if (len == 0) return;
+    if (fasta_) { memcpy(dst, fasta_ + off, len); return; }
+    EDSX_HIP(hipMemcpy(dst, d_fasta_.as<uint8_t>() + off, len, hipMemcpyDeviceToHost));
+    fasta_d2h += len;
+}
+
 void VcfSession::index_fasta(hipStream_t st)
 {
     const u64 n = fasta_n_;
-    if (n == 0 || fasta_[0] != '>') throw FormatError("Invalid FASTA format: expected header line starting with '>'");
-    d_fasta_.ensure(n + 16);
-    EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta_, n, hipMemcpyHostToDevice, st));
-    fasta_h2d += n;
+    uint8_t first = 0;
+    if (n) fetch_fasta(0, 1, &first);
+    if (n == 0 || first != '>') throw FormatError("Invalid FASTA format: expected header line starting with '>'");
+    if (!fasta_resident_) {
+        d_fasta_.ensure(n + 16);
+        EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta_, n, hipMemcpyHostToDevice, st));
+        fasta_h2d += n;
+    }
     const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
     DevBuf hdr, nonnl, tmp, ctl, hstart;
     hdr.ensure(8 * (nblk + 2)); nonnl.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((nblk + 2) / SCAN_TILE + 4)); ctl.ensure(8 * 8);
@@ -229,11 +268,14 @@ void VcfSession::index_fasta(hipStream_t st)
     EDSX_HIP(hipMemcpyAsync(recs_.data(), d_recs_.ptr, sizeof(ContigRec) * nhdr, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
+    names_.resize(recs_.size());
     for (size_t r = 0; r < recs_.size(); r++) {
         ContigRec& c = recs_[r];
         if (c.rec_start >= c.rec_end || c.rec_end > n || c.name_off + c.name_len > c.rec_end || c.seq_start > c.rec_end)
             throw DeviceError("FASTA record index: record " + std::to_string(r) + " out of bounds");
-        const bool fresh = by_name_.emplace(std::string(reinterpret_cast<const char*>(fasta_ + c.name_off), c.name_len), r).second;
+        names_[r].resize(c.name_len);
+        if (c.name_len) fetch_fasta(c.name_off, c.name_len, &names_[r][0]);
+        const bool fresh = by_name_.emplace(names_[r], r).second;
         c.duplicate = fresh ? 0 : 1;
     }
 }
@@ -252,8 +294,10 @@ bool VcfSession::classify_device(hipStream_t st)
     VtCtl h{};
     h.n = nblk;
     EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
-    EDSX_HIP(hipMemcpyAsync(d_vcf_.ptr, vcf_, n, hipMemcpyHostToDevice, st));
-    vcf_h2d += n;
+    if (!vcf_resident_) {
+        EDSX_HIP(hipMemcpyAsync(d_vcf_.ptr, vcf_, n, hipMemcpyHostToDevice, st));
+        vcf_h2d += n;
+    }
     const uint8_t* raw = d_vcf_.as<uint8_t>();
     TraceSpan lines(st, "vcf line starts", 2 * n);     // (count pass + fill pass: the text is read twice)
     hipLaunchKernelGGL(k_vt_line_count, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), ctl);
@@ -267,12 +311,20 @@ bool VcfSession::classify_device(hipStream_t st)
     lstart.ensure(8 * (nr + 1));
     hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), lstart.as<u64>());
     lines.end();
+    if (ignore_chrom_) {                                                     // every record line belongs to record 0, file order
+        EDSX_HIP(hipStreamSynchronize(st));
+        std::swap(lsorted_.ptr, lstart.ptr); std::swap(lsorted_.cap, lstart.cap);
+        first_[0] = 0;
+        recs_[0].vcf_records = nr;
+        records_total = nr;
+        return true;
+    }
 
     // name table: one entry per distinct name, sorted by hash
     std::vector<std::pair<u64, u32>> tab;
     tab.reserve(by_name_.size());
     for (size_t r = 0; r < K; r++)
-        if (!recs_[r].duplicate) tab.push_back({fnv1a(fasta_ + recs_[r].name_off, recs_[r].name_len), (u32)r});
+        if (!recs_[r].duplicate) tab.push_back({fnv1a(reinterpret_cast<const uint8_t*>(names_[r].data()), names_[r].size()), (u32)r});
     std::sort(tab.begin(), tab.end());
     std::vector<u64> hh(tab.size());
     std::vector<u32> hr(tab.size());
@@ -337,10 +389,11 @@ bool VcfSession::classify_device(hipStream_t st)
         EDSX_HIP(hipMemcpy(ls.data(), lsorted_.as<u64>() + first_[K], 8 * records_unknown, hipMemcpyDeviceToHost));
         std::unordered_map<std::string, size_t> at;
         std::vector<std::pair<std::string, u64>> names;
+        const uint8_t* hv = host_vcf();
         for (u64 lo : ls) {
             size_t e = lo;
-            while (e < n && vcf_[e] != '\t' && vcf_[e] != '\n') e++;
-            const auto ins = at.emplace(std::string(reinterpret_cast<const char*>(vcf_ + lo), e - lo), names.size());
+            while (e < n && hv[e] != '\t' && hv[e] != '\n') e++;
+            const auto ins = at.emplace(std::string(reinterpret_cast<const char*>(hv + lo), e - lo), names.size());
             if (ins.second) names.push_back({ins.first->first, 0});
             names[ins.first->second].second++;
         }
@@ -351,6 +404,8 @@ bool VcfSession::classify_device(hipStream_t st)
 
 void VcfSession::classify_host()
 {
+    host_vcf();
+    if (ignore_chrom_) return;                                               // (the whole text is record 0's)
     for (ContigRec& c : recs_) c.vcf_records = 0;
     records_total = records_without_token = records_unknown = 0;
     unknown_text_.clear();
@@ -388,6 +443,8 @@ void VcfSession::open(hipStream_t st)
     if (vcf_n_ == 0) return;
     classified_on_device = classify_device(st);
     if (!classified_on_device) {
+        host_vcf();                                                          // (before the resident text goes)
+        vcf_resident_ = false;
         d_vcf_.release(); lsorted_.release();
         classify_host();
     }
@@ -402,10 +459,11 @@ bool VcfSession::find(const std::string& name, size_t& index) const
 }
 
 // V_c: every line that is empty, starts with '#', or is a record line whose first token is the record's name
-void VcfSession::host_text_of(size_t index, std::vector<uint8_t>& out) const
+void VcfSession::host_text_of(size_t index, std::vector<uint8_t>& out)
 {
     const ContigRec& c = recs_[index];
-    const uint8_t* name = fasta_ + c.name_off;
+    const uint8_t* name = reinterpret_cast<const uint8_t*>(names_[index].data());
+    host_vcf();
     out.clear();
     for (size_t pos = 0; pos < vcf_n_;) {
         const uint8_t* nl = static_cast<const uint8_t*>(memchr(vcf_ + pos, '\n', vcf_n_ - pos));
@@ -426,14 +484,28 @@ void VcfSession::transform(VcfPipeline& pipe, size_t index, HostBytes& eds, Host
     if (index >= recs_.size()) throw ParamError("contig index " + std::to_string(index) + " out of range");
     const ContigRec& c = recs_[index];
     if (c.duplicate)
-        throw ParamError("Contig '" + std::string(reinterpret_cast<const char*>(fasta_ + c.name_off), c.name_len) +
+        throw ParamError("Contig '" + names_[index] +
                          "': record " + std::to_string(index) + " repeats the name of an earlier FASTA record");
     VcfResident res;
     res.d_fasta = d_fasta_.as<uint8_t>() + c.rec_start;
     res.seq_size = c.seq_size;
-    const uint8_t* fa = fasta_ + c.rec_start;
     const size_t fa_n = c.rec_end - c.rec_start;
     static const uint8_t none = 0;
+    // the pipeline parses the record's header line and first sequence line on the host: of a FASTA that lives in HBM
+    // only, a window that holds both comes down (64 KiB, larger while the two lines do not end inside it)
+    std::vector<uint8_t> head;
+    const uint8_t* fa = fasta_ ? fasta_ + c.rec_start : nullptr;
+    if (!fa) {
+        for (u64 w = std::min<u64>(fa_n, 1u << 16);; w = std::min<u64>(fa_n, w * 4)) {
+            head.resize(w + 1);
+            fetch_fasta(c.rec_start, w, head.data());
+            if (w == fa_n) break;
+            bool inside = false;
+            try { u64 ss, lw, rf; fasta_head(head.data(), w, ss, lw, rf); inside = rf < w; } catch (const FormatError&) {}
+            if (inside) break;
+        }
+        fa = head.data();
+    }
     if (classified_on_device) {
         res.d_vcf = d_vcf_.as<uint8_t>(); res.vcf_n = vcf_n_;
         res.nrec = c.vcf_records;
@@ -442,9 +514,12 @@ void VcfSession::transform(VcfPipeline& pipe, size_t index, HostBytes& eds, Host
         res.d_vcf = nullptr; res.d_lstart = nullptr; res.nrec = 0;           // the tokeniser refuses these lines: host text
     }
     std::vector<uint8_t> text;
-    host_text_of(index, text);
+    const uint8_t* tp = &none;
+    size_t tn = 0;
+    if (ignore_chrom_) { tp = host_vcf(); tn = vcf_n_; }
+    else { host_text_of(index, text); if (!text.empty()) { tp = text.data(); tn = text.size(); } }
     try {
-        pipe.run(text.empty() ? &none : text.data(), text.size(), fa, fa_n, eds, seds, stats, st, VcfRange(), &res);
+        pipe.run(tp, tn, fa, fa_n, eds, seds, stats, st, VcfRange(), &res);
     } catch (...) { vcf_h2d += pipe.vcf_h2d_bytes(); throw; }
     vcf_h2d += pipe.vcf_h2d_bytes();
 }

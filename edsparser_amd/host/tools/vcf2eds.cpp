@@ -5,6 +5,7 @@
 #include "edsx.h"
 #include "../cli_util.hpp"
 #include "../device.hpp"
+#include "gz_input.hpp"
 #include "tool_common.hpp"
 
 using namespace edsparser;
@@ -42,12 +43,13 @@ struct Session {                                   // edsx_vcf_session, closed o
 };
 
 // --all-chroms: one session, one pair of files per FASTA record that the VCF has record lines for.  false: a contig failed.
-bool transform_all_contigs(const tool::MappedFile& vcf_in, const tool::MappedFile& fasta_in, const std::filesystem::path& input_file,
+bool transform_all_contigs(const tool::GzInput& vcf_in, const tool::GzInput& fasta_in, bool compressed, const std::string& stem,
                            const std::filesystem::path& out_dir, Length context_length)
 {
     edsx_ctx* ctx = detail::context();
     Session ses;
-    int rc = edsx_vcf_session_open(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), &ses.h);
+    int rc = compressed ? edsx_vcf_session_open_z(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size, &ses.h)
+                        : edsx_vcf_session_open(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size, &ses.h);
     if (rc != EDSX_OK) detail::throw_status(rc, ctx);
     const edsx_contig* recs = nullptr;
     size_t nrecs = 0;
@@ -64,12 +66,15 @@ bool transform_all_contigs(const tool::MappedFile& vcf_in, const tool::MappedFil
         }
     }
     std::filesystem::create_directories(out_dir);
-    const std::string stem = input_file.stem().string();
     std::vector<std::pair<std::string, VCFStats>> done;
     bool all_ok = true;
     for (size_t i = 0; i < nrecs; i++) {
         if (recs[i].duplicate || recs[i].vcf_records == 0) continue;
-        const std::string name(reinterpret_cast<const char*>(fasta_in.data() + recs[i].name_off), recs[i].name_len);
+        const char* name_p = nullptr;
+        size_t name_n = 0;
+        if (edsx_vcf_session_contig_name(ses.h, i, &name_p, &name_n) != EDSX_OK || !name_p)
+            throw std::runtime_error("FASTA record " + std::to_string(i) + " has no name in the session");
+        const std::string name(name_p, name_n);
         try {
             if (name.empty() || name == "." || name == ".." || name.find('/') != std::string::npos || name.find('\0') != std::string::npos)
                 throw std::runtime_error("contig name cannot be used in a file name");
@@ -110,8 +115,8 @@ int main(int argc, char** argv)
     try {
         cli::Parser opts("Transform VCF (Variant Call Format) to EDS/l-EDS");
         opts.add("help", 'h', false, false, "Show help message");
-        opts.add("input", 'i', true, true, "Input VCF file (.vcf)");
-        opts.add("reference", 'r', true, true, "Reference FASTA file");
+        opts.add("input", 'i', true, true, "Input VCF file (.vcf, .vcf.gz, .vcf.bgz)");
+        opts.add("reference", 'r', true, true, "Reference FASTA file (plain, gzip or BGZF: probed by content)");
         opts.add("output", 'o', true, false, "Output EDS file (default: <input>.eds)");
         opts.add("sources", 's', true, false, "Output source file (default: <output>.seds)");
         opts.add("context-length", 'l', true, false, "Create l-EDS with minimum context length (0 = regular EDS)");
@@ -135,12 +140,20 @@ int main(int argc, char** argv)
                          "  vcf2eds -i wgs.vcf -r hg38.fa --all-chroms --output-dir out   # out/wgs.<contig>.eds + .seds\n\n"
                          "CONTIGS:\n"
                          "  Without --chrom / --all-chroms the first FASTA record is the reference and CHROM is\n"
-                         "  ignored, as the reference tool does.\n\n";
+                         "  ignored, as the reference tool does.\n\n"
+                         "COMPRESSED INPUT:\n"
+                         "  -i takes .vcf.gz / .vcf.bgz, -r is probed by content.  BGZF (bgzip) files are inflated on\n"
+                         "  the GPU, one wave per 64 KiB block, CRC-32 checked, and the text stays in device memory;\n"
+                         "  any other gzip file is inflated on the host, on one thread.  x.vcf.gz writes x.eds.\n"
+                         "  With --gpus N a compressed input is inflated on GPU 0 first.\n\n";
             tool::print_performance(timer);
             return 0;
         }
         opts.notify();
         const std::filesystem::path input_file = opts.get("input");
+        // x.vcf.gz / x.vcf.bgz name their outputs as x.vcf does
+        const bool named_gz = tool::gz_extension(input_file);
+        const std::filesystem::path named_file = named_gz ? input_file.parent_path() / input_file.stem() : input_file;
         const std::filesystem::path reference_file = opts.get("reference");
         const std::filesystem::path output_file = opts.get("output");
         const std::filesystem::path sources_file = opts.get("sources");
@@ -157,7 +170,7 @@ int main(int argc, char** argv)
             throw std::runtime_error("--chrom / --all-chroms cannot be combined with --gpus: contigs are transformed on one GPU");
         if (one_chrom && chrom.empty()) throw std::runtime_error("--chrom needs a contig name");
 
-        if (input_file.extension() != ".vcf") {
+        if (named_file.extension() != ".vcf") {
             std::cerr << "Error: Input file must be a VCF file (.vcf)\n";
             std::cerr << "Got: " << input_file << "\n";
             tool::print_performance(timer);
@@ -169,7 +182,10 @@ int main(int argc, char** argv)
             return 1;
         }
         // both files are mapped and handed to the C ABI as they are (no ifstream -> std::string copies)
-        tool::MappedFile vcf_in(input_file, "VCF"), fasta_in(reference_file, "reference FASTA");
+        tool::MappedFile vcf_map(input_file, "VCF"), fasta_map(reference_file, "reference FASTA");
+        // gzip / BGZF inputs: a broken compressed layer ends the run here, before any device work
+        const tool::GzInput vcf_in(vcf_map, "VCF", named_gz), fasta_in(fasta_map, "FASTA", false);
+        const bool compressed = vcf_in.compressed() || fasta_in.compressed();
 
         const bool create_leds = context_length > 0;
         if (create_leds) {
@@ -180,11 +196,13 @@ int main(int argc, char** argv)
         }
         std::cout << "  Input: " << input_file << "\n";
         std::cout << "  Reference: " << reference_file << "\n";
+        if (compressed) std::cout << "  Compression: VCF " << vcf_in.describe() << ", reference " << fasta_in.describe() << "\n";
         if (one_chrom) std::cout << "  Contig: " << chrom << "\n";
         if (all_chroms) {
             std::cout << "  Contigs: every reference record with VCF records\n";
             const std::filesystem::path dir = opts.has("output-dir") ? std::filesystem::path(opts.get("output-dir")) : input_file.parent_path();
-            const bool ok = transform_all_contigs(vcf_in, fasta_in, input_file, dir.empty() ? std::filesystem::path(".") : dir, context_length);
+            const bool ok = transform_all_contigs(vcf_in, fasta_in, compressed, named_file.stem().string(), dir.empty() ? std::filesystem::path(".") : dir,
+                                                  context_length);
             tool::print_performance(timer);
             return ok ? 0 : 1;
         }
@@ -204,8 +222,20 @@ int main(int argc, char** argv)
             edsx_multi* mg = nullptr;
             if (edsx_multi_create(devs.data(), static_cast<int>(ngpu), 1, &mg) != EDSX_OK)
                 throw std::runtime_error("cannot use " + std::to_string(ngpu) + " GPUs (gfx950 devices 0.." + std::to_string(ngpu - 1) + " with RCCL)");
-            const int rc = edsx_vcf_transform_multi(mg, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
-                                                    &eds_out.b, &seds_out.b, &cst);
+            // BGZF inputs are inflated on GPU 0 and handed over as text
+            detail::Buf vtext, ftext;
+            const uint8_t* vp = vcf_in.data; size_t vn = vcf_in.size;
+            const uint8_t* fp = fasta_in.data; size_t fn = fasta_in.size;
+            auto inflate0 = [&](const tool::GzInput& z, detail::Buf& t, const uint8_t*& p, size_t& n) {
+                if (z.kind != 1) return;
+                edsx_ctx* ctx = detail::context();
+                const int zrc = edsx_gz_inflate(ctx, z.data, z.size, &t.b);
+                if (zrc != EDSX_OK) { edsx_multi_destroy(mg); detail::throw_status(zrc, ctx); }
+                p = t.b.data ? t.b.data : reinterpret_cast<const uint8_t*>(""); n = t.b.size;
+            };
+            inflate0(vcf_in, vtext, vp, vn);
+            inflate0(fasta_in, ftext, fp, fn);
+            const int rc = edsx_vcf_transform_multi(mg, vp, vn, fp, fn, context_length, &eds_out.b, &seds_out.b, &cst);
             const std::string what = rc != EDSX_OK ? edsx_multi_last_error(mg) : "";
             edsx_vcf_multi_info info{};
             edsx_multi_last_vcf(mg, &info);
@@ -216,9 +246,11 @@ int main(int argc, char** argv)
                                                                  : std::string(ngpu > 1 ? " (not partitioned: one GPU transforms the file)" : "")) << "\n";
         } else {
             edsx_ctx* ctx = detail::context();
-            const int rc = one_chrom ? edsx_vcf_transform_contig(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(),
+            const int rc = compressed ? edsx_vcf_transform_z(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size,
+                                                             one_chrom ? chrom.c_str() : nullptr, context_length, &eds_out.b, &seds_out.b, &cst)
+                         : one_chrom ? edsx_vcf_transform_contig(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size,
                                                                  chrom.c_str(), context_length, &eds_out.b, &seds_out.b, &cst)
-                                     : edsx_vcf_transform(ctx, vcf_in.data(), vcf_in.size(), fasta_in.data(), fasta_in.size(), context_length,
+                                     : edsx_vcf_transform(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size, context_length,
                                                           &eds_out.b, &seds_out.b, &cst);
             take_stats();
             if (rc != EDSX_OK) detail::throw_status(rc, ctx);
@@ -226,11 +258,11 @@ int main(int argc, char** argv)
 
         std::filesystem::path eds_path, seds_path;
         if (create_leds) {
-            const std::string base = input_file.stem().string(), suffix = "_l" + std::to_string(context_length);
+            const std::string base = named_file.stem().string(), suffix = "_l" + std::to_string(context_length);
             eds_path = output_file.empty() ? input_file.parent_path() / (base + suffix + ".leds") : output_file;
             seds_path = sources_file.empty() ? eds_path.parent_path() / (base + suffix + ".seds") : sources_file;
         } else {
-            eds_path = output_file.empty() ? input_file.parent_path() / (input_file.stem().string() + ".eds") : output_file;
+            eds_path = output_file.empty() ? input_file.parent_path() / (named_file.stem().string() + ".eds") : output_file;
             seds_path = sources_file.empty() ? eds_path.parent_path() / (eds_path.stem().string() + ".seds") : sources_file;
         }
         tool::write_bytes(eds_path, eds_out.b.data, eds_out.b.size, "output");

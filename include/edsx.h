@@ -146,6 +146,45 @@ int  edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_siz
                                const char* contig, uint32_t context_len, edsx_buf* eds, edsx_buf* seds,
                                edsx_vcf_stats* stats);
 
+/* ---- compressed input: gzip and BGZF (bgzip) files, DEFLATE decoded on the device ----
+ * inflate(x) is x itself when x does not begin with the bytes 1f 8b; otherwise the concatenated payloads of all gzip
+ * members of x (RFC 1952 / 1951: what Python's gzip.decompress returns); bytes behind the last member that are not a
+ * member are an error.  A file is BGZF when every member has CM 8, FLG 4, an extra subfield 'B' 'C' of length 2, its
+ * block inside the file and ISIZE <= 65536; every block is then one wave's work on the device (inflate + CRC-32).
+ * Any other gzip file is inflated on the host, on the calling thread.  No compression library is involved.
+ * Errors of the compressed layer are EDSX_ERR_INVALID_FORMAT, "Compressed <VCF|FASTA|input>: block <k> at byte <off>:
+ * <reason>" for the lowest failing member k (from 0) at byte offset off; reason: truncated | not a gzip member |
+ * block size beyond the end of the file | invalid DEFLATE stream | length mismatch | CRC mismatch.
+ * The existing entry points do not look for gzip magic; only the calls below do. */
+/* host only: *kind = 0 plain, 1 BGZF, 2 gzip; never fails on garbage */
+int edsx_gz_probe(const uint8_t* data, size_t size, int* kind);
+typedef struct { uint64_t comp_off, out_off; uint32_t comp_len, isize; } edsx_bgzf_block;
+/* host only, no context: the block table of a BGZF file (an array of edsx_bgzf_block in blocks, EOF block included)
+ * and the size of its text; EDSX_ERR_INVALID_FORMAT when the file is not BGZF.  Reads headers and trailers only. */
+int edsx_bgzf_index(const uint8_t* data, size_t size, edsx_buf* blocks, uint64_t* text_size);
+/* text = inflate(data).  BGZF: on the device; gzip: on the host; plain: a copy. */
+int edsx_gz_inflate(edsx_ctx* ctx, const uint8_t* data, size_t size, edsx_buf* text);
+/* edsx_vcf_transform (contig == NULL: first FASTA record, CHROM ignored) or edsx_vcf_transform_contig on
+ * (inflate(vcf), inflate(fasta)): same texts, counters, status and error text.  Either input may be compressed or
+ * plain.  Text inflated on the device stays in HBM, where the tokeniser, the FASTA index and the contig classifier read it. */
+int edsx_vcf_transform_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                         const char* contig, uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats);
+/* edsx_vcf_session_open on (inflate(vcf), inflate(fasta)); the session works with every edsx_vcf_session_* call and
+ * owns what it needs: the caller's buffers may be released after the call. */
+int edsx_vcf_session_open_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
+                            edsx_vcf_session** out);
+/* The name of FASTA record `index` (not zero-terminated; valid until close): edsx_contig's name_off points into the
+ * inflated FASTA, which a caller of edsx_vcf_session_open_z does not hold.  Works for every session. */
+int edsx_vcf_session_contig_name(const edsx_vcf_session* s, size_t index, const char** name, size_t* len);
+/* A session opened with _open_z keeps the info of its two inputs; every edsx_vcf_session_transform on it publishes them
+ * again (with its downloads so far) as the context's last info, whatever other call ran in between.
+ * The compressed layer of the last call above, per input: which = 0 the VCF (or the input of edsx_gz_inflate), 1 the
+ * FASTA.  h2d_bytes: compressed bytes + block table copied to the device (BGZF); text_d2h_bytes: bytes of inflated
+ * text copied back to the host (windows for the host-side header parse, or the whole text when a host path was taken). */
+typedef struct { int kind; int inflated_on_device; uint64_t blocks, comp_bytes, text_bytes, h2d_bytes, text_d2h_bytes;
+                 double index_ms, inflate_ms, crc_ms; } edsx_gz_info;
+int edsx_gz_last_info(const edsx_ctx* ctx, int which, edsx_gz_info* out);
+
 /* ---- multi-GPU VCF: partition by reference position ----
  * Groups of overlapping records (vcf_transforms.cpp:482-534) never span a cut placed at a group start, so
  * every GPU walks its own position range and the pieces concatenate to the reference's text with no repair.

@@ -1,0 +1,171 @@
+"""CPU: the compressed-input layer without a device - the host build of the decoder core under the sanitizers, the block
+index and probe of the C ABI against the tables tests/bgzf_spec.py wrote, exported symbols, and the tools' argument and
+compressed-layer errors (reported before any device work)."""
+import gzip
+import os
+import re
+import subprocess
+
+import pytest
+
+import bgzf_spec as bz
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "edsparser_amd", "host")
+BUILD = os.path.join(HOST, "build")
+
+
+@pytest.fixture(scope="module")
+def tools():
+    import edsparser_amd.build as b
+    b.build()
+    subprocess.run(["make", "-s", "-C", HOST], check=True)
+    return BUILD
+
+
+def test_spec_writer_round_trips_through_gzip():
+    for name, data, text, kind, table in bz.corpus():
+        assert gzip.decompress(data) == text, name
+        if kind == 1:
+            assert bz.read(data) == text and sum(t[3] for t in table) == len(text) and sum(t[2] for t in table) == len(data), name
+
+
+def test_host_decoder_under_sanitizers(tmp_path):
+    """Corpus parity, 3000 single-bit flips, truncation at every byte, BSIZE / ISIZE / CRC damage, trailing garbage:
+    tests/cpp/test_inflate.cpp built with -fsanitize=address,undefined.  No damaged input may be accepted."""
+    refusals, log = bz.host_refusals(ROOT, str(tmp_path))
+    assert re.search(r"(\d+) cases, 0 failures", log), log
+    flips = {k: v for k, v in refusals.items() if k.startswith("flip")}
+    assert len(flips) == 3000
+    for name, text in refusals.items():
+        m = re.fullmatch(r"Compressed input: block (\d+) at byte (\d+): (.+)", text)
+        assert m and m.group(3) in bz.REASONS, (name, text)
+    assert all(v.startswith("Compressed input: block 1 at byte ") for v in flips.values())
+    # Python's own decoder refuses every one of these flips too (the statement the test rests on)
+    data, pos = bz.flip_positions()
+    for at, bit in pos[:200]:
+        with pytest.raises(Exception):
+            gzip.decompress(bz.flipped(data, at, bit))
+
+
+def test_block_index_and_probe_equal_the_spec():
+    import edsparser_amd
+    for name, data, text, kind, table in bz.corpus():
+        assert edsparser_amd.gz_probe(data) == kind, name
+        if kind == 1:
+            assert edsparser_amd.bgzf_index(data) == (table, len(text)), name
+        else:
+            with pytest.raises(edsparser_amd.EdsxError):
+                edsparser_amd.bgzf_index(data)
+    for name, text in bz.texts().items():
+        assert edsparser_amd.gz_probe(text) == 0, name
+    garbage = [b"", b"\x1f", b"\x1f\x8b", b"\x1f\x8b\x08", b"\x1f\x8b" + bytes(100), b"\x1f\x8b\x08\x04" + b"\xff" * 40,
+               bz.EOF_BLOCK[:-1], bz.EOF_BLOCK + b"x", b"\x8b\x1f" + bz.EOF_BLOCK]
+    want = [0, 0, 2, 2, 2, 2, 2, 2, 0]
+    assert [edsparser_amd.gz_probe(g) for g in garbage] == want
+    assert edsparser_amd.gz_probe(bz.EOF_BLOCK) == 1 and edsparser_amd.bgzf_index(bz.EOF_BLOCK) == ([(0, 0, 28, 0)], 0)
+    # ISIZE above 64 KiB, FNAME, a block that leaves the file: gzip, not BGZF
+    data, table = bz.write(bz.vcf_text(1000))
+    big = bytearray(data); big[table[0][2] - 4:table[0][2]] = (65537).to_bytes(4, "little")
+    assert edsparser_amd.gz_probe(bytes(big)) == 2
+    assert edsparser_amd.gz_probe(data[:-1]) == 2
+    assert edsparser_amd.gz_probe(bz.gzip_member(b"abc", fname=b"x")) == 2
+
+
+def test_new_symbols_are_exported_and_declared():
+    import edsparser_amd.build as b
+    lib = b.build()
+    names = ["edsx_gz_probe", "edsx_bgzf_index", "edsx_gz_inflate", "edsx_vcf_transform_z", "edsx_vcf_session_open_z",
+             "edsx_gz_last_info", "edsx_vcf_session_contig_name"]
+    hdr = open(os.path.join(ROOT, "include", "edsx.h")).read()
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for n in names:
+        assert re.search(r"\b%s\s*\(" % n, hdr), n
+        assert re.search(r" T %s\b" % n, out), n
+    assert "edsx_bgzf_block" in hdr and "edsx_gz_info" in hdr
+    # no compression library on the product path
+    needed = subprocess.run(["readelf", "-d", lib], capture_output=True, text=True, check=True).stdout
+    assert not re.search(r"NEEDED.*lib(z|deflate|bz2|lzma|zstd)\.", needed), needed
+
+
+def _run(args):
+    return subprocess.run(args, capture_output=True, text=True)
+
+
+def test_vcf2eds_compressed_input_cli(tools, tmp_path):
+    vcf2eds = os.path.join(tools, "vcf2eds")
+    r = _run([vcf2eds, "--help"])
+    assert r.returncode == 0 and "COMPRESSED INPUT" in r.stdout and ".vcf.gz" in r.stdout
+    fa = tmp_path / "ref.fa"
+    fa.write_bytes(b">chr1\nACGTACGT\n")
+    text = bz.vcf_text(3000)
+    # .vcf.gz whose content is not gzip
+    p = tmp_path / "x.vcf.gz"
+    p.write_bytes(text)
+    r = _run([vcf2eds, "-i", str(p), "-r", str(fa)])
+    assert r.returncode == 1 and "Error: Compressed VCF: block 0 at byte 0: not a gzip member" in r.stderr
+    # a truncated BGZF file
+    data, table = bz.write(text, payload=1000)
+    p.write_bytes(data[:table[2][0] + 40])
+    r = _run([vcf2eds, "-i", str(p), "-r", str(fa)])
+    assert r.returncode == 1 and "Error: Compressed VCF: block 2 at byte %d: " % table[2][0] in r.stderr
+    assert r.stderr.split("block 2 at byte %d: " % table[2][0])[1].split("\n")[0] in bz.REASONS
+    # a damaged gzip reference, probed by content whatever its name
+    bad = bytearray(gzip.compress(b">chr1\nACGTACGT\n")); bad[-5] ^= 1
+    fz = tmp_path / "ref.fasta"
+    fz.write_bytes(bytes(bad))
+    p.write_bytes(data)
+    r = _run([vcf2eds, "-i", str(p), "-r", str(fz)])
+    assert r.returncode == 1 and "Error: Compressed FASTA: block 0 at byte 0: CRC mismatch" in r.stderr
+    # the extension rule looks through .gz / .bgz
+    q = tmp_path / "x.txt.gz"
+    q.write_bytes(data)
+    r = _run([vcf2eds, "-i", str(q), "-r", str(fa)])
+    assert r.returncode == 1 and "Error: Input file must be a VCF file (.vcf)" in r.stderr
+    for out in tmp_path.iterdir():
+        assert out.suffix not in (".eds", ".seds", ".leds")
+
+
+def test_vcf2eds_default_output_names_drop_the_gz_suffix(tools, tmp_path):
+    """Without a device the run ends at the transform, after the compressed layer was accepted; with one it writes x.eds."""
+    import torch
+    vcf2eds = os.path.join(tools, "vcf2eds")
+    V, F = b"#h\nchr1\t2\t.\tC\tT\t.\t.\t.\tGT\t0|1\n", b">chr1\nACGTACGT\n"
+    for ext in (".vcf.gz", ".vcf.bgz"):
+        d = tmp_path / ext.strip(".").replace(".", "_")
+        d.mkdir()
+        (d / ("x" + ext)).write_bytes(bz.write(V)[0])
+        (d / "ref.fa").write_bytes(F)
+        r = _run([vcf2eds, "-i", str(d / ("x" + ext)), "-r", str(d / "ref.fa")])
+        assert "Compression: VCF BGZF, 2 blocks, reference plain" in r.stdout, r.stdout + r.stderr
+        if torch.cuda.is_available():
+            assert r.returncode == 0, r.stderr
+            assert sorted(p.name for p in d.iterdir()) == ["ref.fa", "x.eds", "x.seds", "x" + ext]
+        else:
+            assert r.returncode == 1 and "Compressed" not in r.stderr
+
+
+def test_edsx_zcat_cli(tools, tmp_path):
+    zcat = os.path.join(tools, "edsx-zcat")
+    r = _run([zcat])
+    assert r.returncode == 1 and "the option '--input' is required but missing" in r.stderr
+    r = _run([zcat, "--help"])
+    assert r.returncode == 0 and "--index" in r.stdout
+    r = _run([zcat, "-i", str(tmp_path / "missing.gz")])
+    assert r.returncode == 1 and "Failed to open input file" in r.stderr
+    text = bz.vcf_text(200000)
+    data, table = bz.write(text)
+    p = tmp_path / "a.vcf.gz"
+    p.write_bytes(data)
+    r = _run([zcat, "-i", str(p), "--index"])                           # headers and trailers only: no device
+    rows = [tuple(map(int, ln.split("\t"))) for ln in r.stdout.splitlines() if ln and not ln.startswith("#")]
+    assert r.returncode == 0 and rows == table
+    g = tmp_path / "b.gz"
+    g.write_bytes(gzip.compress(text))
+    r = _run([zcat, "-i", str(g), "--index"])
+    assert r.returncode == 1 and "Not a BGZF file" in r.stderr
+    r = _run([zcat, "-i", str(g), "-o", str(tmp_path / "b.txt")])       # plain gzip: inflated on the host
+    assert r.returncode == 0 and (tmp_path / "b.txt").read_bytes() == text
+    g.write_bytes(gzip.compress(text)[:-9])
+    r = _run([zcat, "-i", str(g), "-o", str(tmp_path / "c.txt")])
+    assert r.returncode == 1 and "Error: Compressed input: block 0 at byte 0: " in r.stderr
