@@ -124,9 +124,11 @@ def load_library():
     lib.edsx_version.restype = ctypes.c_char_p
     lib.edsx_ctx_create.argtypes = [ctypes.c_int, P(ctypes.c_void_p)]
     lib.edsx_ctx_destroy.argtypes = [ctypes.c_void_p]
+    lib.edsx_ctx_destroy.restype = None
     lib.edsx_last_error.argtypes = [ctypes.c_void_p]
     lib.edsx_last_error.restype = ctypes.c_char_p
     lib.edsx_buf_free.argtypes = [P(_Buf)]
+    lib.edsx_buf_free.restype = None
     lib.edsx_msa_transform.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                        P(_Buf), P(_Buf)]
     lib.edsx_msa_last_batches.argtypes = [ctypes.c_void_p]
@@ -181,6 +183,7 @@ def load_library():
     lib.edsx_msa_copy_columns.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
     lib.edsx_msa_locate_segment.argtypes = [ctypes.c_void_p, ctypes.c_uint64] + [P(ctypes.c_uint64)] * 4
     lib.edsx_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.edsx_set_timing.restype = None
     lib.edsx_get_timing.argtypes = [ctypes.c_void_p, P(ctypes.c_char_p), P(ctypes.c_float), P(ctypes.c_int),
                                     ctypes.c_int]
     lib.edsx_msa_synth_size.argtypes = [ctypes.c_uint32, ctypes.c_uint64]
@@ -190,6 +193,7 @@ def load_library():
                                           ctypes.c_void_p, P(ctypes.c_size_t)]
     lib.edsx_multi_create.argtypes = [P(ctypes.c_int), ctypes.c_int, ctypes.c_int, P(ctypes.c_void_p)]
     lib.edsx_multi_destroy.argtypes = [ctypes.c_void_p]
+    lib.edsx_multi_destroy.restype = None
     lib.edsx_multi_last_error.argtypes = [ctypes.c_void_p]
     lib.edsx_multi_last_error.restype = ctypes.c_char_p
     lib.edsx_msa_transform_multi.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, P(_Buf), P(_Buf)]
@@ -232,6 +236,68 @@ def load_library():
     return lib
 
 
+def _take(lib, b):
+    """The bytes of an edsx_buf, which is freed."""
+    if b.size < (1 << 31):
+        data = ctypes.string_at(b.data, b.size) if b.size else b""
+    else:                                                          # (string_at takes its size as a C int)
+        data = bytes((ctypes.c_char * b.size).from_address(b.data))
+    lib.edsx_buf_free(ctypes.byref(b))
+    return data
+
+
+def _input(obj):
+    """(pointer, length, keep-alive) of bytes, or of any object with the buffer protocol (handed over in place)."""
+    if isinstance(obj, bytes):
+        return obj, len(obj), obj
+    import numpy as np
+    keep = np.frombuffer(obj, dtype=np.uint8)
+    return ctypes.c_void_p(keep.ctypes.data), int(keep.size), keep
+
+
+def _opt(b):
+    """(bytes or None, length) of an optional text."""
+    if b is None:
+        return None, 0
+    b = bytes(b)
+    return b, len(b)
+
+
+def _raw(x):
+    return x
+
+
+def _fields(st, conv=int, flags=()):
+    """A ctypes struct as a dict: conv(value) per field (_raw: as ctypes gives it), bool for the fields in `flags`."""
+    return {n: (bool if n in flags else conv)(getattr(st, n)) for n, _ in st._fields_}
+
+
+def _name(contig):
+    return contig.encode() if isinstance(contig, str) else bytes(contig)
+
+
+class _Handle:
+    """A library handle in self._h, destroyed once by the function named _destroy: close(), `with`, or collection."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def gz_probe(data):
     """0 plain, 1 BGZF, 2 gzip (edsx_gz_probe: host only, never fails on garbage)."""
     data = bytes(data)
@@ -250,14 +316,14 @@ def bgzf_index(data):
     rc = lib.edsx_bgzf_index(data, len(data), ctypes.byref(b), ctypes.byref(n))
     if rc != 0:
         raise EdsxError(rc, "not a BGZF file")
-    raw = ctypes.string_at(b.data, b.size) if b.size else b""
-    lib.edsx_buf_free(ctypes.byref(b))
+    raw = _take(lib, b)
     blocks = (BgzfBlock * (len(raw) // ctypes.sizeof(BgzfBlock))).from_buffer_copy(raw)
     return [(int(x.comp_off), int(x.out_off), int(x.comp_len), int(x.isize)) for x in blocks], int(n.value)
 
 
-class MultiGpu:
+class MultiGpu(_Handle):
     """edsx_multi: MSA -> EDS over several GPUs from one process (C++ rank threads, RCCL or in-process exchange)."""
+    _destroy = "edsx_multi_destroy"
 
     def __init__(self, devices, use_rccl=True):
         self._lib = load_library()
@@ -268,34 +334,16 @@ class MultiGpu:
             raise EdsxError(rc, "edsx_multi_create failed for devices %r (rccl=%r)" % (list(devices), use_rccl))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.edsx_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _check(self, rc):
+        if rc != 0:
+            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
 
     def msa_transform(self, msa, context_len=0):
         e, s = _Buf(), _Buf()
-        if isinstance(msa, bytes):
-            ptr, n, keep = msa, len(msa), msa
-        else:
-            import numpy as np
-            keep = np.frombuffer(msa, dtype=np.uint8)
-            ptr, n = ctypes.c_void_p(keep.ctypes.data), int(keep.size)
-        rc = self._lib.edsx_msa_transform_multi(self._h, ptr, n, context_len, ctypes.byref(e), ctypes.byref(s))
+        ptr, n, keep = _input(msa)
+        self._check(self._lib.edsx_msa_transform_multi(self._h, ptr, n, context_len, ctypes.byref(e), ctypes.byref(s)))
         del keep
-        if rc != 0:
-            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
-        out = []
-        for b in (e, s):
-            out.append(ctypes.string_at(b.data, b.size) if b.size else b"")
-            self._lib.edsx_buf_free(ctypes.byref(b))
-        return out[0], out[1]
+        return _take(self._lib, e), _take(self._lib, s)
 
     def last_partition(self):
         p, c = ctypes.c_int(), ctypes.c_int()
@@ -307,38 +355,25 @@ class MultiGpu:
         outputs, stats and errors as Context.vcf_transform."""
         e, s, st = _Buf(), _Buf(), VcfStats()
         vcf, fasta = bytes(vcf), bytes(fasta)
-        rc = self._lib.edsx_vcf_transform_multi(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
-                                                ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
-        if rc != 0:
-            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
-        out = []
-        for b in (e, s):
-            out.append(ctypes.string_at(b.data, b.size) if b.size else b"")
-            self._lib.edsx_buf_free(ctypes.byref(b))
-        return out[0], out[1], {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+        self._check(self._lib.edsx_vcf_transform_multi(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
+                                                       ctypes.byref(e), ctypes.byref(s), ctypes.byref(st)))
+        return _take(self._lib, e), _take(self._lib, s), _fields(st)
 
     def last_vcf(self):
         """Of the last vcf_transform: partitioned, fasta_windowed, records_min / _max, moved_line_bytes,
         fasta_h2d_bytes_max."""
         info = VcfMultiInfo()
         self._lib.edsx_multi_last_vcf(self._h, ctypes.byref(info))
-        return {n: (bool if n in ("partitioned", "fasta_windowed") else int)(getattr(info, n)) for n, _ in VcfMultiInfo._fields_}
+        return _fields(info, flags=("partitioned", "fasta_windowed"))
 
     def leds_merge(self, eds, seds=None, context_len=1, compact=True):
         """EDS (+ sEDS: LINEAR, else CARTESIAN) -> (leds, seds_out) by symbol ranges over the handle's GPUs; the same
         outputs and errors as Context.leds_merge."""
         o, so = _Buf(), _Buf()
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
-        rc = self._lib.edsx_leds_merge_multi(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0, context_len,
-                                             1 if compact else 0, ctypes.byref(o), ctypes.byref(so))
-        if rc != 0:
-            raise EdsxError(rc, self._lib.edsx_multi_last_error(self._h).decode(errors="replace"))
-        out = []
-        for b in (o, so):
-            out.append(ctypes.string_at(b.data, b.size) if b.size else b"")
-            self._lib.edsx_buf_free(ctypes.byref(b))
-        return out[0], out[1]
+        self._check(self._lib.edsx_leds_merge_multi(self._h, eds, len(eds), *_opt(seds), context_len, 1 if compact else 0,
+                                                    ctypes.byref(o), ctypes.byref(so)))
+        return _take(self._lib, o), _take(self._lib, so)
 
     def last_merge(self):
         """Of the last leds_merge: partitioned, ranges, fallback (0 partitioned; 1 one rank / l = 0; 2 text not plain;
@@ -346,7 +381,7 @@ class MultiGpu:
         eds_h2d_bytes_max, seds_h2d_bytes_max."""
         info = MergeMultiInfo()
         self._lib.edsx_multi_last_merge(self._h, ctypes.byref(info))
-        return {n: (bool if n == "partitioned" else int)(getattr(info, n)) for n, _ in MergeMultiInfo._fields_}
+        return _fields(info, flags=("partitioned",))
 
 
 def synth_size(n_rows, n_cols, row_align=0):
@@ -355,8 +390,9 @@ def synth_size(n_rows, n_cols, row_align=0):
     return int(load_library().edsx_msa_synth_size(n_rows, n_cols))
 
 
-class Context:
+class Context(_Handle):
     """One context per (thread, GPU); mirrors edsx_ctx_create/destroy."""
+    _destroy = "edsx_ctx_destroy"
 
     def __init__(self, device=0):
         self._lib = load_library()
@@ -367,39 +403,18 @@ class Context:
         self._h = h
         self.device = device
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.edsx_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _check(self, rc):
         if rc != 0:
             raise EdsxError(rc, self._lib.edsx_last_error(self._h).decode(errors="replace"))
 
     def _take(self, b):
-        if b.size < (1 << 31):
-            data = ctypes.string_at(b.data, b.size) if b.size else b""
-        else:                                                      # (string_at takes its size as a C int)
-            data = bytes((ctypes.c_char * b.size).from_address(b.data))
-        self._lib.edsx_buf_free(ctypes.byref(b))
-        return data
+        return _take(self._lib, b)
 
     # ---- host-buffer entry points
     def msa_transform(self, msa, context_len=0):
         """msa: bytes, or any object with the buffer protocol (a mapped file is handed over in place, not copied)."""
         e, s = _Buf(), _Buf()
-        if isinstance(msa, bytes):
-            ptr, n, keep = msa, len(msa), msa
-        else:
-            import numpy as np
-            keep = np.frombuffer(msa, dtype=np.uint8)
-            ptr, n = ctypes.c_void_p(keep.ctypes.data), int(keep.size)
+        ptr, n, keep = _input(msa)
         self._check(self._lib.edsx_msa_transform(self._h, ptr, n, context_len, ctypes.byref(e), ctypes.byref(s)))
         del keep
         return self._take(e), self._take(s)
@@ -412,12 +427,7 @@ class Context:
         (eds, seds, batches taken) - 1 when the input is not cut."""
         e, s = _Buf(), _Buf()
         used = ctypes.c_int(0)
-        if isinstance(msa, bytes):
-            ptr, n, keep = msa, len(msa), msa
-        else:
-            import numpy as np
-            keep = np.frombuffer(msa, dtype=np.uint8)
-            ptr, n = ctypes.c_void_p(keep.ctypes.data), int(keep.size)
+        ptr, n, keep = _input(msa)
         self._check(self._lib.edsx_msa_transform_batched(self._h, ptr, n, context_len, batches, ctypes.byref(e), ctypes.byref(s),
                                                          ctypes.byref(used)))
         del keep
@@ -426,8 +436,7 @@ class Context:
     def leds_merge(self, eds, seds=None, context_len=1, compact=True):
         o, so = _Buf(), _Buf()
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
-        self._check(self._lib.edsx_leds_merge(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0,
+        self._check(self._lib.edsx_leds_merge(self._h, eds, len(eds), *_opt(seds),
                                               context_len, 1 if compact else 0, ctypes.byref(o), ctypes.byref(so)))
         return self._take(o), self._take(so)
 
@@ -436,7 +445,7 @@ class Context:
         st = EdsStatistics()
         self._check(self._lib.edsx_eds_stats(self._h, eds, len(eds), seds, len(seds) if seds is not None else 0,
                                              context_len, ctypes.byref(st)))
-        return {n: getattr(st, n) for n, _ in EdsStatistics._fields_}
+        return _fields(st, _raw)
 
     # ---- queries (EDS::generate_patterns / EDS::check_position on the GPU)
     def eds_genpatterns(self, eds, count, length, seed, witness=False):
@@ -462,7 +471,6 @@ class Context:
         -1 out_of_range, -2 invalid_argument."""
         import numpy as np
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
         pos = np.ascontiguousarray(positions, dtype=np.uint64)
         coff = np.ascontiguousarray(choice_off, dtype=np.uint64)
         ch = np.ascontiguousarray(choices, dtype=np.int32)
@@ -473,7 +481,7 @@ class Context:
         if len(coff) != n + 1 or len(poff) != n + 1:
             raise ValueError("choice_off and pattern_off need len(positions) + 1 entries")
         out = np.empty(n, dtype=np.int8)
-        self._check(self._lib.edsx_eds_check_positions(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0, n,
+        self._check(self._lib.edsx_eds_check_positions(self._h, eds, len(eds), *_opt(seds), n,
                                                        pos.ctypes.data, coff.ctypes.data, ch.ctypes.data, poff.ctypes.data,
                                                        pat.ctypes.data, out.ctypes.data))
         return out
@@ -482,7 +490,7 @@ class Context:
         """Counts and timing of the last eds_genpatterns / eds_check_positions call."""
         q = QueryInfo()
         self._check(self._lib.edsx_query_last_info(self._h, ctypes.byref(q)))
-        return {n: getattr(q, n) for n, _ in QueryInfo._fields_}
+        return _fields(q, _raw)
 
     def genrandomeds(self, total_bp, variability=0.10, min_alt=2, max_alt=4, var_len_max=10, snp_ratio=0.7,
                      alphabet="ACGT", min_context=0, seed=42):
@@ -505,7 +513,7 @@ class Context:
         """The compressed layer of the last gz_inflate / compressed=True call: which=0 the VCF (or the input), 1 the FASTA."""
         info = GzInfo()
         self._check(self._lib.edsx_gz_last_info(self._h, which, ctypes.byref(info)))
-        return {n: getattr(info, n) for n, _ in GzInfo._fields_}
+        return _fields(info, _raw)
 
     def vcf_transform(self, vcf, fasta, context_len=0, contig=None, compressed=False):
         """contig=None: the first FASTA record, CHROM ignored (the reference's rule).  contig=name: the record lines whose
@@ -514,18 +522,18 @@ class Context:
         e, s, st = _Buf(), _Buf(), VcfStats()
         vcf, fasta = bytes(vcf), bytes(fasta)
         if compressed:
-            name = None if contig is None else contig.encode() if isinstance(contig, str) else bytes(contig)
+            name = None if contig is None else _name(contig)
             rc = self._lib.edsx_vcf_transform_z(self._h, vcf, len(vcf), fasta, len(fasta), name, context_len,
                                                 ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
         elif contig is None:
             rc = self._lib.edsx_vcf_transform(self._h, vcf, len(vcf), fasta, len(fasta), context_len,
                                               ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
         else:
-            name = contig.encode() if isinstance(contig, str) else bytes(contig)
+            name = _name(contig)
             rc = self._lib.edsx_vcf_transform_contig(self._h, vcf, len(vcf), fasta, len(fasta), name, context_len,
                                                      ctypes.byref(e), ctypes.byref(s), ctypes.byref(st))
         self._check(rc)
-        return self._take(e), self._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+        return self._take(e), self._take(s), _fields(st)
 
     def vcf_session(self, vcf, fasta, compressed=False):
         return VcfSession(self, vcf, fasta, compressed)
@@ -539,13 +547,13 @@ class Context:
         """One-shot edsx_eds_spell_paths -> (fasta bytes, missing counts as numpy uint64)."""
         import numpy as np
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
+        sb, sn = _opt(seds)
         ids, nm, n_out = _path_args(paths, names)
         if paths is None or len(ids) == 0:                       # all paths: P records, learnt from the text
             n_out = max([int(x) for x in _re_ids(sb)] + [0]) if sb else 0
         miss = np.zeros(max(n_out, 1), dtype=np.uint64)
         f = _Buf()
-        self._check(self._lib.edsx_eds_spell_paths(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0,
+        self._check(self._lib.edsx_eds_spell_paths(self._h, eds, len(eds), sb, sn,
                                                    ids.ctypes.data if len(ids) else None, len(ids), nm,
                                                    prefix.encode() if prefix is not None else None, int(line_width),
                                                    ctypes.byref(f), miss.ctypes.data))
@@ -563,8 +571,7 @@ class Context:
         o, so = _Buf(), _Buf()
         hi, ti = ctypes.c_int(), ctypes.c_int()
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
-        self._check(self._lib.edsx_leds_merge_range(self._h, eds, len(eds), sb, len(sb) if sb is not None else 0,
+        self._check(self._lib.edsx_leds_merge_range(self._h, eds, len(eds), *_opt(seds),
                                                     context_len, 1 if compact else 0, 1 if head_sentinel else 0,
                                                     1 if tail_sentinel else 0, ctypes.byref(o), ctypes.byref(so),
                                                     ctypes.byref(hi), ctypes.byref(ti)))
@@ -601,7 +608,7 @@ class Context:
         vcf = bytes(vcf)
         self._check(self._lib.edsx_vcf_index(self._h, vcf, len(vcf), *[ctypes.byref(b) for b in bufs], ctypes.byref(st)))
         arrs = [np.frombuffer(self._take(b), dtype=np.uint64) for b in bufs]
-        return (*arrs, {n: int(getattr(st, n)) for n, _ in VcfStats._fields_})
+        return (*arrs, _fields(st))
 
     def vcf_sort_order(self, pos):
         """Permutation of the reference's std::sort for these positions (numpy uint64 -> uint32)."""
@@ -619,7 +626,7 @@ class Context:
         nxt = 0xFFFFFFFFFFFFFFFF if next_start is None else int(next_start)
         self._check(self._lib.edsx_vcf_transform_range(self._h, vcf_lines, len(vcf_lines), fasta, len(fasta), int(cur0),
                                                        nxt, ctypes.byref(e), ctypes.byref(s), ctypes.byref(st)))
-        return self._take(e), self._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+        return self._take(e), self._take(s), _fields(st)
 
     # ---- device-resident entry points (pointers are ints: tensor.data_ptr())
     def msa_plan_device(self, d_msa, n, context_len=0, stream=0):
@@ -636,18 +643,18 @@ class Context:
         rc = self._lib.edsx_msa_last_info(self._h, ctypes.byref(info))
         if rc != 0:
             raise EdsxError(rc, "no planned alignment")
-        return {n: int(getattr(info, n)) for n, _ in MsaInfo._fields_}
+        return _fields(info)
 
     def msa_edge_info(self):
         e = MsaEdges()
         self._check(self._lib.edsx_msa_edge_info(self._h, ctypes.byref(e)))
-        return {n: int(getattr(e, n)) for n, _ in MsaEdges._fields_}
+        return _fields(e)
 
     def msa_anchor_info(self, min_cols):
         """First / last common segment of at least min_cols columns of the planned alignment (see edsx.h)."""
         a = MsaAnchors()
         self._check(self._lib.edsx_msa_anchor_info(self._h, min_cols, ctypes.byref(a)))
-        return {n: int(getattr(a, n)) for n, _ in MsaAnchors._fields_}
+        return _fields(a)
 
     def msa_copy_columns(self, col0, ncols, n_rows):
         buf = ctypes.create_string_buffer(n_rows * ncols)
@@ -702,51 +709,34 @@ def _path_args(paths, names):
     if names is not None:
         if len(names) != len(ids) or len(ids) == 0:
             raise ValueError("names need one entry per explicitly requested path")
-        nm = (ctypes.c_char_p * len(ids))(*[x.encode() if isinstance(x, str) else bytes(x) for x in names])
+        nm = (ctypes.c_char_p * len(ids))(*[_name(x) for x in names])
     return ids, nm, len(ids)
 
 
-class PathSession:
+class PathSession(_Handle):
     """An EDS with sources kept tokenised in HBM (edsx_paths_*): the sequence of every path as FASTA.  The session owns its
     device tables: other calls on the context do not invalidate it."""
+    _destroy = "edsx_paths_close"
 
     def __init__(self, ctx, eds, seds):
         self._ctx, self._lib = ctx, ctx._lib
         eds = bytes(eds)
-        sb = bytes(seds) if seds is not None else None
         h = ctypes.c_void_p()
-        ctx._check(self._lib.edsx_paths_open(ctx._h, eds, len(eds), sb, len(sb) if sb is not None else 0, ctypes.byref(h)))
+        ctx._check(self._lib.edsx_paths_open(ctx._h, eds, len(eds), *_opt(seds), ctypes.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.edsx_paths_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def info(self):
         i = PathsInfo()
         self._ctx._check(self._lib.edsx_paths_info(self._h, ctypes.byref(i)))
-        return {n: int(getattr(i, n)) for n, _ in PathsInfo._fields_}
+        return _fields(i)
 
     @property
     def timing(self):
         """Of the last lengths / spell: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
         t = PathsTiming()
         self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
-        return {n: getattr(t, n) for n, _ in PathsTiming._fields_}
+        return _fields(t, _raw)
 
     def _ids(self, paths):
         import numpy as np
@@ -785,9 +775,10 @@ class PathSession:
         return self._ctx._take(f), miss[:n_out]
 
 
-class VcfSession:
+class VcfSession(_Handle):
     """A multi-contig VCF and a multi-record FASTA kept in HBM (edsx_vcf_session_*): the FASTA record index, the contig of
     every record line, and one transform per contig without another upload.  vcf=b"": the FASTA index alone."""
+    _destroy = "edsx_vcf_session_close"
 
     def __init__(self, ctx, vcf, fasta, compressed=False):
         self._ctx, self._lib = ctx, ctx._lib
@@ -803,30 +794,13 @@ class VcfSession:
                                                    ctypes.byref(h)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.edsx_vcf_session_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def contigs(self):
         """FASTA records in file order: dicts of the edsx_contig fields plus "name" (bytes)."""
         p, n = ctypes.POINTER(Contig)(), ctypes.c_size_t()
         self._ctx._check(self._lib.edsx_vcf_session_contigs(self._h, ctypes.byref(p), ctypes.byref(n)))
         out = []
         for i in range(n.value):
-            d = {f: int(getattr(p[i], f)) for f, _ in Contig._fields_}
+            d = _fields(p[i])
             if self._compressed:                                   # (name_off points into the inflated FASTA)
                 q, ln = ctypes.c_char_p(), ctypes.c_size_t()
                 self._ctx._check(self._lib.edsx_vcf_session_contig_name(self._h, i, ctypes.byref(q), ctypes.byref(ln)))
@@ -837,9 +811,8 @@ class VcfSession:
         return out
 
     def find(self, name):
-        name = name.encode() if isinstance(name, str) else bytes(name)
         i = ctypes.c_size_t()
-        self._ctx._check(self._lib.edsx_vcf_session_find(self._h, name, ctypes.byref(i)))
+        self._ctx._check(self._lib.edsx_vcf_session_find(self._h, _name(name), ctypes.byref(i)))
         return i.value
 
     def transform(self, contig, context_len=0):
@@ -848,12 +821,12 @@ class VcfSession:
         e, s, st = _Buf(), _Buf(), VcfStats()
         self._ctx._check(self._lib.edsx_vcf_session_transform(self._h, index, context_len, ctypes.byref(e), ctypes.byref(s),
                                                               ctypes.byref(st)))
-        return self._ctx._take(e), self._ctx._take(s), {n: int(getattr(st, n)) for n, _ in VcfStats._fields_}
+        return self._ctx._take(e), self._ctx._take(s), _fields(st)
 
     def info(self):
         st = VcfSessionStats()
         self._ctx._check(self._lib.edsx_vcf_session_info(self._h, ctypes.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in VcfSessionStats._fields_}
+        return _fields(st)
 
     def unknown_contigs(self):
         """[(name, record lines)] of the contigs the VCF names and the FASTA lacks."""

@@ -1,4 +1,14 @@
 // capi.hip — the extern "C" boundary declared in include/edsx.h.  No exceptions cross it.
+//
+// Every convention of the boundary has one definition, in the anonymous namespace below ("The boundary's
+// contract"):
+//   status_of          exception in flight -> status code and text; guarded(ctx, f) and guarded(multi, f) run f under it
+//   clear, zero        out-parameters before anything can fail: buffers {NULL, 0}, structs all zero
+//   give, take_copy    an edsx_buf receives a download buffer itself, or a malloc'ed copy of host data
+//   put                VcfCounters -> edsx_vcf_stats, with or without variant_groups
+//   or_empty           a NULL input of size 0 reads as an empty text
+//   vcf_result         the VCF transforms: counters out on success and on failure, then the l-EDS merge, then the buffers
+//   in_session         the one-shot entry points: open a session, run on it, close it, keep the status
 #include "../../include/edsx.h"
 
 #include "bgzf_device.hpp"
@@ -42,7 +52,21 @@ struct edsx_ctx {
     GzInfo gz[2];                            // compressed layer of the last *_z / edsx_gz_inflate call: VCF (or input), FASTA
 };
 
+struct edsx_multi_impl { std::unique_ptr<MultiMsa> m; std::string err; };
+
 namespace {
+
+// inside a catch (...): the status of the exception in flight, its text into err
+int status_of(std::string& err)
+{
+    try { throw; }
+    catch (const FormatError& ex) { err = ex.what(); return EDSX_ERR_INVALID_FORMAT; }
+    catch (const ParamError& ex) { err = ex.what(); return EDSX_ERR_INVALID_PARAMETER; }
+    catch (const LimitError& ex) { err = ex.what(); return EDSX_ERR_BUILD_FAILED; }
+    catch (const DeviceError& ex) { err = ex.what(); return EDSX_ERR_BUILD_FAILED; }
+    catch (const std::bad_alloc&) { err = "out of host memory"; return EDSX_ERR_BUILD_FAILED; }
+    catch (const std::exception& ex) { err = ex.what(); return EDSX_ERR_UNKNOWN; }
+}
 
 template <class F> int guarded(edsx_ctx* ctx, F&& f)
 {
@@ -53,18 +77,86 @@ template <class F> int guarded(edsx_ctx* ctx, F&& f)
         if (e != hipSuccess) throw DeviceError(std::string("hipSetDevice: ") + hipGetErrorString(e));
         f();
         return EDSX_OK;
-    } catch (const FormatError& ex) { ctx->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
-    } catch (const ParamError& ex) { ctx->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
-    } catch (const LimitError& ex) { ctx->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const DeviceError& ex) { ctx->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::bad_alloc&) { ctx->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::exception& ex) { ctx->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+    } catch (...) { return status_of(ctx->err); }
 }
 
-void take(edsx_buf* b, size_t n)
+// the multi handle: its ranks choose their devices themselves
+template <class F> int guarded(edsx_multi_impl* mi, F&& f)
+{
+    if (!mi) return EDSX_ERR_INVALID_PARAMETER;
+    try {
+        mi->err.clear();
+        f();
+        return EDSX_OK;
+    } catch (...) { return status_of(mi->err); }
+}
+
+template <class... B> void clear(B*... bufs)
+{
+    for (edsx_buf* b : {static_cast<edsx_buf*>(bufs)...}) if (b) { b->data = nullptr; b->size = 0; }
+}
+
+template <class T> void zero(T* out) { if (out) std::memset(out, 0, sizeof(*out)); }
+
+// the download buffer itself
+void give(edsx_buf* b, HostBytes& h)
+{
+    b->size = h.size;
+    b->data = h.release();
+}
+
+void take_copy(edsx_buf* b, const void* src, size_t n)
 {
     b->data = HostBytes::alloc(n);
     b->size = n;
+    if (n) std::memcpy(b->data, src, n);
+}
+
+void put(edsx_vcf_stats* stats, const VcfCounters& c, bool groups)
+{
+    if (!stats) return;
+    stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
+    stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
+    if (groups) stats->variant_groups = c.variant_groups;
+}
+
+const uint8_t* or_empty(const uint8_t* p)
+{
+    static const uint8_t none = 0;
+    return p ? p : &none;
+}
+
+// run(e, s, c) is a VCF transform.  The reference counts while parsing, before it can throw: the counters of the parse
+// survive a later error (variant_groups is known only after the transform).  context_len > 0: merge(e, s) turns the EDS
+// text into the l-EDS - LINEAR merge with defaults (compact), vcf_transforms.cpp:735-755 - with the counters already out.
+template <class Run, class Merge>
+void vcf_result(Run&& run, Merge&& merge, uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
+{
+    HostBytes e, s;
+    VcfCounters c;
+    try { run(e, s, c); } catch (...) { put(stats, c, false); throw; }
+    put(stats, c, true);
+    if (context_len > 0) merge(e, s);
+    give(eds, e);
+    give(seds, s);
+}
+
+void merge_in_place(edsx_ctx* ctx, HostBytes& e, HostBytes& s, uint32_t context_len)
+{
+    HostBytes lo, so;
+    ctx->merge.run(e.data, e.size, s.data, s.size, context_len, true, lo, so, nullptr);
+    std::swap(e.data, lo.data); std::swap(e.size, lo.size);
+    std::swap(s.data, so.data); std::swap(s.size, so.size);
+}
+
+// `opened` is the status of opening the session s: run body on it and close it.  The body's status is the call's, and
+// ctx->err stays: closing reports nothing.
+template <class S, class Body> int in_session(int opened, S*& s, void (*close)(S*), Body&& body)
+{
+    if (opened != EDSX_OK) return opened;
+    const int rc = body();
+    close(s);
+    return rc;
 }
 
 // everything the MSA entry points hold on the device goes back to the allocator
@@ -85,21 +177,13 @@ void msa_transform_whole(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, con
     // bytes (2D copies: free on the way up): the column scan's loads are then aligned (multi_gpu.hip).  Everything
     // else - small inputs, files the geometry walk does not accept - is copied as it is, and the transform itself
     // words what is wrong with it.
-    size_t dev_size = msa_size;
-    if (lay.ok) dev_size = (size_t)upload_row_image(msa, lay, 0, lay.L, ctx->d_in, ctx->host_tmp, st).bytes;
-    else {
-        ctx->d_in.ensure(msa_size);
-        EDSX_HIP(hipMemcpyAsync(ctx->d_in.ptr, msa, msa_size, hipMemcpyHostToDevice, st));
-    }
-    uint64_t E = 0, Q = 0;
-    ctx->msa.plan(ctx->d_in.as<uint8_t>(), dev_size, context_len, st, &E, &Q);
-    ctx->d_eds.ensure(E + 16);
-    ctx->d_seds.ensure(Q + 16);
-    ctx->msa.emit(ctx->d_eds.as<uint8_t>(), ctx->d_seds.as<uint8_t>(), st);
-    take(eds, E);
-    take(seds, Q);
-    PinnedDownload::copy(eds->data, ctx->d_eds.ptr, E, st);
-    PinnedDownload::copy(seds->data, ctx->d_seds.ptr, Q, st);
+    HostBytes e, q;
+    if (lay.ok) {
+        const size_t dev_size = (size_t)upload_row_image(msa, lay, 0, lay.L, ctx->d_in, ctx->host_tmp, st).bytes;
+        msa_image_to_text(ctx->msa, ctx->d_in, dev_size, context_len, ctx->d_eds, ctx->d_seds, e, q, st);
+    } else msa_transform_plain(ctx->msa, msa, msa_size, context_len, ctx->d_in, ctx->d_eds, ctx->d_seds, e, q, st);
+    give(eds, e);
+    give(seds, q);
 }
 
 // K column batches; false: this input is not cut (see msa_transform_batched)
@@ -110,8 +194,8 @@ bool msa_transform_in_batches(edsx_ctx* ctx, const uint8_t* msa, const MsaLayout
     const BatchResources R{&ctx->msa, ctx->mini.get(), &ctx->d_in, &ctx->d_eds, &ctx->d_seds, &ctx->d_mini, &ctx->host_tmp};
     HostBytes e, q;
     if (!msa_transform_batched(R, msa, lay, context_len, K, e, q, nullptr)) return false;
-    eds->size = e.size; eds->data = e.release();
-    seds->size = q.size; seds->data = q.release();
+    give(eds, e);
+    give(seds, q);
     return true;
 }
 
@@ -226,8 +310,6 @@ int edsx_msa_locate_segment(edsx_ctx* ctx, uint64_t col, uint64_t* seg, uint64_t
     });
 }
 
-struct edsx_multi_impl { std::unique_ptr<MultiMsa> m; std::string err; };
-
 int edsx_multi_create(const int* device_ids, int n, int use_rccl, edsx_multi** out)
 {
     if (!out) return EDSX_ERR_INVALID_PARAMETER;
@@ -249,23 +331,15 @@ const char* edsx_multi_last_error(const edsx_multi* m)
 }
 int edsx_msa_transform_multi(edsx_multi* m, const uint8_t* msa, size_t msa_size, uint32_t context_len, edsx_buf* eds, edsx_buf* seds)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
+    clear(eds, seds);
     edsx_multi_impl* mi = reinterpret_cast<edsx_multi_impl*>(m);
-    if (!mi || !msa || !eds || !seds) return EDSX_ERR_INVALID_PARAMETER;
-    try {
-        mi->err.clear();
+    if (!mi || !msa || !eds || !seds) return EDSX_ERR_INVALID_PARAMETER;       // (no text: the handle's last one stays)
+    return guarded(mi, [&] {
         HostBytes e, s;
         mi->m->transform(msa, msa_size, context_len, e, s);
-        eds->size = e.size; eds->data = e.release();
-        seds->size = s.size; seds->data = s.release();
-        return EDSX_OK;
-    } catch (const FormatError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
-    } catch (const ParamError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
-    } catch (const LimitError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const DeviceError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::bad_alloc&) { mi->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::exception& ex) { mi->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+        give(eds, e);
+        give(seds, s);
+    });
 }
 int edsx_multi_last_partition(const edsx_multi* m, int* partitioned, int* chains)
 {
@@ -279,36 +353,14 @@ int edsx_multi_last_partition(const edsx_multi* m, int* partitioned, int* chains
 int edsx_vcf_transform_multi(edsx_multi* m, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
                              uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     edsx_multi_impl* mi = reinterpret_cast<edsx_multi_impl*>(m);
-    if (!mi) return EDSX_ERR_INVALID_PARAMETER;
-    VcfCounters c;
-    auto put = [&](bool groups) {          // edsx_vcf_transform's stats, on success and on failure
-        if (!stats) return;
-        stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-        stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-        if (groups) stats->variant_groups = c.variant_groups;
-    };
-    try {
-        mi->err.clear();
+    return guarded(mi, [&] {
         if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
-        HostBytes e, s;
-        try {
-            mi->m->vcf_transform(vcf, vcf_size, fasta, fasta_size, e, s, c);
-        } catch (...) { put(false); throw; }     // the reference counts while parsing, before it can throw
-        put(true);
-        if (context_len > 0) mi->m->leds_merge(e, s, context_len);      // as edsx_vcf_transform: counters already out
-        eds->size = e.size; eds->data = e.release();
-        seds->size = s.size; seds->data = s.release();
-        return EDSX_OK;
-    } catch (const FormatError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
-    } catch (const ParamError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
-    } catch (const LimitError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const DeviceError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::bad_alloc&) { mi->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::exception& ex) { mi->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+        vcf_result([&](HostBytes& e, HostBytes& s, VcfCounters& c) { mi->m->vcf_transform(vcf, vcf_size, fasta, fasta_size, e, s, c); },
+                   [&](HostBytes& e, HostBytes& s) { mi->m->leds_merge(e, s, context_len); }, context_len, eds, seds, stats);
+    });
 }
 int edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out)
 {
@@ -325,24 +377,15 @@ int edsx_multi_last_vcf(const edsx_multi* m, edsx_vcf_multi_info* out)
 int edsx_leds_merge_multi(edsx_multi* m, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                           uint32_t context_len, int compact, edsx_buf* leds, edsx_buf* seds_out)
 {
-    if (leds) { leds->data = nullptr; leds->size = 0; }
-    if (seds_out) { seds_out->data = nullptr; seds_out->size = 0; }
+    clear(leds, seds_out);
     edsx_multi_impl* mi = reinterpret_cast<edsx_multi_impl*>(m);
-    if (!mi) return EDSX_ERR_INVALID_PARAMETER;
-    try {
-        mi->err.clear();
+    return guarded(mi, [&] {
         if (!leds || !seds_out || (!eds && eds_size)) throw ParamError("null argument");
         HostBytes out, sout;
         mi->m->leds_merge_multi(eds, eds_size, seds, seds_size, context_len, compact != 0, out, sout);
-        leds->size = out.size; leds->data = out.release();
-        seds_out->size = sout.size; seds_out->data = sout.release();
-        return EDSX_OK;
-    } catch (const FormatError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_FORMAT;
-    } catch (const ParamError& ex) { mi->err = ex.what(); return EDSX_ERR_INVALID_PARAMETER;
-    } catch (const LimitError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const DeviceError& ex) { mi->err = ex.what(); return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::bad_alloc&) { mi->err = "out of host memory"; return EDSX_ERR_BUILD_FAILED;
-    } catch (const std::exception& ex) { mi->err = ex.what(); return EDSX_ERR_UNKNOWN; }
+        give(leds, out);
+        give(seds_out, sout);
+    });
 }
 int edsx_multi_last_merge(const edsx_multi* m, edsx_merge_multi_info* out)
 {
@@ -366,8 +409,7 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
                        edsx_buf* eds, edsx_buf* seds)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
+    clear(eds, seds);
     return guarded(ctx, [&] {
         if (!msa || !eds || !seds) throw ParamError("null argument");
         if (msa_size == 0) throw FormatError("Invalid MSA: empty input");
@@ -379,14 +421,13 @@ int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint3
         catch (const OutOfDeviceMemory& ex) { oom = ex.what(); }
         // The alignment and its tables do not fit the device in one piece: column batches, each with the working set of
         // a K-th of the columns (the reference streams an alignment of any size, msa_transforms.cpp:36-90)
-        edsx_buf_free(eds); edsx_buf_free(seds);
         for (int K = 2; K <= 256 && lay.ok; K *= 2) {
             release_msa_buffers(ctx);
             try {
                 if (!msa_transform_in_batches(ctx, msa, lay, context_len, K, eds, seds)) break;
                 ctx->last_batches = K;
                 return;
-            } catch (const OutOfDeviceMemory& ex) { oom = ex.what(); edsx_buf_free(eds); edsx_buf_free(seds); }
+            } catch (const OutOfDeviceMemory& ex) { oom = ex.what(); }
         }
         release_msa_buffers(ctx);
         throw LimitError("the alignment does not fit the device, in one piece or in column batches (" + oom + ")");
@@ -396,8 +437,7 @@ int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint3
 int edsx_msa_transform_batched(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len, int batches,
                                edsx_buf* eds, edsx_buf* seds, int* batches_used)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
+    clear(eds, seds);
     if (batches_used) *batches_used = 0;
     return guarded(ctx, [&] {
         if (!msa || !eds || !seds) throw ParamError("null argument");
@@ -419,27 +459,24 @@ int edsx_msa_transform_batched(edsx_ctx* ctx, const uint8_t* msa, size_t msa_siz
 int edsx_leds_merge(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                     uint32_t context_len, int compact, edsx_buf* leds, edsx_buf* seds_out)
 {
-    if (leds) { leds->data = nullptr; leds->size = 0; }
-    if (seds_out) { seds_out->data = nullptr; seds_out->size = 0; }
+    clear(leds, seds_out);
     return guarded(ctx, [&] {
         if (!leds || !seds_out || (!eds && eds_size)) throw ParamError("null argument");
         HostBytes out, sout;
-        static const uint8_t none = 0;
-        ctx->merge.run(eds ? eds : &none, eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr);
-        leds->size = out.size; leds->data = out.release();       // the download buffers themselves
-        seds_out->size = sout.size; seds_out->data = sout.release();
+        ctx->merge.run(or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr);
+        give(leds, out);
+        give(seds_out, sout);
     });
 }
 
 int edsx_eds_stats(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                    uint32_t context_len, edsx_eds_statistics* out)
 {
-    if (out) std::memset(out, 0, sizeof(*out));
+    zero(out);
     return guarded(ctx, [&] {
         if (!out || (!eds && eds_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         EdsStats s{};
-        ctx->merge.stats(eds ? eds : &none, eds_size, seds, seds_size, context_len, s, nullptr);
+        ctx->merge.stats(or_empty(eds), eds_size, seds, seds_size, context_len, s, nullptr);
         out->n_symbols = s.n_symbols; out->n_chars = s.n_chars; out->n_strings = s.n_strings;
         out->num_degenerate_symbols = s.num_degenerate; out->total_change_size = s.total_change_size;
         out->num_common_chars = s.num_common_chars; out->num_empty_strings = s.num_empty_strings;
@@ -459,47 +496,40 @@ int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
                           uint32_t context_len, int compact, int head_sentinel, int tail_sentinel, edsx_buf* leds,
                           edsx_buf* seds_out, int* head_intact, int* tail_intact)
 {
-    if (leds) { leds->data = nullptr; leds->size = 0; }
-    if (seds_out) { seds_out->data = nullptr; seds_out->size = 0; }
+    clear(leds, seds_out);
     if (head_intact) *head_intact = 0;
     if (tail_intact) *tail_intact = 0;
     return guarded(ctx, [&] {
         if (!leds || !seds_out || !head_intact || !tail_intact || (!eds && eds_size)) throw ParamError("null argument");
         HostBytes out, sout;
-        static const uint8_t none = 0;
         MergeShard sh;
         sh.head_sentinel = head_sentinel != 0; sh.tail_sentinel = tail_sentinel != 0;
-        ctx->merge.run(eds ? eds : &none, eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr, &sh);
+        ctx->merge.run(or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr, &sh);
         *head_intact = sh.head_intact ? 1 : 0;
         *tail_intact = sh.tail_intact ? 1 : 0;
-        leds->size = out.size; leds->data = out.release();
-        seds_out->size = sout.size; seds_out->data = sout.release();
+        give(leds, out);
+        give(seds_out, sout);
     });
 }
 
 int edsx_eds_genpatterns(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t count, uint32_t pattern_length,
                          uint64_t seed, edsx_buf* patterns, edsx_buf* witness_pos, edsx_buf* witness_off, edsx_buf* witness_deg)
 {
-    for (edsx_buf* b : {patterns, witness_pos, witness_off, witness_deg}) if (b) { b->data = nullptr; b->size = 0; }
+    clear(patterns, witness_pos, witness_off, witness_deg);
     return guarded(ctx, [&] {
         const int nw = (witness_pos != nullptr) + (witness_off != nullptr) + (witness_deg != nullptr);
         if (!patterns || (!eds && eds_size) || (nw != 0 && nw != 3)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         HostBytes out;
         std::vector<u64> wpos, woff;
         std::vector<int32_t> wdeg;
-        ctx->query.genpatterns(ctx->merge, eds ? eds : &none, eds_size, count, pattern_length, seed, out, nw ? &wpos : nullptr,
+        ctx->query.genpatterns(ctx->merge, or_empty(eds), eds_size, count, pattern_length, seed, out, nw ? &wpos : nullptr,
                                nw ? &woff : nullptr, nw ? &wdeg : nullptr, nullptr);
         if (nw) {
-            take(witness_pos, 8 * wpos.size());
-            if (!wpos.empty()) std::memcpy(witness_pos->data, wpos.data(), 8 * wpos.size());
-            take(witness_off, 8 * woff.size());
-            std::memcpy(witness_off->data, woff.data(), 8 * woff.size());
-            take(witness_deg, 4 * wdeg.size());
-            if (!wdeg.empty()) std::memcpy(witness_deg->data, wdeg.data(), 4 * wdeg.size());
+            take_copy(witness_pos, wpos.data(), 8 * wpos.size());
+            take_copy(witness_off, woff.data(), 8 * woff.size());
+            take_copy(witness_deg, wdeg.data(), 4 * wdeg.size());
         }
-        patterns->size = out.size; patterns->data = out.data;      // the download buffer itself
-        out.data = nullptr; out.size = 0;
+        give(patterns, out);
     });
 }
 
@@ -511,9 +541,8 @@ int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size,
         if ((!eds && eds_size) || (n && (!common_pos || !choice_off || !pattern_off || !status_out)) ||
             (n && choice_off[n] && !choices) || (n && pattern_off[n] && !patterns))
             throw ParamError("null argument");
-        static const uint8_t none = 0;
         static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
-        ctx->query.check(ctx->merge, eds ? eds : &none, eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
+        ctx->query.check(ctx->merge, or_empty(eds), eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
                          reinterpret_cast<const u64*>(choice_off), choices, reinterpret_cast<const u64*>(pattern_off), patterns,
                          status_out, nullptr);
     });
@@ -532,11 +561,10 @@ int edsx_query_last_info(const edsx_ctx* ctx, edsx_query_info* out)
 int edsx_eds_scan_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t lo, uint64_t hi, uint32_t context_len,
                         edsx_eds_range_scan* out)
 {
-    if (out) std::memset(out, 0, sizeof(*out));
+    zero(out);
     return guarded(ctx, [&] {
         if (!out || (!eds && eds_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
-        const uint8_t* p = eds ? eds : &none;
+        const uint8_t* p = or_empty(eds);
         const EdsRangeScan s = ctx->scan.eds(p, eds_size, text_end(p, eds_size), lo, hi, context_len, nullptr);
         out->ok = s.ok ? 1 : 0;
         out->strings = s.strings;
@@ -553,10 +581,9 @@ int edsx_seds_scan_range(edsx_ctx* ctx, const uint8_t* seds, size_t seds_size, u
     return guarded(ctx, [&] {
         if (!ok || !braces || (!seds && seds_size) || (n_ordinals && (!ordinals || !set_start || !set_end)))
             throw ParamError("null argument");
-        static const uint8_t none = 0;
         static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
         u64 b = 0;
-        const bool good = ctx->scan.seds_count(seds ? seds : &none, seds_size, lo, hi, b, nullptr);
+        const bool good = ctx->scan.seds_count(or_empty(seds), seds_size, lo, hi, b, nullptr);
         *ok = good ? 1 : 0;
         *braces = b;
         if (good && n_ordinals)
@@ -570,37 +597,14 @@ int edsx_vcf_tokenised_on_device(const edsx_ctx* ctx) { return ctx && ctx->vcf.t
 int edsx_vcf_transform(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
                        uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     return guarded(ctx, [&] {
         if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
-        HostBytes e, s;
-        VcfCounters c;
-        try {
-            ctx->vcf.run(vcf ? vcf : &none, vcf_size, fasta ? fasta : &none, fasta_size, e, s, c, nullptr);
-        } catch (...) {
-            if (stats) {   // the reference counts while parsing, before it can throw
-                stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-                stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-            }
-            throw;
-        }
-        if (stats) {
-            stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-            stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-            stats->variant_groups = c.variant_groups;
-        }
-        if (context_len > 0) {   // vcf_transforms.cpp:735-755: EDS text -> LINEAR merge with defaults (compact)
-            HostBytes lo, so;
-            ctx->merge.run(e.data, e.size, s.data, s.size, context_len, true, lo, so, nullptr);
-            eds->size = lo.size; eds->data = lo.release();
-            seds->size = so.size; seds->data = so.release();
-            return;
-        }
-        eds->size = e.size; eds->data = e.release();           // the download buffers themselves
-        seds->size = s.size; seds->data = s.release();
+        vcf_result([&](HostBytes& e, HostBytes& s, VcfCounters& c) {
+                       ctx->vcf.run(or_empty(vcf), vcf_size, or_empty(fasta), fasta_size, e, s, c, nullptr);
+                   },
+                   [&](HostBytes& e, HostBytes& s) { merge_in_place(ctx, e, s, context_len); }, context_len, eds, seds, stats);
     });
 }
 
@@ -630,8 +634,7 @@ int edsx_vcf_session_open(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, co
     if (out) *out = nullptr;
     return guarded(ctx, [&] {
         if (!out || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
-        std::unique_ptr<edsx_vcf_session> s(new edsx_vcf_session(ctx, vcf ? vcf : &none, vcf_size, fasta ? fasta : &none, fasta_size));
+        std::unique_ptr<edsx_vcf_session> s(new edsx_vcf_session(ctx, or_empty(vcf), vcf_size, or_empty(fasta), fasta_size));
         s->s.open(nullptr);
         *out = s.release();
     });
@@ -657,40 +660,17 @@ int edsx_vcf_session_find(const edsx_vcf_session* s, const char* name, size_t* i
 int edsx_vcf_session_transform(edsx_vcf_session* s, size_t index, uint32_t context_len, edsx_buf* eds, edsx_buf* seds,
                                edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     if (!s) return EDSX_ERR_INVALID_PARAMETER;
     edsx_ctx* ctx = s->ctx;
     return guarded(ctx, [&] {
         if (!eds || !seds) throw ParamError("null argument");
-        HostBytes e, q;
-        VcfCounters c;
-        try {
-            s->s.transform(ctx->vcf, index, e, q, c, nullptr);
-            s->count_downloads();
-        } catch (...) {
-            s->count_downloads();
-            if (stats) {   // as edsx_vcf_transform: the counters of the parse survive a later error
-                stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-                stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-            }
-            throw;
-        }
-        if (stats) {
-            stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-            stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-            stats->variant_groups = c.variant_groups;
-        }
-        if (context_len > 0) {
-            HostBytes lo, so;
-            ctx->merge.run(e.data, e.size, q.data, q.size, context_len, true, lo, so, nullptr);
-            eds->size = lo.size; eds->data = lo.release();
-            seds->size = so.size; seds->data = so.release();
-            return;
-        }
-        eds->size = e.size; eds->data = e.release();
-        seds->size = q.size; seds->data = q.release();
+        vcf_result([&](HostBytes& e, HostBytes& q, VcfCounters& c) {
+                       try { s->s.transform(ctx->vcf, index, e, q, c, nullptr); } catch (...) { s->count_downloads(); throw; }
+                       s->count_downloads();
+                   },
+                   [&](HostBytes& e, HostBytes& q) { merge_in_place(ctx, e, q, context_len); }, context_len, eds, seds, stats);
     });
 }
 
@@ -706,13 +686,12 @@ int edsx_vcf_session_info(const edsx_vcf_session* s, edsx_vcf_session_stats* out
 
 int edsx_vcf_session_unknown_contigs(const edsx_vcf_session* s, edsx_buf* text)
 {
-    if (text) { text->data = nullptr; text->size = 0; }
+    clear(text);
     if (!s) return EDSX_ERR_INVALID_PARAMETER;
     return guarded(s->ctx, [&] {
         if (!text) throw ParamError("null argument");
         const std::string& t = s->s.unknown_contigs();
-        take(text, t.size());
-        if (!t.empty()) std::memcpy(text->data, t.data(), t.size());
+        take_copy(text, t.data(), t.size());
     });
 }
 
@@ -726,17 +705,14 @@ void edsx_vcf_session_close(edsx_vcf_session* s)
 int edsx_vcf_transform_contig(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
                               const char* contig, uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     edsx_vcf_session* s = nullptr;
-    int rc = edsx_vcf_session_open(ctx, vcf, vcf_size, fasta, fasta_size, &s);
-    if (rc != EDSX_OK) return rc;
-    size_t index = 0;
-    rc = edsx_vcf_session_find(s, contig, &index);
-    if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
-    edsx_vcf_session_close(s);                                   // (ctx->err stays: closing reports nothing)
-    return rc;
+    return in_session(edsx_vcf_session_open(ctx, vcf, vcf_size, fasta, fasta_size, &s), s, edsx_vcf_session_close, [&] {
+        size_t index = 0;
+        const int rc = edsx_vcf_session_find(s, contig, &index);
+        return rc == EDSX_OK ? edsx_vcf_session_transform(s, index, context_len, eds, seds, stats) : rc;
+    });
 }
 
 // ---- compressed input (bgzf_device.hip, inflate.hpp)
@@ -749,7 +725,7 @@ int edsx_gz_probe(const uint8_t* data, size_t size, int* kind)
 
 int edsx_bgzf_index(const uint8_t* data, size_t size, edsx_buf* blocks, uint64_t* text_size)
 {
-    if (blocks) { blocks->data = nullptr; blocks->size = 0; }
+    clear(blocks);
     if (text_size) *text_size = 0;
     if (!blocks || !text_size || (!data && size)) return EDSX_ERR_INVALID_PARAMETER;
     static_assert(sizeof(edsx_bgzf_block) == sizeof(gz::BgzfBlock) && offsetof(edsx_bgzf_block, isize) == offsetof(gz::BgzfBlock, isize),
@@ -758,8 +734,7 @@ int edsx_bgzf_index(const uint8_t* data, size_t size, edsx_buf* blocks, uint64_t
         std::vector<gz::BgzfBlock> tab;
         u64 n = 0;
         if (gz::gz_walk(data, size, n, [&](const gz::BgzfBlock& b) { tab.push_back(b); }) != gz::GZ_BGZF) return EDSX_ERR_INVALID_FORMAT;
-        take(blocks, tab.size() * sizeof(gz::BgzfBlock));
-        if (!tab.empty()) std::memcpy(blocks->data, tab.data(), blocks->size);
+        take_copy(blocks, tab.data(), tab.size() * sizeof(gz::BgzfBlock));
         *text_size = n;
     } catch (...) { return EDSX_ERR_BUILD_FAILED; }
     return EDSX_OK;
@@ -767,18 +742,17 @@ int edsx_bgzf_index(const uint8_t* data, size_t size, edsx_buf* blocks, uint64_t
 
 int edsx_gz_inflate(edsx_ctx* ctx, const uint8_t* data, size_t size, edsx_buf* text)
 {
-    if (text) { text->data = nullptr; text->size = 0; }
+    clear(text);
     return guarded(ctx, [&] {
         if (!text || (!data && size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         ctx->gz[0] = GzInfo(); ctx->gz[1] = GzInfo();
         GzText t;
-        gz_open(data ? data : &none, size, "input", t, ctx->gz[0], nullptr);
+        gz_open(or_empty(data), size, "input", t, ctx->gz[0], nullptr);
         HostBytes out;
         out.take(t.n);
         if (t.on_device) PinnedDownload::copy(out.data, t.dev.ptr, t.n, nullptr);     // (the caller asked for the text: not a text_d2h of a transform)
         else if (t.n) std::memcpy(out.data, t.on_host ? t.host.data() : t.plain, t.n);
-        text->size = out.size; text->data = out.release();
+        give(text, out);
     });
 }
 
@@ -795,11 +769,10 @@ namespace {
 // inflate both inputs (the VCF's errors first) and build the session on them
 edsx_vcf_session* open_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size, bool own, bool ignore_chrom)
 {
-    static const uint8_t none = 0;
     ctx->gz[0] = GzInfo(); ctx->gz[1] = GzInfo();
     GzText v, f;
-    gz_open(vcf ? vcf : &none, vcf_size, "VCF", v, ctx->gz[0], nullptr);
-    gz_open(fasta ? fasta : &none, fasta_size, "FASTA", f, ctx->gz[1], nullptr);
+    gz_open(or_empty(vcf), vcf_size, "VCF", v, ctx->gz[0], nullptr);
+    gz_open(or_empty(fasta), fasta_size, "FASTA", f, ctx->gz[1], nullptr);
     std::unique_ptr<edsx_vcf_session> s(new edsx_vcf_session(ctx, v, f, own, ignore_chrom));
     s->gz[0] = ctx->gz[0]; s->gz[1] = ctx->gz[1];
     try { s->s.open(nullptr); } catch (...) { s->count_downloads(); throw; }
@@ -830,20 +803,18 @@ int edsx_vcf_session_contig_name(const edsx_vcf_session* s, size_t index, const 
 int edsx_vcf_transform_z(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size, const char* contig,
                          uint32_t context_len, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     edsx_vcf_session* s = nullptr;
-    int rc = guarded(ctx, [&] {
+    const int opened = guarded(ctx, [&] {
         if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
         s = open_z(ctx, vcf, vcf_size, fasta, fasta_size, false, contig == nullptr);
     });
-    if (rc != EDSX_OK) return rc;
-    size_t index = 0;
-    if (contig) rc = edsx_vcf_session_find(s, contig, &index);
-    if (rc == EDSX_OK) rc = edsx_vcf_session_transform(s, index, context_len, eds, seds, stats);
-    edsx_vcf_session_close(s);
-    return rc;
+    return in_session(opened, s, edsx_vcf_session_close, [&] {
+        size_t index = 0;
+        const int rc = contig ? edsx_vcf_session_find(s, contig, &index) : EDSX_OK;
+        return rc == EDSX_OK ? edsx_vcf_session_transform(s, index, context_len, eds, seds, stats) : rc;
+    });
 }
 
 // ---- path sessions (path_device.hip)
@@ -858,9 +829,8 @@ int edsx_paths_open(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
     if (out) *out = nullptr;
     return guarded(ctx, [&] {
         if (!out || (!eds && eds_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         std::unique_ptr<edsx_paths_session> s(new edsx_paths_session{ctx, {}});
-        s->p.open(eds ? eds : &none, eds_size, seds, seds_size, nullptr);
+        s->p.open(or_empty(eds), eds_size, seds, seds_size, nullptr);
         *out = s.release();
     });
 }
@@ -887,7 +857,7 @@ int edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, uin
 int edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
                      uint64_t line_width, edsx_buf* fasta, uint64_t* missing)
 {
-    if (fasta) { fasta->data = nullptr; fasta->size = 0; }
+    clear(fasta);
     if (!s) return EDSX_ERR_INVALID_PARAMETER;
     return guarded(s->ctx, [&] {
         if (!fasta || (n && !ids)) throw ParamError("null argument");
@@ -901,7 +871,7 @@ int edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const
         HostBytes out;
         s->p.spell(n ? reinterpret_cast<const u64*>(ids) : all.data(), n ? n : all.size(), names, prefix, line_width, out,
                    reinterpret_cast<u64*>(missing), nullptr);
-        fasta->size = out.size; fasta->data = out.release();     // the download buffer itself
+        give(fasta, out);
     });
 }
 
@@ -925,40 +895,28 @@ int edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, con
                          const uint64_t* ids, size_t n, const char* const* names, const char* prefix, uint64_t line_width,
                          edsx_buf* fasta, uint64_t* missing)
 {
-    if (fasta) { fasta->data = nullptr; fasta->size = 0; }
+    clear(fasta);
     edsx_paths_session* s = nullptr;
-    int rc = edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s);
-    if (rc != EDSX_OK) return rc;
-    rc = edsx_paths_spell(s, ids, n, names, prefix, line_width, fasta, missing);
-    edsx_paths_close(s);                                         // (ctx->err stays: closing reports nothing)
-    return rc;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_spell(s, ids, n, names, prefix, line_width, fasta, missing); });
 }
-
-namespace {
-void take_u64(edsx_buf* b, const std::vector<u64>& v)
-{
-    take(b, 8 * v.size());
-    if (!v.empty()) std::memcpy(b->data, v.data(), 8 * v.size());
-}
-} // namespace
 
 int edsx_vcf_index(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, edsx_buf* pos, edsx_buf* reflen, edsx_buf* line_off,
                    edsx_buf* line_len, edsx_vcf_stats* stats)
 {
-    for (edsx_buf* b : {pos, reflen, line_off, line_len}) if (b) { b->data = nullptr; b->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(pos, reflen, line_off, line_len);
+    zero(stats);
     return guarded(ctx, [&] {
         if (!pos || !reflen || !line_off || !line_len || (!vcf && vcf_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         std::vector<u64> p, r, lo, ll;
         VcfCounters c;
-        if (!ctx->vcf.index_device(vcf ? vcf : &none, vcf_size, nullptr, p, r, lo, ll, c))   // plain text: on the GPU
-            vcf_index(vcf ? vcf : &none, vcf_size, p, r, lo, ll, c);
-        if (stats) {
-            stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-            stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-        }
-        take_u64(pos, p); take_u64(reflen, r); take_u64(line_off, lo); take_u64(line_len, ll);
+        if (!ctx->vcf.index_device(or_empty(vcf), vcf_size, nullptr, p, r, lo, ll, c))   // plain text: on the GPU
+            vcf_index(or_empty(vcf), vcf_size, p, r, lo, ll, c);
+        put(stats, c, false);
+        take_copy(pos, p.data(), 8 * p.size());
+        take_copy(reflen, r.data(), 8 * r.size());
+        take_copy(line_off, lo.data(), 8 * lo.size());
+        take_copy(line_len, ll.data(), 8 * ll.size());
     });
 }
 
@@ -974,24 +932,18 @@ int edsx_vcf_sort_order(const uint64_t* pos, size_t n, uint32_t* order_out)
 int edsx_vcf_transform_range(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, const uint8_t* fasta, size_t fasta_size,
                              uint64_t cur0, uint64_t next_start, edsx_buf* eds, edsx_buf* seds, edsx_vcf_stats* stats)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    clear(eds, seds);
+    zero(stats);
     return guarded(ctx, [&] {
         if (!eds || !seds || (!vcf && vcf_size) || (!fasta && fasta_size)) throw ParamError("null argument");
-        static const uint8_t none = 0;
         HostBytes e, s;
         VcfCounters c;
         VcfRange range;
         range.presorted = true; range.cur0 = cur0; range.next_start = next_start;
-        ctx->vcf.run(vcf ? vcf : &none, vcf_size, fasta ? fasta : &none, fasta_size, e, s, c, nullptr, range);
-        if (stats) {
-            stats->total_variants = c.total_variants; stats->processed_variants = c.processed_variants;
-            stats->skipped_malformed = c.skipped_malformed; stats->skipped_unsupported_sv = c.skipped_unsupported_sv;
-            stats->variant_groups = c.variant_groups;
-        }
-        eds->size = e.size; eds->data = e.release();
-        seds->size = s.size; seds->data = s.release();
+        ctx->vcf.run(or_empty(vcf), vcf_size, or_empty(fasta), fasta_size, e, s, c, nullptr, range);
+        put(stats, c, true);
+        give(eds, e);
+        give(seds, s);
     });
 }
 
@@ -999,8 +951,7 @@ int edsx_genrandomeds(edsx_ctx* ctx, uint64_t total_bp, double variability, uint
                       uint32_t var_len_max, double snp_ratio, const char* alphabet, uint64_t min_context, uint64_t seed,
                       edsx_buf* eds, edsx_buf* seds, uint64_t* n_sites)
 {
-    if (eds) { eds->data = nullptr; eds->size = 0; }
-    if (seds) { seds->data = nullptr; seds->size = 0; }
+    clear(eds, seds);
     return guarded(ctx, [&] {
         if (!eds || !seds || !alphabet) throw ParamError("null argument");
         GenParams gp{};
@@ -1014,21 +965,20 @@ int edsx_genrandomeds(edsx_ctx* ctx, uint64_t total_bp, double variability, uint
         u64 sites = 0;
         ctx->gen.run(gp, e, s, sites, nullptr);
         if (n_sites) *n_sites = sites;
-        eds->size = e.size; eds->data = e.release();
-        seds->size = s.size; seds->data = s.release();
+        give(eds, e);
+        give(seds, s);
     });
 }
 
 int edsx_genvcf(edsx_ctx* ctx, uint64_t ref_len, uint64_t n_records, uint32_t n_samples, uint64_t seed, edsx_buf* vcf, edsx_buf* fasta)
 {
-    if (vcf) { vcf->data = nullptr; vcf->size = 0; }
-    if (fasta) { fasta->data = nullptr; fasta->size = 0; }
+    clear(vcf, fasta);
     return guarded(ctx, [&] {
         if (!vcf || !fasta) throw ParamError("null argument");
         HostBytes v, f;
         ctx->genvcf.run(ref_len, n_records, n_samples, seed, v, f, nullptr);
-        vcf->size = v.size; vcf->data = v.release();
-        fasta->size = f.size; fasta->data = f.release();
+        give(vcf, v);
+        give(fasta, f);
     });
 }
 

@@ -19,7 +19,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <thread>
 
 namespace edsx {
 
@@ -191,16 +190,7 @@ void MultiMsa::leds_merge_multi(const uint8_t* eds, size_t eds_n, const uint8_t*
     sh.leds = &leds; sh.sout = &seds_out;
     sh.error.assign(N, nullptr);
     sh.eds_h2d.assign(N, 0); sh.seds_h2d.assign(N, 0); sh.range_bytes.assign(N, NONE);
-    bar_->reset();
-    std::vector<std::thread> th;
-    for (int r = 1; r < N; r++) th.emplace_back([&, r] { run_rank_merge(r, sh); });
-    run_rank_merge(0, sh);
-    for (auto& t : th) t.join();
-    if (bar_->failed()) {
-        const int fr = bar_->failed_rank();
-        if (fr >= 0 && fr < N && sh.error[fr]) std::rethrow_exception(sh.error[fr]);
-        throw DeviceError(bar_->message());
-    }
+    run_ranks([&](int r) { run_rank_merge(r, sh); }, &sh.error);
     MergeMultiInfo& info = merge_info_;
     info.fallback = sh.fallback;
     info.partitioned = sh.fallback == 0;

@@ -252,6 +252,29 @@ RowImage upload_row_image(const uint8_t* fasta, const MsaLayout& lay, u64 c0, u6
     return ri;
 }
 
+// an alignment image of n bytes in d_img on the current device -> plan, emit, download
+void msa_image_to_text(MsaPipeline& p, const DevBuf& d_img, size_t n, uint32_t l, DevBuf& d_eds, DevBuf& d_seds, HostBytes& eds,
+                       HostBytes& seds, hipStream_t st)
+{
+    uint64_t E = 0, Q = 0;
+    p.plan(d_img.as<uint8_t>(), n, l, st, &E, &Q);
+    d_eds.ensure(E + 16);
+    d_seds.ensure(Q + 16);
+    p.emit(d_eds.as<uint8_t>(), d_seds.as<uint8_t>(), st);
+    eds.take(E);
+    seds.take(Q);
+    PinnedDownload::copy(eds.data, d_eds.ptr, E, st);
+    PinnedDownload::copy(seds.data, d_seds.ptr, Q, st);
+}
+
+void msa_transform_plain(MsaPipeline& p, const uint8_t* msa, size_t n, uint32_t l, DevBuf& d_img, DevBuf& d_eds, DevBuf& d_seds,
+                         HostBytes& eds, HostBytes& seds, hipStream_t st)
+{
+    d_img.ensure(n);
+    EDSX_HIP(hipMemcpyAsync(d_img.ptr, msa, n, hipMemcpyHostToDevice, st));
+    msa_image_to_text(p, d_img, n, l, d_eds, d_seds, eds, seds, st);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // MultiMsa
 // ---------------------------------------------------------------------------------------------------------------
@@ -291,31 +314,37 @@ void MultiMsa::transform(const uint8_t* fasta, size_t n, uint32_t context_len, H
         // words; an l-EDS whose slabs have no standalone common run to anchor the stitch on is not partitioned either.
         Rank& r0 = *ranks_[0];
         EDSX_HIP(hipSetDevice(r0.device));
-        r0.d_img.ensure(n);
-        EDSX_HIP(hipMemcpyAsync(r0.d_img.ptr, fasta, n, hipMemcpyHostToDevice, nullptr));
-        uint64_t E = 0, Q = 0;
-        r0.slab.plan(r0.d_img.as<uint8_t>(), n, context_len, nullptr, &E, &Q);
-        r0.d_eds.ensure(E + 16); r0.d_seds.ensure(Q + 16);
-        r0.slab.emit(r0.d_eds.as<uint8_t>(), r0.d_seds.as<uint8_t>(), nullptr);
-        eds.take(E); seds.take(Q);
-        PinnedDownload::copy(eds.data, r0.d_eds.ptr, E, nullptr);
-        PinnedDownload::copy(seds.data, r0.d_seds.ptr, Q, nullptr);
+        msa_transform_plain(r0.slab, fasta, n, context_len, r0.d_img, r0.d_eds, r0.d_seds, eds, seds, nullptr);
     };
     if (!partitioned_) { whole_on_rank0(); return; }
-    bar_->reset();
     no_anchor_ = false;
     piece_e_.assign(N, 0); piece_s_.assign(N, 0);
-    std::vector<std::thread> th;
-    auto one = [&](int r) { if (context_len) run_rank_leds(r, fasta, lay, context_len, eds, seds); else run_rank(r, fasta, n, lay, eds, seds); };
-    for (int r = 1; r < N; r++) th.emplace_back([&, r] { one(r); });
-    one(0);
-    for (auto& t : th) t.join();
-    if (bar_->failed()) {
-        const std::string m = bar_->message();
-        if (m.rfind("Invalid MSA", 0) == 0) throw FormatError(m);
-        throw DeviceError(m);
+    // (no typed rethrow here: a failed rank's text decides between a format error and a device error)
+    try {
+        run_ranks([&](int r) { if (context_len) run_rank_leds(r, fasta, lay, context_len, eds, seds); else run_rank(r, fasta, n, lay, eds, seds); },
+                  nullptr);
+    } catch (const DeviceError& ex) {
+        if (std::string(ex.what()).rfind("Invalid MSA", 0) == 0) throw FormatError(ex.what());
+        throw;
     }
     if (no_anchor_) { partitioned_ = false; chains_ = 0; whole_on_rank0(); }
+}
+
+// The rank threads of one call: ranks 1 .. N-1 on threads of their own, rank 0 on the caller's.  After a failure (the
+// barrier keeps the one of the lowest rank) that rank's own exception is thrown again where the caller has kept them
+// (`errors`, one per rank), else a DeviceError with its text.
+void MultiMsa::run_ranks(const std::function<void(int)>& one_rank, const std::vector<std::exception_ptr>* errors)
+{
+    const int N = world();
+    bar_->reset();
+    std::vector<std::thread> th;
+    for (int r = 1; r < N; r++) th.emplace_back([&, r] { one_rank(r); });
+    one_rank(0);
+    for (auto& t : th) t.join();
+    if (!bar_->failed()) return;
+    const int fr = bar_->failed_rank();
+    if (errors && fr >= 0 && fr < N && (*errors)[fr]) std::rethrow_exception((*errors)[fr]);
+    throw DeviceError(bar_->message());
 }
 
 // One rank.  Every phase ends in the thread barrier, which also carries a failure of any rank to all of them: nobody

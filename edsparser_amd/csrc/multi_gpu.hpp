@@ -18,6 +18,8 @@
 #include "merge_scan.hpp"
 #include "vcf_device.hpp"
 
+#include <exception>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -46,6 +48,11 @@ MsaLayout msa_layout(const uint8_t* f, size_t n);
 struct RowImage { u64 rows = 0, cols = 0, hdr0 = 0, hdr = 0, bytes = 0; };
 RowImage upload_row_image(const uint8_t* fasta, const MsaLayout& lay, u64 c0, u64 c1, DevBuf& d_img, std::vector<uint8_t>& host_tmp,
                           hipStream_t st);
+// one alignment image on the current device: the n bytes in d_img -> plan, emit, download; _plain uploads the file as it is first
+void msa_image_to_text(MsaPipeline& p, const DevBuf& d_img, size_t n, uint32_t l, DevBuf& d_eds, DevBuf& d_seds, HostBytes& eds,
+                       HostBytes& seds, hipStream_t st);
+void msa_transform_plain(MsaPipeline& p, const uint8_t* msa, size_t n, uint32_t l, DevBuf& d_img, DevBuf& d_eds, DevBuf& d_seds,
+                         HostBytes& eds, HostBytes& seds, hipStream_t st);
 
 // msa2eds in K column batches on one GPU (working set of one slab; see multi_gpu.hip).  false: not batched - the image is
 // not a plain uniform alignment, the batches would be too narrow, or (l > 0) a slab has no standalone common runs to
@@ -110,6 +117,8 @@ private:
     void run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, HostBytes& eds, HostBytes& seds);
     void run_rank_vcf(int r, VcfShared& sh);
     void run_rank_merge(int r, MergeShared& sh);
+    // one_rank(r) on a thread per rank (multi_gpu.hip); throws what the failed rank threw (errors[rank]) or a DeviceError
+    void run_ranks(const std::function<void(int)>& one_rank, const std::vector<std::exception_ptr>* errors);
     std::vector<int> devices_;
     std::vector<std::unique_ptr<Rank>> ranks_;
     std::unique_ptr<Exchange> xch_;

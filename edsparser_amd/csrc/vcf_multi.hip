@@ -20,7 +20,6 @@
 #include <algorithm>
 #include <cstring>
 #include <numeric>
-#include <thread>
 
 namespace edsx {
 
@@ -50,7 +49,7 @@ struct MultiMsa::VcfShared {
     const uint8_t* vcf; u64 vcf_n; const uint8_t* fasta; u64 fasta_n;
     u64 seq_start, lw, rest_from;
     HostBytes* eds; HostBytes* seds;
-    VcfCounters stats;                          // written by rank 0 as soon as known
+    VcfCounters* stats;                         // the caller's: written by rank 0 as soon as known
     std::vector<std::exception_ptr> error;      // per rank
 };
 
@@ -114,7 +113,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
     meta.regular = sh.lw > 0 && rec_end == sh.fasta_n && flags == 0 &&
                    (offgrid == ~0ull || (offgrid + 1 == rec_end && (offgrid - sh.seq_start) % (sh.lw + 1) != 0));
     const u64 n = base[N];
-    if (r == 0) sh.stats = tot;
+    if (r == 0) *sh.stats = tot;
     if (!phase([&] {
             // the single transform refuses this after its tokeniser has counted the records (vcf_device.hip)
             if (sh.lw == 0) throw FormatError("Invalid FASTA format: empty first sequence line");
@@ -208,7 +207,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
                 if (r != 0) return;
                 VcfCounters c;
                 me.vcf->run(sh.vcf_n ? sh.vcf : &none, sh.vcf_n, sh.fasta, sh.fasta_n, *sh.eds, *sh.seds, c, st);
-                sh.stats = c;
+                *sh.stats = c;
             })) return;
         const u64 mine_h2d = r == 0 ? h2d + me.vcf->fasta_h2d_bytes() : h2d;
         std::vector<u64> h2ds(N);
@@ -294,7 +293,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
             info.partitioned = nonempty.size() >= 2;
             info.fasta_windowed = meta.regular;
             for (int k = 0; k < N; k++) {
-                sh.stats.variant_groups += piece[5 * k + 2];
+                sh.stats->variant_groups += piece[5 * k + 2];
                 info.moved_line_bytes += piece[5 * k + 3];
                 info.fasta_h2d_bytes_max = std::max(info.fasta_h2d_bytes_max, piece[5 * k + 4]);
             }
@@ -323,19 +322,9 @@ void MultiMsa::vcf_transform(const uint8_t* vcf, size_t vcf_n, const uint8_t* fa
     sh.vcf = vcf_n ? vcf : &none; sh.vcf_n = vcf_n; sh.fasta = fasta_n ? fasta : &none; sh.fasta_n = fasta_n;
     // header and first line on the host, with the unpartitioned transform's error texts (and, like it, no counters yet)
     fasta_head(sh.fasta, fasta_n, sh.seq_start, sh.lw, sh.rest_from);
-    sh.eds = &eds; sh.seds = &seds;
+    sh.eds = &eds; sh.seds = &seds; sh.stats = &stats;
     sh.error.assign(N, nullptr);
-    bar_->reset();
-    std::vector<std::thread> th;
-    for (int r = 1; r < N; r++) th.emplace_back([&, r] { run_rank_vcf(r, sh); });
-    run_rank_vcf(0, sh);
-    for (auto& t : th) t.join();
-    stats = sh.stats;
-    if (bar_->failed()) {
-        const int fr = bar_->failed_rank();
-        if (fr >= 0 && fr < N && sh.error[fr]) std::rethrow_exception(sh.error[fr]);
-        throw DeviceError(bar_->message());
-    }
+    run_ranks([&](int r) { run_rank_vcf(r, sh); }, &sh.error);
 }
 
 void MultiMsa::leds_merge(HostBytes& eds, HostBytes& seds, uint32_t context_len)
