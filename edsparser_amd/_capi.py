@@ -220,6 +220,8 @@ def load_library():
     lib.edsx_eds_check_positions.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                              ctypes.c_size_t] + [ctypes.c_void_p] * 6
     lib.edsx_query_last_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
+    lib.edsx_eds_locate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                    ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32] + [P(_Buf)] * 6
     lib.edsx_paths_open.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                     P(ctypes.c_void_p)]
     lib.edsx_paths_info.argtypes = [ctypes.c_void_p, P(PathsInfo)]
@@ -234,6 +236,10 @@ def load_library():
                                          P(_Buf), ctypes.c_void_p]
     _LIB = lib
     return lib
+
+
+# edsx_locate_hit as a numpy structured dtype
+LOCATE_HIT = [("common_pos", "<u8"), ("symbol", "<u8"), ("string", "<u8"), ("offset", "<u8")]
 
 
 def _take(lib, b):
@@ -486,8 +492,29 @@ class Context(_Handle):
                                                        pat.ctypes.data, out.ctypes.data))
         return out
 
+    def eds_locate(self, eds, patterns, seds=None, max_hits=1024, common_only=False):
+        """Every occurrence of every pattern (a list of bytes) in the .eds (+ .seds), in check_position's coordinates.
+        Returns numpy arrays (hit_off, hits, choice_off, choices, totals, flags): the hits of pattern q are
+        hits[hit_off[q]:hit_off[q + 1]] (LOCATE_HIT: common_pos, 2**64-1 for a start inside a degenerate symbol; symbol;
+        string, its index in the symbol; offset), ascending by (symbol, string, offset), then by choices; hit h chose the
+        degenerate string numbers choices[choice_off[h]:choice_off[h + 1]].  At most max_hits hits come back per pattern:
+        flags[q] bit 0 says some were left out (totals[q] is then a lower bound), bit 1 that a walk was cut at its 65th
+        choice.  common_only: only starts in common symbols."""
+        import numpy as np
+        patterns = [bytes(p) for p in patterns]
+        poff = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        poff[1:] = np.cumsum([len(p) for p in patterns], dtype=np.uint64)
+        text = np.frombuffer(b"".join(patterns), dtype=np.uint8)
+        bufs = [_Buf() for _ in range(6)]
+        ptr, n, keep = _input(eds)
+        self._check(self._lib.edsx_eds_locate(self._h, ptr, n, *_opt(seds), len(patterns), poff.ctypes.data, text.ctypes.data,
+                                              int(max_hits), 1 if common_only else 0, *[ctypes.byref(b) for b in bufs]))
+        del keep
+        dtypes = (np.uint64, LOCATE_HIT, np.uint64, np.int32, np.uint64, np.uint8)
+        return tuple(np.frombuffer(self._take(b), dtype=d) for b, d in zip(bufs, dtypes))
+
     def query_last_info(self):
-        """Counts and timing of the last eds_genpatterns / eds_check_positions call."""
+        """Counts and timing of the last eds_genpatterns / eds_check_positions / eds_locate call."""
         q = QueryInfo()
         self._check(self._lib.edsx_query_last_info(self._h, ctypes.byref(q)))
         return _fields(q, _raw)

@@ -14,6 +14,7 @@
 #include "bgzf_device.hpp"
 #include "genrandom.hpp"
 #include "genvcf.hpp"
+#include "locate_device.hpp"
 #include "merge_device.hpp"
 #include "merge_scan.hpp"
 #include "msa_device.hpp"
@@ -41,6 +42,7 @@ struct edsx_ctx {
     MergePipeline merge;
     RangeScanner scan;                       // edsx_eds_scan_range / edsx_seds_scan_range
     QueryPipeline query;                     // edsx_eds_genpatterns / edsx_eds_check_positions
+    LocatePipeline locate;                   // edsx_eds_locate, over query's tables
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -545,6 +547,33 @@ int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size,
         ctx->query.check(ctx->merge, or_empty(eds), eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
                          reinterpret_cast<const u64*>(choice_off), choices, reinterpret_cast<const u64*>(pattern_off), patterns,
                          status_out, nullptr);
+    });
+}
+
+int edsx_eds_locate(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, size_t n,
+                    const uint64_t* pattern_off, const uint8_t* patterns, uint64_t max_hits, uint32_t flags, edsx_buf* hit_off,
+                    edsx_buf* hits, edsx_buf* choice_off, edsx_buf* choices, edsx_buf* totals, edsx_buf* pattern_flags)
+{
+    clear(hit_off, hits, choice_off, choices, totals, pattern_flags);
+    return guarded(ctx, [&] {
+        if (!hit_off || !hits || !choice_off || !choices || !totals || !pattern_flags || (!eds && eds_size) ||
+            (n && (!pattern_off || !patterns)))
+            throw ParamError("null argument");
+        if (flags & ~EDSX_LOCATE_COMMON_ONLY) throw ParamError("edsx_eds_locate: unknown flag");
+        static_assert(sizeof(u64) == sizeof(uint64_t) && sizeof(LocateHit) == sizeof(edsx_locate_hit) &&
+                      offsetof(LocateHit, offset) == offsetof(edsx_locate_hit, offset) && LocatePipeline::MAX_CHOICES == EDSX_LOCATE_MAX_CHOICES,
+                      "edsx_locate_hit is LocateHit");
+        const u64 none = 0;
+        LocateOut o;
+        ctx->locate.run(ctx->query, ctx->merge, or_empty(eds), eds_size, seds, seds_size, n,
+                        n ? reinterpret_cast<const u64*>(pattern_off) : &none, patterns, max_hits,
+                        (flags & EDSX_LOCATE_COMMON_ONLY) != 0, o, nullptr);
+        take_copy(hit_off, o.hit_off.data(), 8 * o.hit_off.size());
+        take_copy(hits, o.hits.data(), sizeof(LocateHit) * o.hits.size());
+        take_copy(choice_off, o.choice_off.data(), 8 * o.choice_off.size());
+        take_copy(choices, o.choices.data(), 4 * o.choices.size());
+        take_copy(totals, o.totals.data(), 8 * o.totals.size());
+        take_copy(pattern_flags, o.flags.data(), o.flags.size());
     });
 }
 

@@ -41,6 +41,7 @@ public:
 
 private:
     friend class QueryPipeline;              // pattern sampling / position checks read the tokenised arrays (query_device.hip)
+    friend class LocatePipeline;             // pattern search reads them through QueryPipeline's tables (locate_device.hip)
     friend class PathPipeline;               // path spelling reads them too, from a pipeline of its own (path_device.hip)
     struct Loaded { u64 n0 = 0, m = 0, head_len = 0; u32 W = 1; bool head_single = false, tail_single = false; };
     void prepare(const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, bool linear, hipStream_t st, Loaded& L);

@@ -137,9 +137,8 @@ struct CheckArgs {
 // (decode_degenerate_string_number :1051-1095, with the pins of EDS::check_position) and compares characters, but keeps
 // walking after a mismatch, since an error met later wins (:1047 compares at the end).  With sources, the walk of
 // calculate_path_intersection (:1300-1418) visits the same symbols: its first empty step E is found word by word (the
-// lane re-walks the T valid steps once per 64-bit word: no W-word accumulator), and an error at step T counts only when
-// E >= T.  A set with bit 0 is universal: the intersection of a prefix is that of its non-universal sets, or non-empty
-// when it has none, and it is empty from step max over words of (first step whose running AND of that word is 0).
+// lane re-walks the T valid steps once per 64-bit word: no W-word accumulator; first_empty_step, query_device.hpp), and an
+// error at step T counts only when E >= T.
 __global__ void __launch_bounds__(256) k_pat_check(CheckArgs a)
 {
     for (u64 q = blockIdx.x * (u64)blockDim.x + threadIdx.x; q < a.nq; q += (u64)gridDim.x * blockDim.x) {
@@ -176,23 +175,13 @@ __global__ void __launch_bounds__(256) k_pat_check(CheckArgs a)
             got += take;
         }
         if (a.bits) {
-            u64 E = NONE;                                          // first step after which the intersection is empty
-            for (u32 w = 0; w < a.W; w++) {
-                u64 acc = ~0ull, z = NONE, d = 0;
-                bool seen = false;
-                for (u64 t = 0; t < T; t++) {
-                    const u64 sym = s + t;
-                    u64 sid = a.ent_off[sym];
-                    if (a.size[sym] > 1) sid += (u64)ch[d++] - a.cd[sym];
-                    const u64* b = a.bits + sid * a.W;
-                    if (b[0] & 1) continue;                        // universal
-                    seen = true;
-                    acc &= b[w];
-                    if (acc == 0) { z = t; break; }
-                }
-                if (!seen || z == NONE) { E = NONE; break; }       // this word keeps a path: never empty
-                E = (w == 0 || z > E) ? z : E;
-            }
+            // first step after which the intersection is empty
+            const u64 E = first_empty_step(a.bits, a.W, T, [&](u64 t, u64& d) {
+                const u64 sym = s + t;
+                u64 sid = a.ent_off[sym];
+                if (a.size[sym] > 1) sid += (u64)ch[d++] - a.cd[sym];
+                return sid;
+            });
             if (E != NONE && E < T) { a.status[q] = 0; continue; }
         }
         if (err) { a.status[q] = (int8_t)err; continue; }

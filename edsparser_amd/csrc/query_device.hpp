@@ -14,6 +14,33 @@ struct QueryInfo {
     double tokenise_ms = 0, tables_ms = 0, kernel_ms = 0, download_ms = 0;
 };
 
+// The source rule of EDS::check_position (calculate_path_intersection, eds.cpp:1300-1418) over the strings of T walk
+// steps: the first step after which their path sets (W words per string, bit 0 = universal) have an empty intersection,
+// Q_NONE when they keep a path.  sid_at(t, d) names the string of step t; d counts the choices it has consumed and starts
+// at 0 for every word: the steps are re-walked once per 64-bit word, so no W-word accumulator is kept.  A universal set
+// drops out: the intersection of a prefix is that of its other sets, or non-empty when it has none, and it is empty from
+// step max over words of (first step whose running AND of that word is 0).  Shared by k_pat_check and the locate kernels.
+constexpr u64 Q_NONE = ~0ull;
+template <class SidAt>
+__device__ __forceinline__ u64 first_empty_step(const u64* __restrict__ bits, u32 W, u64 T, SidAt sid_at)
+{
+    u64 E = Q_NONE;
+    for (u32 w = 0; w < W; w++) {
+        u64 acc = ~0ull, z = Q_NONE, d = 0;
+        bool seen = false;
+        for (u64 t = 0; t < T; t++) {
+            const u64* b = bits + sid_at(t, d) * W;
+            if (b[0] & 1) continue;                            // universal
+            seen = true;
+            acc &= b[w];
+            if (acc == 0) { z = t; break; }
+        }
+        if (!seen || z == Q_NONE) return Q_NONE;               // this word keeps a path: never empty
+        E = (w == 0 || z > E) ? z : E;
+    }
+    return E;
+}
+
 class QueryPipeline {
 public:
     // count patterns of pattern_length characters, each followed by '\n' (count * (pattern_length + 1) bytes).
@@ -31,6 +58,7 @@ public:
     static constexpr u64 CHUNK_BYTES = 256ull << 20;         // ... and at most this much text per launch
 
 private:
+    friend class LocatePipeline;             // the locate kernels read the same tables (locate_device.hip)
     u64 tables(MergePipeline& mp, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, hipStream_t st);
     u64 n_ = 0, m_ = 0, C_ = 0, D_ = 0;
     u32 W_ = 0;

@@ -277,7 +277,40 @@ int edsx_eds_genpatterns(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uin
 int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                              size_t n, const uint64_t* common_pos, const uint64_t* choice_off, const int32_t* choices,
                              const uint64_t* pattern_off, const uint8_t* patterns, int8_t* status_out);
-/* Of the last edsx_eds_genpatterns / edsx_eds_check_positions on this context: the EDS's counts and where the time
+/* ---- pattern search: every occurrence of every pattern ----
+ * n patterns as CSR (pattern_off[n + 1], patterns); the .eds (+ .seds) as for edsx_eds_check_positions.  An occurrence of
+ * a pattern P of L >= 1 bytes is (string g, offset o, choices d_1..d_k): g is a string of symbol `symbol` (its index
+ * there is `string`, in file order, the order the .seds uses) and o < |g|, so an occurrence begins on a character.  The
+ * walk takes g[o:], then, while fewer than L characters are taken and symbols remain, the only string of a common symbol
+ * or the string the next choice names of a degenerate one (a degenerate string number, cum_deg[symbol] + index, as in
+ * check_position), each cut to what is still needed.  It spells P with exactly L characters; k is exactly the number of
+ * degenerate symbols visited after g's, and a symbol after the last character is not visited.  With sources the strings
+ * used, g included, must share a path by check_position's rule (bit 0 / {0} is universal).  So for a start in a common
+ * symbol, (common_pos, choices) is an occurrence exactly when check_position(common_pos, choices, P) is true and no
+ * choice is left over.  Bytes are compared raw: a pattern with '{', '}', ',' or white space never matches.
+ * Order: by pattern; within a pattern ascending by (symbol, string, offset), then by choices in lexicographic order
+ * (depth-first over the alternatives in file order).
+ * Caps, reported in pattern_flags[q]:
+ *   bit 0  hits were left out: the first min(found, max_hits) in the order above are returned; a single start stops
+ *          enumerating at max_hits of its own.  totals[q] sums min(occurrences of the start, max_hits) over the starts:
+ *          the exact number of occurrences when the flags are 0, a lower bound otherwise.  max_hits above 2^32 acts as 2^32.
+ *   bit 1  a walk was cut where it needed choice number EDSX_LOCATE_MAX_CHOICES + 1: whatever lies beyond is neither
+ *          reported nor counted.
+ * n = 0: empty buffers, hit_off = [0].  An empty EDS has no hits.  An empty pattern, a pattern_off that decreases and
+ * max_hits = 0 are EDSX_ERR_INVALID_PARAMETER (the text names the pattern); parse errors as for edsx_leds_merge. */
+typedef struct { uint64_t common_pos;   /* UINT64_MAX: the start is inside a degenerate symbol */
+                 uint64_t symbol, string, offset; } edsx_locate_hit;
+#define EDSX_LOCATE_COMMON_ONLY 1u      /* report only starts in common symbols (check_position's domain) */
+#define EDSX_LOCATE_MAX_CHOICES 64
+int edsx_eds_locate(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                    size_t n, const uint64_t* pattern_off, const uint8_t* patterns, uint64_t max_hits, uint32_t flags,
+                    edsx_buf* hit_off,      /* uint64, n + 1 */
+                    edsx_buf* hits,         /* edsx_locate_hit, hit_off[n] */
+                    edsx_buf* choice_off,   /* uint64, hit_off[n] + 1 */
+                    edsx_buf* choices,      /* int32 */
+                    edsx_buf* totals,       /* uint64, n */
+                    edsx_buf* pattern_flags /* uint8, n */);
+/* Of the last edsx_eds_genpatterns / edsx_eds_check_positions / edsx_eds_locate on this context: the EDS's counts and where the time
  * went (tokenise: host clock around the upload and tokeniser; tables / kernels: device events; download: host clock). */
 typedef struct {
     uint64_t n_symbols, n_strings, n_chars, num_common_chars, num_degenerate_strings;
