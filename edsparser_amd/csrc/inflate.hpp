@@ -199,13 +199,21 @@ EDSX_HD void read_dynamic_lengths(BitReader& br, BlockHeader& h, ClenTable& ct, 
     if (lens[256] == 0) { br.err = INF_E_STREAM; return; }                      // no end-of-block code
     h.nlen = nlen; h.ndist = ndist;
 }
-// validity of a block's two codes as prepared: an incomplete code is accepted only when it has a single symbol
+// validity of a block's two codes as prepared, by zlib's rule: an over-subscribed code is refused; an incomplete code is
+// accepted only when it has exactly one symbol, of length 1, or - the distance code alone - no symbol at all (RFC 1951
+// 3.2.7: a block of literals only; a length symbol met in such a block has no distance code to read and ends the stream
+// in next_token).  read_dynamic_lengths has seen to the end-of-block code.
+template <class H> EDSX_HD bool code_acceptable(int left, const H& h, u32 n, bool may_be_empty)
+{
+    if (left < 0) return false;
+    if (left == 0) return true;
+    const u32 used = n - h.count[0];
+    return (used == 0 && may_be_empty) || (used == 1 && h.count[1] == 1);
+}
 EDSX_HD bool codes_acceptable(int lit_left, int dist_left, const LitTable& lit, const DistTable& dist, u32 nlen, u32 ndist, bool fixed)
 {
     if (fixed) return true;
-    if (lit_left < 0 || (lit_left > 0 && nlen - lit.count[0] != 1)) return false;
-    if (dist_left < 0 || (dist_left > 0 && ndist - dist.count[0] != 1)) return false;
-    return true;
+    return code_acceptable(lit_left, lit, nlen, false) && code_acceptable(dist_left, dist, ndist, true);
 }
 
 // ---- the symbol step ---------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import bgzf_spec as bz
+import deflate_spec as ds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "edsparser_amd", "host")
@@ -46,6 +47,46 @@ def test_host_decoder_under_sanitizers(tmp_path):
     for at, bit in pos[:200]:
         with pytest.raises(Exception):
             gzip.decompress(bz.flipped(data, at, bit))
+
+
+def test_deflate_spec_corpus_has_the_streams_zlib_never_writes():
+    """The generator's own counters (kept from its token lists, no decoder involved) over the corpus both suites use."""
+    cases, cnt = ds.random_corpus()
+    print("random corpus:", cnt)
+    assert cnt["drops"] * 50 <= cnt["seeds"] and len(cases) == cnt["seeds"] - cnt["drops"]
+    assert cnt["far"] >= 100 and cnt["at_window"] >= 50 and cnt["batch_edge"] >= 200 and cnt["max_distance"] == 32768
+    assert cnt["blocks_no_dist"] >= 1 and cnt["blocks_one_dist"] >= 1 and cnt["cross17"] >= 1 and cnt["cross18"] >= 1
+    assert cnt["len258"] >= 1 and cnt["overlap"] >= 1
+    names = [c[0] for c in ds.accepted_cases()] + [c[0] for c in ds.refused()]
+    assert len(set(names)) == len(names)
+    for d in ds.FAR_DISTANCES:
+        assert sum(1 for n in names if n.startswith("far/d%d_" % d)) == len(ds.FAR_LENGTHS) * len(ds.FAR_LEADS)
+    # every member size starts at every residue of the output offset mod 16
+    starts = {}
+    for _, table, members in ds.bgzf_files(ds.sized(), 48):
+        for (name, text), (_, out_off, _, isize) in zip(members, table):
+            if not name.endswith(("_lead", "_trail")):
+                assert isize == len(text)
+                starts.setdefault(isize, set()).add(out_off % 16)
+    assert starts == {n: set(range(16)) for n in ds.SIZES}
+    for _, _, raw, text in ds.accepted_cases():
+        assert len(text) <= 65536 and len(raw) + 26 <= 65536
+
+
+def test_host_decoder_on_streams_zlib_never_writes(tmp_path):
+    """The directed, random and refused corpora of tests/deflate_spec.py (reference: zlib) through the sanitized host
+    build of the decoder core; the raw streams also as plain gzip members, one of them above 64 KiB (the host path's
+    unbounded branch).  Accepted: the text is zlib's.  Refused: block 1, with the reason the fault calls for."""
+    code, refusals, log = ds.host_run(ROOT, str(tmp_path))
+    failed = re.findall(r"^FAIL (.+)$", log, re.M)
+    assert code == 0 and not failed, "%d failures: %s" % (len(failed), failed[:40])
+    n = len(ds.accepted_cases()) + len(ds.gzip_cases()) + len(ds.refused())
+    assert re.search(r"^%d cases, 0 failures$" % n, log, re.M), log[-2000:]
+    want = {name: reason for name, _, reason in ds.refused_files()}
+    assert sorted(refusals) == sorted(want)
+    for name, text in refusals.items():
+        m = re.fullmatch(r"Compressed input: block 1 at byte (\d+): (.+)", text)
+        assert m and m.group(2) == want[name] and m.group(2) in bz.REASONS, (name, text)
 
 
 def test_block_index_and_probe_equal_the_spec():

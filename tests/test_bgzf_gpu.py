@@ -4,11 +4,13 @@ calls on the inflated texts: texts, counters and error text."""
 import gzip
 import os
 import subprocess
+import time
 import zlib
 
 import pytest
 
 import bgzf_spec as bz
+import deflate_spec as ds
 import contig_spec as cs
 from conftest import GOLDEN
 
@@ -70,6 +72,90 @@ def test_corrupted_streams_are_refused_as_the_host_decoder_refuses_them(ctx, tmp
         assert ex.value.code == 2 and ex.value.message == want[name], name
         on_device += edsparser_amd.gz_probe(bad) == 1
     assert on_device >= 3000                                            # the bit flips leave the file BGZF: the device decides
+
+
+# ---- 1b. streams zlib never writes (tests/deflate_spec.py; the reference is zlib) ---------------------------------------
+def test_streams_zlib_never_writes_inflate_to_zlibs_text(ctx):
+    """Directed, sized and random members, about 64 to a BGZF file, one call per file; compared member by member through
+    the block table so that a failure names the case or the seed."""
+    t0 = time.time()
+    files = ds.accepted_files()
+    cnt = ds.random_corpus()[1]
+    t1 = time.time()
+    members, bad = 0, []
+    for data, table, names in files:
+        out = ctx.gz_inflate(data)
+        info = ctx.gz_last_info(0)
+        assert info["kind"] == 1 and info["inflated_on_device"] == 1 and info["blocks"] == len(table), (names[0][0], info)
+        assert info["text_bytes"] == len(out) == table[-1][1], (names[0][0], info)
+        for (name, text), (_, off, _, isize) in zip(names, table):
+            members += 1
+            if out[off:off + isize] != text:
+                first = next((i for i in range(min(isize, len(text))) if out[off + i] != text[i]), None)
+                bad.append((name, isize, first))
+    print("deflate_spec on the device: %d files, %d members, generated in %.1f s, inflated and compared in %.1f s; random corpus %s"
+          % (len(files), members, t1 - t0, time.time() - t1, cnt))
+    assert not bad, "%d members differ from zlib's text (name, size, first differing byte): %s" % (len(bad), bad[:20])
+    assert members == len(ds.accepted_cases())
+
+
+def test_streams_gzip_refuses_are_refused_as_the_host_decoder_refuses_them(ctx, tmp_path):
+    """One fault per file, between two valid members; gzip.decompress raises on every faulty member (deflate_spec.refused
+    asserts it).  The device gives the host decoder's status and text, and names block 1; each case runs once."""
+    import edsparser_amd
+    t0 = time.time()
+    code, want, log = ds.host_run(ROOT, str(tmp_path), with_accepted=False)
+    assert code == 0, log[-4000:]
+    cases = ds.refused_files()
+    assert sorted(want) == sorted(name for name, _, _ in cases)
+    t1 = time.time()
+    for name, bad, reason in cases:
+        assert edsparser_amd.gz_probe(bad) == 1, name                       # BGZF: the device decides
+        with pytest.raises(edsparser_amd.EdsxError) as ex:
+            ctx.gz_inflate(bad)
+        assert ex.value.code == 2 and ex.value.message == want[name], (name, ex.value.message, want[name])
+        assert ex.value.message.startswith("Compressed input: block 1 at byte ") and ex.value.message.endswith(": " + reason), name
+    print("refused streams: %d cases, host decoder %.1f s, device %.1f s" % (len(cases), t1 - t0, time.time() - t1))
+
+
+def test_far_match_streams_through_the_compressed_transform(ctx):
+    """A fixture's VCF and FASTA as one BGZF member each whose matches all reach back 32 507 bytes or more: the records
+    stand 32 640 bytes in front of themselves as meta lines, the sequence is followed by unrelated lines and then by itself
+    at that distance.  The compressed call must equal the plain one."""
+    import random
+    c = max(cs.load_fixtures(GOLDEN), key=lambda x: len(x["vcf"]) if "error" not in x["expect"] else 0)
+    v, f = c["vcf"].encode(), c["fasta"].encode()
+    rng, back = random.Random(5), 32640
+
+    def lines(n, prefix, alphabet, width=60):
+        """exactly n bytes of lines"""
+        out = b""
+        while len(out) < n:
+            out += prefix + bytes(rng.choice(alphabet) for _ in range(width)) + b"\n"
+        return out[:n - 1] + b"\n"
+
+    records = [ln for ln in v.split(b"\n") if ln and not ln.startswith(b"#")]
+    first = v.index(records[0])
+    meta = b"".join(b"##" + ln[2:] + b"\n" for ln in records)            # as long as the record lines
+    V = meta + lines(back - len(meta) - first, b"##pad=", b"ACGTacgt0123456789|") + v
+    head, seq = f.rstrip(b"\n").split(b"\n", 1)
+    F = head + b"\n" + seq + b"\n" + lines(back - len(seq) - 1, b"", b"ACGT", len(seq.split(b"\n")[0])) + seq + b"\n"
+    files = []
+    for text in (V, F):
+        assert len(text) <= 65536
+        toks = ds.far_lz77(text)
+        far = [t for t in toks if not isinstance(t, int)]
+        assert len(far) >= 5 and min(t[1] for t in far) > ds.FAR and sum(t[0] for t in far) >= 300, (len(far), len(text))
+        blocks = [("dynamic", toks, ds.auto_codes(toks))]
+        raw = ds.assemble(blocks)
+        assert zlib.decompress(raw, -15) == text == ds.expand(blocks)
+        files.append(ds.wrap(raw, text) + bz.EOF_BLOCK)
+    plain = _res(lambda: ctx.vcf_transform(V, F, c["l"]))
+    assert "error" not in plain, plain
+    assert _res(lambda: ctx.vcf_transform(files[0], files[1], c["l"], compressed=True)) == plain
+    for which, text in ((0, V), (1, F)):
+        info = ctx.gz_last_info(which)
+        assert info["kind"] == 1 and info["inflated_on_device"] == 1 and info["blocks"] == 2 and info["text_bytes"] == len(text), info
 
 
 # ---- 2. the fixtures through the compressed calls ----------------------------------------------------------------------
