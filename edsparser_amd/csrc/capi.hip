@@ -39,7 +39,9 @@ struct edsx_ctx {
     int device = 0;
     std::string err;
     MsaPipeline msa;
+    DeviceEds eds;                           // the tokenised .eds (+ .seds) of the last merge / stats / query / locate call
     MergePipeline merge;
+    DevBuf stats_acc;                        // edsx_eds_stats
     RangeScanner scan;                       // edsx_eds_scan_range / edsx_seds_scan_range
     QueryPipeline query;                     // edsx_eds_genpatterns / edsx_eds_check_positions
     LocatePipeline locate;                   // edsx_eds_locate, over query's tables
@@ -146,7 +148,7 @@ void vcf_result(Run&& run, Merge&& merge, uint32_t context_len, edsx_buf* eds, e
 void merge_in_place(edsx_ctx* ctx, HostBytes& e, HostBytes& s, uint32_t context_len)
 {
     HostBytes lo, so;
-    ctx->merge.run(e.data, e.size, s.data, s.size, context_len, true, lo, so, nullptr);
+    ctx->merge.run(ctx->eds, e.data, e.size, s.data, s.size, context_len, true, lo, so, nullptr);
     std::swap(e.data, lo.data); std::swap(e.size, lo.size);
     std::swap(s.data, so.data); std::swap(s.size, so.size);
 }
@@ -465,7 +467,7 @@ int edsx_leds_merge(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
     return guarded(ctx, [&] {
         if (!leds || !seds_out || (!eds && eds_size)) throw ParamError("null argument");
         HostBytes out, sout;
-        ctx->merge.run(or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr);
+        ctx->merge.run(ctx->eds, or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr);
         give(leds, out);
         give(seds_out, sout);
     });
@@ -478,7 +480,8 @@ int edsx_eds_stats(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uin
     return guarded(ctx, [&] {
         if (!out || (!eds && eds_size)) throw ParamError("null argument");
         EdsStats s{};
-        ctx->merge.stats(or_empty(eds), eds_size, seds, seds_size, context_len, s, nullptr);
+        ctx->eds.load(or_empty(eds), eds_size, seds, seds_size, seds != nullptr, nullptr);
+        eds_stats(ctx->eds, context_len, ctx->stats_acc, s, nullptr);
         out->n_symbols = s.n_symbols; out->n_chars = s.n_chars; out->n_strings = s.n_strings;
         out->num_degenerate_symbols = s.num_degenerate; out->total_change_size = s.total_change_size;
         out->num_common_chars = s.num_common_chars; out->num_empty_strings = s.num_empty_strings;
@@ -492,7 +495,7 @@ int edsx_eds_stats(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uin
     });
 }
 
-int edsx_leds_tokenised_on_device(const edsx_ctx* ctx) { return ctx && ctx->merge.tokenised_on_device() ? 1 : 0; }
+int edsx_leds_tokenised_on_device(const edsx_ctx* ctx) { return ctx && ctx->eds.tokenised_on_device() ? 1 : 0; }
 
 int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                           uint32_t context_len, int compact, int head_sentinel, int tail_sentinel, edsx_buf* leds,
@@ -506,7 +509,7 @@ int edsx_leds_merge_range(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
         HostBytes out, sout;
         MergeShard sh;
         sh.head_sentinel = head_sentinel != 0; sh.tail_sentinel = tail_sentinel != 0;
-        ctx->merge.run(or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr, &sh);
+        ctx->merge.run(ctx->eds, or_empty(eds), eds_size, seds, seds_size, context_len, compact != 0, out, sout, nullptr, &sh);
         *head_intact = sh.head_intact ? 1 : 0;
         *tail_intact = sh.tail_intact ? 1 : 0;
         give(leds, out);
@@ -524,7 +527,7 @@ int edsx_eds_genpatterns(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uin
         HostBytes out;
         std::vector<u64> wpos, woff;
         std::vector<int32_t> wdeg;
-        ctx->query.genpatterns(ctx->merge, or_empty(eds), eds_size, count, pattern_length, seed, out, nw ? &wpos : nullptr,
+        ctx->query.genpatterns(ctx->eds, or_empty(eds), eds_size, count, pattern_length, seed, out, nw ? &wpos : nullptr,
                                nw ? &woff : nullptr, nw ? &wdeg : nullptr, nullptr);
         if (nw) {
             take_copy(witness_pos, wpos.data(), 8 * wpos.size());
@@ -544,7 +547,7 @@ int edsx_eds_check_positions(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size,
             (n && choice_off[n] && !choices) || (n && pattern_off[n] && !patterns))
             throw ParamError("null argument");
         static_assert(sizeof(u64) == sizeof(uint64_t), "u64");
-        ctx->query.check(ctx->merge, or_empty(eds), eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
+        ctx->query.check(ctx->eds, or_empty(eds), eds_size, seds, seds_size, n, reinterpret_cast<const u64*>(common_pos),
                          reinterpret_cast<const u64*>(choice_off), choices, reinterpret_cast<const u64*>(pattern_off), patterns,
                          status_out, nullptr);
     });
@@ -565,7 +568,7 @@ int edsx_eds_locate(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
                       "edsx_locate_hit is LocateHit");
         const u64 none = 0;
         LocateOut o;
-        ctx->locate.run(ctx->query, ctx->merge, or_empty(eds), eds_size, seds, seds_size, n,
+        ctx->locate.run(ctx->query, ctx->eds, or_empty(eds), eds_size, seds, seds_size, n,
                         n ? reinterpret_cast<const u64*>(pattern_off) : &none, patterns, max_hits,
                         (flags & EDSX_LOCATE_COMMON_ONLY) != 0, o, nullptr);
         take_copy(hit_off, o.hit_off.data(), 8 * o.hit_off.size());

@@ -7,6 +7,7 @@
 #include "draw.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
@@ -110,6 +111,23 @@ inline bool device_scratch_fits(size_t bytes)
     return bytes <= free_b / 2;
 }
 
+// ---- host-side launch helpers ----------------------------------------------------------------------------
+inline double since_ms(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// two device events around a stretch of a stream; ms() after the stream has been synchronised
+struct EventPair {
+    hipEvent_t a, b;
+    EventPair() { EDSX_HIP(hipEventCreate(&a)); EDSX_HIP(hipEventCreate(&b)); }
+    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    float ms() const { float v = 0; EDSX_HIP(hipEventElapsedTime(&v, a, b)); return v; }
+};
+
+// blocks of 256 threads for a grid-stride kernel over `work` items, at most `cap`
+inline unsigned grid_for(u64 work, u64 cap) { return (unsigned)std::max<u64>(1, std::min<u64>((work + 255) / 256, cap)); }
+
 // ---- wave64 primitives -------------------------------------------------------------------
 __device__ __forceinline__ u32 lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 // number of set bits of `mask` strictly below this lane
@@ -174,7 +192,7 @@ __device__ __forceinline__ u32 ndigits(u32 v)
 // ---- device-wide scans on u64 arrays, element count read from device memory -----------------
 // OP 0: exclusive sum (out[i] = sum(in[0..i)), *total = sum of all)
 // OP 1: inclusive max (out[i] = max(in[0..i]),  *total = max of all)
-// in/out may alias.  Three grid-stride kernels; tmp holds one u64 per SCAN_TILE elements.
+// in/out may alias (they are not __restrict__: callers scan in place).  Three grid-stride kernels; tmp holds one u64 per SCAN_TILE elements.
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;   // 2048
@@ -195,7 +213,7 @@ __device__ __forceinline__ u64 block_reduce(u64 v, u64* sh /*[SCAN_THREADS/64]*/
 }
 
 template <int OP>
-static __global__ void k_scan_tile_sums(const u64* __restrict__ in, const u64* __restrict__ n_ptr,
+static __global__ void k_scan_tile_sums(const u64* in, const u64* __restrict__ n_ptr,
                                         u64* __restrict__ bsum)
 {
     __shared__ u64 sh[SCAN_THREADS / 64];
@@ -247,7 +265,7 @@ static __global__ void k_scan_spine(u64* __restrict__ bsum, const u64* __restric
 }
 
 template <int OP>
-static __global__ void k_scan_apply(const u64* __restrict__ in, u64* __restrict__ out,
+static __global__ void k_scan_apply(const u64* in, u64* out,
                                     const u64* __restrict__ n_ptr, const u64* __restrict__ bsum)
 {
     __shared__ u64 wsum[SCAN_THREADS / 64];

@@ -258,41 +258,29 @@ __global__ void k_loc_kept(const u64* __restrict__ scanned, u64 ntiles, u64 np, 
     }
 }
 
-double since_ms(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-struct EventPair {
-    hipEvent_t a, b;
-    EventPair() { EDSX_HIP(hipEventCreate(&a)); EDSX_HIP(hipEventCreate(&b)); }
-    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    float ms() const { float v = 0; EDSX_HIP(hipEventElapsedTime(&v, a, b)); return v; }
-};
-
-unsigned grid_for(u64 work) { return (unsigned)std::max<u64>(1, std::min<u64>((work + 255) / 256, 4096)); }
-
 } // namespace
 
-void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n,
+void LocatePipeline::run(QueryPipeline& qp, DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n,
                          size_t n, const u64* pattern_off, const uint8_t* patterns, u64 max_hits, bool common_only, LocateOut& out,
                          hipStream_t st)
 {
-    qp.info_ = QueryInfo{};
+    QueryInfo& info = qp.info();
+    info = QueryInfo{};
     if (max_hits == 0) throw ParamError("max_hits must be at least 1");
     for (size_t q = 0; q < n; q++) {
         if (pattern_off[q + 1] < pattern_off[q]) throw ParamError("pattern_off decreases at pattern " + std::to_string(q));
         if (pattern_off[q + 1] == pattern_off[q]) throw ParamError("Pattern " + std::to_string(q) + " is empty");
     }
     max_hits = std::min(max_hits, MAX_HITS_CEILING);
-    const u64 ns = qp.tables(mp, eds, eds_n, seds, seds_n, st);
+    const u64 ns = qp.tables(de, eds, eds_n, seds, seds_n, st);
     out = LocateOut{};
     out.hit_off.assign(n + 1, 0);
     out.choice_off.assign(1, 0);
     out.totals.assign(n, 0);
     out.flags.assign(n, 0);
-    const u64 N = qp.info_.n_chars, m = qp.m_;
+    const u64 N = de.n_chars(), m = de.m();
     if (n == 0 || ns == 0 || N == 0) return;                   // an empty EDS, or one without a character: no hits
+    const EdsView v = de.view();
 
     const u64 ntiles = (N + LTILE - 1) / LTILE;
     str_sym_.ensure(8 * m);
@@ -300,19 +288,18 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
     u64* ctl = ctl_.as<u64>();                                  // scan lengths: [0] counters  [1] patterns  [2] hits
     EventPair ev;
     EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_loc_str_sym, dim3(grid_for(ns)), dim3(256), 0, st, mp.size_[0].as<u64>(), mp.ent_off_[0].as<u64>(), ns,
+    hipLaunchKernelGGL(k_loc_str_sym, dim3(grid_for(ns, 4096)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, ns,
                        str_sym_.as<u64>());
     EDSX_HIP(hipEventRecord(ev.b, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    qp.info_.tables_ms += ev.ms();
+    info.tables_ms += ev.ms();
 
     // patterns per launch: whole chunks, within the counter budget
     const u64 group = std::max<u64>(LCHUNK, COUNT_ENTRIES / ntiles / LCHUNK * LCHUNK);
     LocArgs a{};
-    a.size = mp.size_[0].as<u64>(); a.ent_off = mp.ent_off_[0].as<u64>(); a.str_off = mp.d_str_off_.as<u64>();
-    a.chars = mp.d_chars_.as<uint8_t>(); a.bits = qp.W_ ? mp.bits_.as<u64>() : nullptr; a.W = qp.W_;
-    a.cc = qp.cum_common_.as<u64>(); a.cd = qp.cum_deg_.as<u64>(); a.str_sym = str_sym_.as<u64>();
+    a.size = v.sym.size; a.ent_off = v.sym.ent_off; a.str_off = v.str_off; a.chars = v.chars; a.bits = v.bits; a.W = v.W;
+    a.cc = qp.cum_common(); a.cd = qp.cum_deg(); a.str_sym = str_sym_.as<u64>();
     a.n = ns; a.m = m; a.N = N; a.max_hits = max_hits; a.common_only = common_only ? 1 : 0; a.ntiles = ntiles;
     std::vector<u64> seed, pmask, poff, hoff, coff;
     std::vector<u32> flg;
@@ -343,7 +330,7 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
         EDSX_HIP(hipEventRecord(ev.a, st));
         hipLaunchKernelGGL(k_locate<M_COUNT>, grid, dim3(LNT), 0, st, a);
         exclusive_scan_u64(a.counts, a.counts, ctl, a.counts + len, scan_tmp_.as<u64>(), st);
-        hipLaunchKernelGGL(k_loc_kept, dim3(grid_for(np)), dim3(256), 0, st, a.counts, ntiles, np, max_hits, totals_.as<u64>(),
+        hipLaunchKernelGGL(k_loc_kept, dim3(grid_for(np, 4096)), dim3(256), 0, st, a.counts, ntiles, np, max_hits, totals_.as<u64>(),
                            kept_.as<u64>(), a.flags);
         exclusive_scan_u64(kept_.as<u64>(), hoff_.as<u64>(), ctl + 1, hoff_.as<u64>() + np, scan_tmp_.as<u64>(), st);
         EDSX_HIP(hipEventRecord(ev.b, st));
@@ -353,7 +340,7 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
         EDSX_HIP(hipMemcpyAsync(flg.data(), flags_.ptr, 4 * np, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        qp.info_.kernel_ms += ev.ms();
+        info.kernel_ms += ev.ms();
         const u64 H = hoff[np], h0 = out.hits.size();
         for (u64 q = 0; q < np; q++) { out.flags[g0 + q] = (uint8_t)flg[q]; out.hit_off[g0 + q + 1] = h0 + hoff[q + 1]; }
         if (H == 0) continue;
@@ -370,7 +357,7 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
         EDSX_HIP(hipMemcpyAsync(&K, coff_.as<u64>() + H, 8, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        qp.info_.kernel_ms += ev.ms();
+        info.kernel_ms += ev.ms();
         if (K) {
             choices_.ensure(4 * K);
             a.choices = choices_.as<int32_t>();
@@ -379,7 +366,7 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
             EDSX_HIP(hipEventRecord(ev.b, st));
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
-            qp.info_.kernel_ms += ev.ms();
+            info.kernel_ms += ev.ms();
         }
         const auto t0 = std::chrono::steady_clock::now();
         const u64 k0 = out.choices.size();
@@ -391,7 +378,7 @@ void LocatePipeline::run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* ed
         if (K) EDSX_HIP(hipMemcpyAsync(out.choices.data() + k0, choices_.ptr, 4 * K, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         for (u64 h = 1; h <= H; h++) out.choice_off.push_back(k0 + coff[h]);
-        qp.info_.download_ms += since_ms(t0);
+        info.download_ms += since_ms(t0);
     }
 }
 

@@ -27,7 +27,7 @@ public:
     static constexpr u64 COUNT_ENTRIES = 32ull << 20;        // (pattern, tile) counters per launch: 256 MB
 
     // n patterns as CSR.  Counts and times of the call go to qp's QueryInfo (edsx_query_last_info).
-    void run(QueryPipeline& qp, MergePipeline& mp, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n,
+    void run(QueryPipeline& qp, DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n,
              size_t n, const u64* pattern_off, const uint8_t* patterns, u64 max_hits, bool common_only, LocateOut& out,
              hipStream_t st);
 

@@ -133,7 +133,7 @@ void MultiMsa::run_rank_merge(int r, MergeShared& sh)
                         MergeShard shard;
                         shard.head_sentinel = r != 0;
                         shard.tail_sentinel = nxt >= 0;
-                        me.merge->run(sh.eds + e0, e1 - e0, linear ? sh.seds + s0 : nullptr, s1 - s0, sh.l, sh.compact, out, so, st, &shard);
+                        me.merge->run(me.merge_eds, sh.eds + e0, e1 - e0, linear ? sh.seds + s0 : nullptr, s1 - s0, sh.l, sh.compact, out, so, st, &shard);
                         ok = shard.head_intact && shard.tail_intact ? 1 : 0;
                     } catch (const std::exception&) { ok = 0; }
                 })) return;
@@ -174,7 +174,7 @@ void MultiMsa::run_rank_merge(int r, MergeShared& sh)
         sh.seds_h2d[0] += linear ? sh.seds_n : 0;
         EDSX_HIP(hipSetDevice(me.device));
         if (!me.merge) me.merge.reset(new MergePipeline());
-        me.merge->run(sh.eds, sh.eds_n, sh.seds, sh.seds_n, sh.l, sh.compact, *sh.leds, *sh.sout, st);
+        me.merge->run(me.merge_eds, sh.eds, sh.eds_n, sh.seds, sh.seds_n, sh.l, sh.compact, *sh.leds, *sh.sout, st);
     });
 }
 

@@ -140,6 +140,7 @@ struct MultiMsa::Rank {
     std::string error;
     std::unique_ptr<VcfPipeline> vcf;    // vcf_transform: created on first use
     std::unique_ptr<MergePipeline> merge;   // (rank 0, context length > 0; every rank in leds_merge_multi)
+    DeviceEds merge_eds;                    // the text that merge works on
     std::unique_ptr<RangeScanner> scan;     // leds_merge_multi: the device scans of this rank's slices
 };
 

@@ -2,8 +2,9 @@
 //
 // The chosen string of path p at symbol i is the first string of the symbol, in file order, whose source set holds p
 // or 0; the sequence of p is the concatenation over the symbols, and a symbol without such a string adds one to
-// missing[p].  The kernels read what MergePipeline::prepare leaves in HBM (per symbol: size, first string,
-// single-string length; per string: str_off into the character pool, its path bitset of W words, bit 0 = universal).
+// missing[p].  The kernels read a DeviceEds of the session's own through its view (eds_device.hpp: per symbol size,
+// first string, single-string length; per string str_off into the character pool, its path bitset of W words, bit 0 =
+// universal).
 //
 //   open      k_path_flags   a symbol is FIXED when its one string is universal: every path takes it, so one shared
 //                            exclusive scan (cum_fixed) gives its share of every path's offsets; all other symbols
@@ -239,20 +240,6 @@ __global__ void __launch_bounds__(CP_THREADS) k_path_copy(CopyArgs a)
     }
 }
 
-double since_ms(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-struct EventPair {
-    hipEvent_t a, b;
-    EventPair() { EDSX_HIP(hipEventCreate(&a)); EDSX_HIP(hipEventCreate(&b)); }
-    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    float ms() const { float v = 0; EDSX_HIP(hipEventElapsedTime(&v, a, b)); return v; }
-};
-
-unsigned grid_for(u64 work) { return (unsigned)std::max<u64>(1, std::min<u64>((work + 255) / 256, 8192)); }
-
 u64 free_hbm()
 {
     size_t free_b = 0, total_b = 0;
@@ -268,49 +255,45 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     info_ = PathInfo{};
     timing_ = PathTiming{};
     const auto t0 = std::chrono::steady_clock::now();
-    MergePipeline::Loaded L;
-    mp_.prepare(eds, eds_n, seds, seds_n, true, st, L);
-    n_ = L.n0; m_ = L.m; W_ = L.W; nc_ = 0; F_ = 0;
-    info_.tokenised_on_device = mp_.tokenised_on_device();
-    // what only the merge rounds and the tokenisers need goes back to the allocator: the session may live long
-    for (DevBuf* b : {&mp_.d_raw_, &mp_.tk_a_, &mp_.tk_b_, &mp_.tk_c_, &mp_.d_sym_first_, &mp_.left_, &mp_.right_, &mp_.elen_,
-                      &mp_.size_[1], &mp_.ent_off_[1], &mp_.len1_[1], &mp_.scan_tmp_})
-        b->release();
+    eds_.load(eds, eds_n, seds, seds_n, true, st);
+    eds_.drop_scratch();                                                      // the session may live long
+    n_ = eds_.n(); nc_ = 0; F_ = 0;
+    info_.tokenised_on_device = eds_.tokenised_on_device();
     if (n_ == 0) { timing_.tokenise_ms = since_ms(t0); return; }              // empty EDS: P = 0
+    const EdsView v = eds_.view();
+    const u32 W = v.W;
     cum_fixed_.ensure(8 * (n_ + 1));
     rank_.ensure(8 * (n_ + 1));
     ctl_.ensure(8 * 8);
     scan_tmp_.ensure(8 * 2 * (n_ / SCAN_TILE + 4));
-    tot_.ensure(8 * (size_t)W_);
+    tot_.ensure(8 * (size_t)W);
     u64 hn = n_;
     EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &hn, 8, hipMemcpyHostToDevice, st));
-    EDSX_HIP(hipMemsetAsync(tot_.ptr, 0, 8 * (size_t)W_, st));
+    EDSX_HIP(hipMemsetAsync(tot_.ptr, 0, 8 * (size_t)W, st));
     u64 *cf = cum_fixed_.as<u64>(), *rk = rank_.as<u64>();
-    const u64* bits = mp_.bits_.as<u64>();
-    hipLaunchKernelGGL(k_path_flags, dim3(grid_for(n_)), dim3(256), 0, st, mp_.size_[0].as<u64>(), mp_.ent_off_[0].as<u64>(),
-                       mp_.len1_[0].as<u64>(), bits, W_, n_, cf, rk);
+    hipLaunchKernelGGL(k_path_flags, dim3(grid_for(n_, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.sym.len1, v.bits, W,
+                       n_, cf, rk);
     ScanSet<2> ss{{cf, rk}, {cf, rk}, {cf + n_, rk + n_}};
     exclusive_scan_multi<2>(ss, ctl_.as<u64>(), scan_tmp_.as<u64>(), st);
-    hipLaunchKernelGGL(k_path_or, dim3(1024), dim3(256), 0, st, bits, W_, m_, tot_.as<u64>());
-    u64 h[3] = {0, 0, 0};
-    std::vector<u64> orb(W_, 0);
+    hipLaunchKernelGGL(k_path_or, dim3(1024), dim3(256), 0, st, v.bits, W, v.m, tot_.as<u64>());
+    u64 h[2] = {0, 0};
+    std::vector<u64> orb(W, 0);
     EDSX_HIP(hipMemcpyAsync(&h[0], cf + n_, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipMemcpyAsync(&h[1], rk + n_, 8, hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipMemcpyAsync(&h[2], mp_.d_str_off_.as<u64>() + m_, 8, hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipMemcpyAsync(orb.data(), tot_.ptr, 8 * (size_t)W_, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(orb.data(), tot_.ptr, 8 * (size_t)W, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
     F_ = h[0]; nc_ = h[1];
     if (nc_) {
         cidx_.ensure(8 * nc_);
-        hipLaunchKernelGGL(k_path_cidx, dim3(grid_for(n_)), dim3(256), 0, st, rk, n_, cidx_.as<u64>());
+        hipLaunchKernelGGL(k_path_cidx, dim3(grid_for(n_, 8192)), dim3(256), 0, st, rk, n_, cidx_.as<u64>());
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
     }
     u64 P = 0;
-    for (u32 w = 0; w < W_; w++)
+    for (u32 w = 0; w < W; w++)
         if (orb[w]) P = 64ull * w + 63 - (u64)__builtin_clzll(orb[w]);
-    info_.n_symbols = n_; info_.n_strings = m_; info_.n_chars = h[2]; info_.num_paths = P; info_.n_choice_symbols = nc_;
+    info_.n_symbols = n_; info_.n_strings = v.m; info_.n_chars = v.n_chars; info_.num_paths = P; info_.n_choice_symbols = nc_;
     timing_.tokenise_ms = since_ms(t0);
 }
 
@@ -350,9 +333,9 @@ void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vec
         ctl_.ensure(8 * 8);
         EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &cells, 8, hipMemcpyHostToDevice, st));
         EDSX_HIP(hipEventRecord(ec.a, st));
-        hipLaunchKernelGGL(k_path_choose, dim3(grid_for(cells)), dim3(256), 0, st, mp_.size_[0].as<u64>(), mp_.ent_off_[0].as<u64>(),
-                           mp_.d_str_off_.as<u64>(), mp_.bits_.as<u64>(), W_, cidx_.as<u64>(), nc_, ids_.as<u64>(), K,
-                           csid_.as<u64>(), clen_.as<u64>(), miss_.as<u64>());
+        const EdsView v = eds_.view();
+        hipLaunchKernelGGL(k_path_choose, dim3(grid_for(cells, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, v.bits,
+                           v.W, cidx_.as<u64>(), nc_, ids_.as<u64>(), K, csid_.as<u64>(), clen_.as<u64>(), miss_.as<u64>());
         EDSX_HIP(hipEventRecord(ec.b, st));
         EDSX_HIP(hipEventRecord(es.a, st));
         exclusive_scan_u64(clen_.as<u64>(), clen_.as<u64>(), ctl_.as<u64>(), clen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
@@ -446,8 +429,8 @@ void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, con
             out_.ensure(bytes + 16);                             // 16 bytes of slack behind the text, as every output buffer here
             rec_.ensure(sizeof(PathRec) * nrec);
             EDSX_HIP(hipMemcpyAsync(rec_.ptr, rec.data() + r0, sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
-            CopyArgs a{mp_.ent_off_[0].as<u64>(), mp_.d_str_off_.as<u64>(), mp_.d_chars_.as<uint8_t>(), cum_fixed_.as<u64>(),
-                       rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, nc_ ? clen_.as<u64>() : nullptr, n_, nc_,
+            const EdsView v = eds_.view();
+            CopyArgs a{v.sym.ent_off, v.str_off, v.chars, cum_fixed_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, nc_ ? clen_.as<u64>() : nullptr, n_, nc_,
                        rec_.as<PathRec>(), nrec, (max_body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>()};
             EventPair ev;
             EDSX_HIP(hipEventRecord(ev.a, st));

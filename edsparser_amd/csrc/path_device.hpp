@@ -2,7 +2,7 @@
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
 #pragma once
 
-#include "merge_device.hpp"
+#include "eds_device.hpp"
 
 #include <vector>
 
@@ -24,7 +24,7 @@ struct PathTiming {
 // its row of the choice tables
 struct PathRec { u64 rec_off, body_off, hdr_src, L, lw, body, row; };
 
-// One EDS + sEDS kept tokenised in HBM by a MergePipeline of its own (other calls on the context do not touch it).
+// One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
 public:
     // Tokenises as edsx_leds_merge does in LINEAR mode (same statuses and texts); seds == nullptr: ParamError.
@@ -46,11 +46,10 @@ private:
     // choose + scan for ids[0..K): device tables for the copy kernel, host lengths and missing counts
     void tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st);
 
-    MergePipeline mp_;
+    DeviceEds eds_;
     PathInfo info_;
     PathTiming timing_;
-    u64 n_ = 0, m_ = 0, nc_ = 0, F_ = 0;
-    u32 W_ = 0;
+    u64 n_ = 0, nc_ = 0, F_ = 0;
     DevBuf cum_fixed_, rank_, cidx_, ctl_, scan_tmp_, ids_, csid_, clen_, tot_, miss_, rec_, hdr_, hoff_, out_;
 };
 

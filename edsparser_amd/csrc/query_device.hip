@@ -3,8 +3,8 @@
 // Replaces the reference's one-pattern-at-a-time loops (src/cpp/lib/formats/eds.cpp):
 //   generate_patterns :673-769                      -> k_pat_sample, one lane per pattern
 //   check_position :953-1047 + helpers :1051-1418   -> k_pat_check, one lane per query
-// Both read the tokenised arrays MergePipeline::prepare leaves in HBM (per symbol: size, first string, single-string
-// length; per string: str_off into the character pool; with sources: the path bitsets, W words, bit 0 = universal)
+// Both read a loaded DeviceEds through its view (eds_device.hpp: per symbol size, first string, single-string length;
+// per string str_off into the character pool; with sources the path bitsets, W words, bit 0 = universal)
 // plus two exclusive scans built here:
 //   cum_common[i]  common characters in front of symbol i (n+1 entries; the reference's cum_common_positions)
 //   cum_deg[i]     degenerate strings in front of symbol i (n+1 entries; cum_degenerate_counts)
@@ -189,32 +189,19 @@ __global__ void __launch_bounds__(256) k_pat_check(CheckArgs a)
     }
 }
 
-double since_ms(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-struct EventPair {
-    hipEvent_t a, b;
-    EventPair() { EDSX_HIP(hipEventCreate(&a)); EDSX_HIP(hipEventCreate(&b)); }
-    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    float ms() const { float v = 0; EDSX_HIP(hipEventElapsedTime(&v, a, b)); return v; }
-};
-
-unsigned grid_for(u64 work) { return (unsigned)std::max<u64>(1, std::min<u64>((work + 255) / 256, 4096)); }
-
 } // namespace
 
-// Tokenise (MergePipeline::prepare) and scan the two position tables; returns n.
-u64 QueryPipeline::tables(MergePipeline& mp, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, hipStream_t st)
+// Tokenise (DeviceEds::load) and scan the two position tables; returns n.
+u64 QueryPipeline::tables(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, hipStream_t st)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    MergePipeline::Loaded L;
-    mp.prepare(eds, eds_n, seds, seds_n, seds != nullptr, st, L);
+    de.load(eds, eds_n, seds, seds_n, seds != nullptr, st);
     info_.tokenise_ms = since_ms(t0);
-    n_ = L.n0; m_ = L.m; W_ = seds ? L.W : 0; C_ = D_ = 0;
-    info_.n_symbols = n_; info_.n_strings = m_;
+    n_ = de.n(); C_ = D_ = 0;
+    info_.n_symbols = n_; info_.n_strings = de.m();
     if (n_ == 0) return 0;
+    const EdsView v = de.view();
+    info_.n_chars = v.n_chars;
     cum_common_.ensure(8 * (n_ + 1));
     cum_deg_.ensure(8 * (n_ + 1));
     ctl_.ensure(8 * 8);
@@ -224,28 +211,27 @@ u64 QueryPipeline::tables(MergePipeline& mp, const uint8_t* eds, size_t eds_n, c
     u64 *cc = cum_common_.as<u64>(), *cd = cum_deg_.as<u64>();
     EventPair ev;
     EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_q_flags, dim3(grid_for(n_)), dim3(256), 0, st, mp.size_[0].as<u64>(), mp.len1_[0].as<u64>(), n_, cc, cd);
+    hipLaunchKernelGGL(k_q_flags, dim3(grid_for(n_, 4096)), dim3(256), 0, st, v.sym.size, v.sym.len1, n_, cc, cd);
     ScanSet<2> ss{{cc, cd}, {cc, cd}, {cc + n_, cd + n_}};
     exclusive_scan_multi<2>(ss, ctl_.as<u64>(), scan_tmp_.as<u64>(), st);
     EDSX_HIP(hipEventRecord(ev.b, st));
-    u64 h[3] = {0, 0, 0};
+    u64 h[2] = {0, 0};
     EDSX_HIP(hipMemcpyAsync(&h[0], cc + n_, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipMemcpyAsync(&h[1], cd + n_, 8, hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipMemcpyAsync(&h[2], mp.d_str_off_.as<u64>() + m_, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
     info_.tables_ms = ev.ms();
     C_ = h[0]; D_ = h[1];
-    info_.num_common_chars = C_; info_.num_degenerate_strings = D_; info_.n_chars = h[2];
+    info_.num_common_chars = C_; info_.num_degenerate_strings = D_;
     return n_;
 }
 
-void QueryPipeline::genpatterns(MergePipeline& mp, const uint8_t* eds, size_t eds_n, u64 count, u32 pattern_length, u64 seed,
+void QueryPipeline::genpatterns(DeviceEds& de, const uint8_t* eds, size_t eds_n, u64 count, u32 pattern_length, u64 seed,
                                 HostBytes& out, std::vector<u64>* wpos, std::vector<u64>* woff, std::vector<int32_t>* wdeg,
                                 hipStream_t st)
 {
     info_ = QueryInfo{};
-    const u64 n = tables(mp, eds, eds_n, nullptr, 0, st);
+    const u64 n = tables(de, eds, eds_n, nullptr, 0, st);
     if (n == 0) throw ParamError("Cannot generate patterns from empty EDS");          // eds.cpp:674-680
     if (pattern_length == 0) throw ParamError("Pattern length must be greater than 0");
     const u64 rec = (u64)pattern_length + 1;
@@ -260,8 +246,8 @@ void QueryPipeline::genpatterns(MergePipeline& mp, const uint8_t* eds, size_t ed
     scan_tmp_.ensure(8 * (chunk / SCAN_TILE + 4));
     ctl_.ensure(8 * 8);
     u64* ctl = ctl_.as<u64>();                                  // [0] err  [1] chunk size (scan length)
-    SampleArgs a{mp.size_[0].as<u64>(), mp.ent_off_[0].as<u64>(), mp.d_str_off_.as<u64>(), mp.d_chars_.as<uint8_t>(),
-                 cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, seed, 0, 0, pattern_length, out_.as<uint8_t>(),
+    const EdsView v = de.view();
+    SampleArgs a{v.sym.size, v.sym.ent_off, v.str_off, v.chars, cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, seed, 0, 0, pattern_length, out_.as<uint8_t>(),
                  witness ? wpos_.as<u64>() : nullptr, witness ? wcnt_.as<u64>() : nullptr, woff_.as<u64>(), nullptr, ctl};
     EventPair ev;
     std::vector<u64> hoff;
@@ -271,7 +257,7 @@ void QueryPipeline::genpatterns(MergePipeline& mp, const uint8_t* eds, size_t ed
         u64 hctl[2] = {NONE, cnt};
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
         EDSX_HIP(hipEventRecord(ev.a, st));
-        hipLaunchKernelGGL(k_pat_sample<false>, dim3(grid_for(cnt)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_pat_sample<false>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a);
         EDSX_HIP(hipEventRecord(ev.b, st));
         u64 err = NONE, total = 0;
         EDSX_HIP(hipMemcpyAsync(&err, ctl, 8, hipMemcpyDeviceToHost, st));
@@ -290,7 +276,7 @@ void QueryPipeline::genpatterns(MergePipeline& mp, const uint8_t* eds, size_t ed
             wdeg_.ensure(4 * std::max<u64>(total, 1));
             a.wdeg = wdeg_.as<int32_t>();
             EDSX_HIP(hipEventRecord(ev.a, st));
-            hipLaunchKernelGGL(k_pat_sample<true>, dim3(grid_for(cnt)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_pat_sample<true>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a);
             EDSX_HIP(hipEventRecord(ev.b, st));
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
@@ -312,12 +298,12 @@ void QueryPipeline::genpatterns(MergePipeline& mp, const uint8_t* eds, size_t ed
     }
 }
 
-void QueryPipeline::check(MergePipeline& mp, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, size_t nq,
+void QueryPipeline::check(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, size_t nq,
                           const u64* pos, const u64* choice_off, const int32_t* choices, const u64* pattern_off,
                           const uint8_t* patterns, int8_t* status, hipStream_t st)
 {
     info_ = QueryInfo{};
-    const u64 n = tables(mp, eds, eds_n, seds, seds_n, st);
+    const u64 n = tables(de, eds, eds_n, seds, seds_n, st);
     if (nq == 0) return;
     if (n == 0) { std::memset(status, 0, nq); return; }         // an empty EDS answers false first (:957)
     const u64 nch = choice_off[nq], npat = pattern_off[nq];
@@ -328,13 +314,13 @@ void QueryPipeline::check(MergePipeline& mp, const uint8_t* eds, size_t eds_n, c
     EDSX_HIP(hipMemcpyAsync(q_poff_.ptr, pattern_off, 8 * (nq + 1), hipMemcpyHostToDevice, st));
     if (nch) EDSX_HIP(hipMemcpyAsync(q_ch_.ptr, choices, 4 * nch, hipMemcpyHostToDevice, st));
     if (npat) EDSX_HIP(hipMemcpyAsync(q_pat_.ptr, patterns, npat, hipMemcpyHostToDevice, st));
-    CheckArgs a{mp.size_[0].as<u64>(), mp.ent_off_[0].as<u64>(), mp.d_str_off_.as<u64>(), mp.d_chars_.as<uint8_t>(),
-                W_ ? mp.bits_.as<u64>() : nullptr, W_, cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, D_,
+    const EdsView v = de.view();
+    CheckArgs a{v.sym.size, v.sym.ent_off, v.str_off, v.chars, v.bits, v.W, cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, D_,
                 nq, q_pos_.as<u64>(), q_coff_.as<u64>(), q_ch_.as<int32_t>(), nch, q_poff_.as<u64>(), q_pat_.as<uint8_t>(), npat,
                 q_status_.as<int8_t>()};
     EventPair ev;
     EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_pat_check, dim3(grid_for(nq)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_pat_check, dim3(grid_for(nq, 4096)), dim3(256), 0, st, a);
     EDSX_HIP(hipEventRecord(ev.b, st));
     EDSX_HIP(hipMemcpyAsync(status, q_status_.ptr, nq, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));

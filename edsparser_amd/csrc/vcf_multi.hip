@@ -333,7 +333,7 @@ void MultiMsa::leds_merge(HostBytes& eds, HostBytes& seds, uint32_t context_len)
     EDSX_HIP(hipSetDevice(r0.device));
     if (!r0.merge) r0.merge.reset(new MergePipeline());
     HostBytes lo, so;
-    r0.merge->run(eds.data, eds.size, seds.data, seds.size, context_len, true, lo, so, nullptr);
+    r0.merge->run(r0.merge_eds, eds.data, eds.size, seds.data, seds.size, context_len, true, lo, so, nullptr);
     std::swap(eds.data, lo.data); std::swap(eds.size, lo.size);
     std::swap(seds.data, so.data); std::swap(seds.size, so.size);
 }

@@ -2,7 +2,7 @@
 about 1 GB (edsx_eds_genpatterns), the checking of their 10**7 witnesses (edsx_eds_check_positions), and the
 container's seeded EDS::generate_patterns on the same EDS for comparison.
 
-Every call tokenises its .eds text again (MergePipeline::prepare); the kernel times below are device events around
+Every call tokenises its .eds text again (DeviceEds::load); the kernel times below are device events around
 k_pat_sample / k_pat_check only, on tables already in HBM.  Median of 5 timed runs after one warm-up.
 
     python tests/measure_genpatterns.py [--mb 1000] [--count 10000000] [--host-count 100000] [--out FILE]
