@@ -86,6 +86,11 @@ class PathsTiming(ctypes.Structure):
                [("bytes_written", ctypes.c_uint64)]
 
 
+class SubsetInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
+                                                "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
+
+
 class MsaInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("n_rows", "n_cols", "line_width", "n_variant_cols", "n_segments", "msa_bytes",
@@ -234,6 +239,8 @@ def load_library():
     lib.edsx_eds_spell_paths.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                          ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p, ctypes.c_uint64,
                                          P(_Buf), ctypes.c_void_p]
+    lib.edsx_eds_subset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(_Buf), P(_Buf), P(SubsetInfo)]
     _LIB = lib
     return lib
 
@@ -585,6 +592,20 @@ class Context(_Handle):
                                                    prefix.encode() if prefix is not None else None, int(line_width),
                                                    ctypes.byref(f), miss.ctypes.data))
         return self._take(f), miss[:n_out]
+
+    # ---- path subsetting (edsparser-subset)
+    def eds_subset(self, eds, seds, paths, keep_ids=False):
+        """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
+        FULL .eds text and .seds, each with a trailing line feed; kept paths are renumbered 1..len(paths) in ascending
+        order of their ids unless keep_ids (edsx_eds_subset)."""
+        import numpy as np
+        ids = np.ascontiguousarray(list(paths), dtype=np.uint64)
+        e, s, info = _Buf(), _Buf(), SubsetInfo()
+        ptr, n, keep = _input(eds)
+        self._check(self._lib.edsx_eds_subset(self._h, ptr, n, *_opt(seds), ids.ctypes.data if len(ids) else None, len(ids),
+                                              1 if keep_ids else 0, ctypes.byref(e), ctypes.byref(s), ctypes.byref(info)))
+        del keep
+        return self._take(e), self._take(s), _fields(info)
 
     def vcf_tokenised_on_device(self):
         return bool(self._lib.edsx_vcf_tokenised_on_device(self._h))

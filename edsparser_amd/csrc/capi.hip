@@ -21,6 +21,7 @@
 #include "multi_gpu.hpp"
 #include "path_device.hpp"
 #include "query_device.hpp"
+#include "subset_device.hpp"
 #include "synth.hpp"
 #include "vcf_contig.hpp"
 #include "vcf_device.hpp"
@@ -45,6 +46,7 @@ struct edsx_ctx {
     RangeScanner scan;                       // edsx_eds_scan_range / edsx_seds_scan_range
     QueryPipeline query;                     // edsx_eds_genpatterns / edsx_eds_check_positions
     LocatePipeline locate;                   // edsx_eds_locate, over query's tables
+    SubsetPipeline subset;                   // edsx_eds_subset
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -404,10 +406,17 @@ int edsx_multi_last_merge(const edsx_multi* m, edsx_merge_multi_info* out)
     return EDSX_OK;
 }
 
-void edsx_set_timing(edsx_ctx* ctx, int enabled) { if (ctx) ctx->msa.set_timing(enabled != 0); }
+void edsx_set_timing(edsx_ctx* ctx, int enabled)
+{
+    if (!ctx) return;
+    ctx->msa.set_timing(enabled != 0);
+    ctx->subset.set_timing(enabled != 0);
+}
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
-    return ctx ? ctx->msa.get_timing(names, total_ms, launches, cap) : 0;
+    if (!ctx) return 0;
+    const int n = ctx->msa.get_timing(names, total_ms, launches, cap);
+    return n + ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -931,6 +940,26 @@ int edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, con
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_spell(s, ids, n, names, prefix, line_width, fasta, missing); });
+}
+
+int edsx_eds_subset(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                    size_t n, int keep_ids, edsx_buf* eds_out, edsx_buf* seds_out, edsx_subset_info* info)
+{
+    clear(eds_out, seds_out);
+    zero(info);
+    return guarded(ctx, [&] {
+        if (!eds_out || !seds_out || (!eds && eds_size) || (n && !ids)) throw ParamError("null argument");
+        static_assert(sizeof(SubsetInfo) == sizeof(edsx_subset_info) &&
+                      offsetof(SubsetInfo, common_runs_merged) == offsetof(edsx_subset_info, common_runs_merged),
+                      "edsx_subset_info is SubsetInfo");
+        HostBytes e, s;
+        SubsetInfo si;
+        ctx->subset.run(ctx->eds, or_empty(eds), eds_size, seds, seds_size, reinterpret_cast<const u64*>(ids), n, keep_ids != 0, e, s,
+                        si, nullptr);
+        if (info) std::memcpy(info, &si, sizeof(si));
+        give(eds_out, e);
+        give(seds_out, s);
+    });
 }
 
 int edsx_vcf_index(edsx_ctx* ctx, const uint8_t* vcf, size_t vcf_size, edsx_buf* pos, edsx_buf* reflen, edsx_buf* line_off,

@@ -62,6 +62,29 @@ void eds_to_fasta(std::istream& eds_in, std::istream& seds_in, std::ostream& out
     if (missing) missing->assign(miss.begin(), miss.end());
 }
 
+void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
+                const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    edsx_ctx* ctx = detail::context();
+    detail::Buf e, s;
+    edsx_subset_info si;
+    const int rc = edsx_eds_subset(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                                   reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), ids.data(), ids.size(),
+                                   keep_ids ? 1 : 0, &e.b, &s.b, &si);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    eds_out.write(reinterpret_cast<const char*>(e.b.data), static_cast<std::streamsize>(e.b.size));
+    seds_out.write(reinterpret_cast<const char*>(s.b.data), static_cast<std::streamsize>(s.b.size));
+    if (info) {
+        info->symbols_in = si.symbols_in; info->symbols_out = si.symbols_out; info->strings_in = si.strings_in;
+        info->strings_out = si.strings_out; info->chars_in = si.chars_in; info->chars_out = si.chars_out;
+        info->paths_in = si.paths_in; info->paths_out = si.paths_out; info->symbols_removed = si.symbols_removed;
+        info->common_runs_merged = si.common_runs_merged;
+    }
+}
+
 bool is_leds(const EDS& eds, Length context_length)
 {
     if (context_length == 0) return true;

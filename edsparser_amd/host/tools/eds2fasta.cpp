@@ -14,36 +14,6 @@ using namespace edsparser;
 
 namespace {
 
-// "1,5,7-9" -> 1 5 7 8 9
-std::vector<uint64_t> parse_paths(const std::string& text)
-{
-    std::vector<uint64_t> ids;
-    auto bad = [&] { return std::runtime_error("the argument ('" + text + "') for option '--paths' is invalid"); };
-    auto number = [&](const std::string& t) {
-        size_t used = 0;
-        unsigned long long v = 0;
-        if (t.empty() || t[0] < '0' || t[0] > '9') throw bad();
-        try { v = std::stoull(t, &used); } catch (...) { used = 0; }
-        if (used != t.size()) throw bad();
-        return static_cast<uint64_t>(v);
-    };
-    size_t pos = 0;
-    while (pos <= text.size()) {
-        size_t end = text.find(',', pos);
-        if (end == std::string::npos) end = text.size();
-        const std::string item = text.substr(pos, end - pos);
-        const size_t dash = item.find('-');
-        if (dash == std::string::npos) ids.push_back(number(item));
-        else {
-            const uint64_t a = number(item.substr(0, dash)), b = number(item.substr(dash + 1));
-            if (b < a || b - a > (1ull << 32)) throw bad();
-            for (uint64_t p = a; p <= b; p++) ids.push_back(p);
-        }
-        pos = end + 1;
-    }
-    return ids;
-}
-
 struct Session {
     edsx_paths_session* s = nullptr;
     ~Session() { edsx_paths_close(s); }
@@ -90,7 +60,7 @@ int main(int argc, char** argv)
         if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
         if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
         std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = parse_paths(opts.get("paths"));
+        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
 
         std::cout << "EDS → FASTA path spelling\n";
         std::cout << "  Input: " << input_file << "\n";

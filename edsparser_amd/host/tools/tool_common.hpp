@@ -14,6 +14,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace tool {
 
@@ -72,6 +73,36 @@ inline void write_bytes(const std::filesystem::path& path, const uint8_t* data, 
     std::ofstream out(path, std::ios::binary);
     if (!out) throw std::runtime_error(std::string("Failed to open ") + what + " file: " + path.string());
     out.write(reinterpret_cast<const char*>(data), static_cast<std::streamsize>(n));
+}
+
+// "1,5,7-9" -> 1 5 7 8 9 (the -p / --paths grammar of eds2fasta and edsparser-subset)
+inline std::vector<uint64_t> parse_paths(const std::string& text)
+{
+    std::vector<uint64_t> ids;
+    auto bad = [&] { return std::runtime_error("the argument ('" + text + "') for option '--paths' is invalid"); };
+    auto number = [&](const std::string& t) {
+        size_t used = 0;
+        unsigned long long v = 0;
+        if (t.empty() || t[0] < '0' || t[0] > '9') throw bad();
+        try { v = std::stoull(t, &used); } catch (...) { used = 0; }
+        if (used != t.size()) throw bad();
+        return static_cast<uint64_t>(v);
+    };
+    size_t pos = 0;
+    while (pos <= text.size()) {
+        size_t end = text.find(',', pos);
+        if (end == std::string::npos) end = text.size();
+        const std::string item = text.substr(pos, end - pos);
+        const size_t dash = item.find('-');
+        if (dash == std::string::npos) ids.push_back(number(item));
+        else {
+            const uint64_t a = number(item.substr(0, dash)), b = number(item.substr(dash + 1));
+            if (b < a || b - a > (1ull << 32)) throw bad();
+            for (uint64_t p = a; p <= b; p++) ids.push_back(p);
+        }
+        pos = end + 1;
+    }
+    return ids;
 }
 
 } // namespace tool

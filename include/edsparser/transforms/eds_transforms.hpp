@@ -34,6 +34,19 @@ void eds_to_fasta(std::istream& eds, std::istream& seds, std::ostream& out, cons
                   size_t line_width = 60, const std::vector<std::string>* names = nullptr,
                   std::vector<size_t>* missing = nullptr);
 
+// edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
+// .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
+// a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of
+// adjacent common symbols are joined (edsx_eds_subset states the rules in full).  Kept paths are renumbered 1..|paths| in
+// ascending order of their ids unless keep_ids.  Every kept path spells the sequence it spelled before.
+// std::invalid_argument for an empty list, a path outside 1..P or a path listed twice.
+struct SubsetInfo {
+    size_t symbols_in = 0, symbols_out = 0, strings_in = 0, strings_out = 0, chars_in = 0, chars_out = 0, paths_in = 0,
+           paths_out = 0, symbols_removed = 0, common_runs_merged = 0;
+};
+void eds_subset(std::istream& eds, std::istream& seds, std::ostream& eds_out, std::ostream& seds_out,
+                const std::vector<int>& paths, bool keep_ids = false, SubsetInfo* info = nullptr);
+
 } // namespace edsparser
 
 #endif

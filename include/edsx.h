@@ -472,8 +472,38 @@ int  edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, co
                           const uint64_t* ids, size_t n, const char* const* names, const char* prefix, uint64_t line_width,
                           edsx_buf* fasta, uint64_t* missing);
 
+/* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
+ * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
+ * n path ids, the keep set K.  P is the largest path id in the .seds.
+ *   1. Strings.  String j has the source set S_j.  If S_j holds 0 the string is kept and stays universal.  Otherwise
+ *      S'_j = S_j & K, and the string is kept iff S'_j is not empty.  File order is kept; equal texts are not merged.
+ *   2. Symbols.  A symbol without a kept string is removed (no kept path took a string there).  A symbol with exactly
+ *      one kept string whose set is universal or holds all of K is COMMON: its set becomes {0}.  A symbol with one kept
+ *      string whose set does not hold all of K stays a one-string symbol with its explicit set ({0} would hand the string
+ *      to paths that had none there).  Sets inside symbols with several kept strings are never rewritten to {0}, not
+ *      even when they equal K.
+ *   3. Runs.  After the removals, every maximal run of adjacent common symbols is concatenated into one symbol with the
+ *      set {0}; removed symbols between two commons do not break a run.  A run whose concatenation is empty is dropped.
+ *   Ids.  Path p of K becomes its 1-based rank in ascending K (ids stay dense), or stays p with keep_ids != 0.
+ *   Output.  The .eds is always in FULL form - braces around every symbol - followed by '\n', as EDS::save writes it;
+ *      the .seds has one "{ids}" per kept string, ids ascending, followed by '\n'.  There is no compact form: a
+ *      one-string symbol with an explicit set, printed without braces, would fuse with its neighbours when read back and
+ *      no longer match its .seds in cardinality.  When every symbol is dropped both texts are "\n".
+ *   Invariant.  For every p of K, the sequence edsx_paths_spell spells for p's new id in the output equals the sequence
+ *      it spells for p in the input; missing[p] can only decrease (removed symbols no longer count).
+ * info (may be NULL): symbols_removed counts the symbols of step 2; common_runs_merged the runs of step 3 that were
+ * formed from two or more symbols (dropped ones included).
+ * Errors, all EDSX_ERR_INVALID_PARAMETER: seds == NULL "Path subsetting needs sources (.seds)"; n == 0 "No paths
+ * selected"; an id of 0 or above P "Path id <p> out of range (1..<P>)"; an id listed twice "Path id <p> given twice".
+ * The call tokenises into the context's own tables, like edsx_eds_stats: path sessions are not touched. */
+typedef struct { uint64_t symbols_in, symbols_out, strings_in, strings_out, chars_in, chars_out,
+                 paths_in /* P */, paths_out /* |K| */, symbols_removed, common_runs_merged; } edsx_subset_info;
+int edsx_eds_subset(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                    const uint64_t* ids, size_t n, int keep_ids, edsx_buf* eds_out, edsx_buf* seds_out,
+                    edsx_subset_info* info);
+
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
- * accumulated over all plan/emit calls since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
+ * accumulated over all plan/emit calls (and edsx_eds_subset calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
  * total_ms[i] / launches[i] is the average duration of kernel names[i].  Returns the entry count. */
 void edsx_set_timing(edsx_ctx* ctx, int enabled);
 int  edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap);
