@@ -1,6 +1,8 @@
 """Build libedsx.so (HIP kernels + C ABI) for gfx950 with hipcc, in-tree.
 
-One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link.
+One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link; two more
+libraries for the tests only (libedsx_smallstacks.so, libedsx_guard.so) relink the same objects with one source each
+compiled with other flags.
 """
 import os
 import subprocess
@@ -11,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libedsx.so")
-SOURCES = ["msa_device.hip", "msa_scan.hip", "eds_device.hip", "merge_device.hip", "merge_scan.hip", "vcf_device.hip", "vcf_contig.hip", "bgzf_device.hip", "synth.hip", "genrandom.hip", "genvcf.hip", "multi_gpu.hip", "vcf_multi.hip", "merge_multi.hip", "query_device.hip", "locate_device.hip", "path_device.hip", "subset_device.hip", "capi.hip"]
+SOURCES = ["dev_alloc.hip", "msa_device.hip", "msa_scan.hip", "eds_device.hip", "merge_device.hip", "merge_scan.hip", "vcf_device.hip", "vcf_contig.hip", "bgzf_device.hip", "synth.hip", "genrandom.hip", "genvcf.hip", "multi_gpu.hip", "vcf_multi.hip", "merge_multi.hip", "query_device.hip", "locate_device.hip", "path_device.hip", "subset_device.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # per-source flags.  msa_scan.hip: machine scheduler off - the column scan's loads stay in source order (bench shape: scan
 # 26.5 instead of 26.9 ms; the same flag on msa_device.hip costs its emitters 0.2 ms: alternating A/B runs, EXPERIMENTS.md)
@@ -21,6 +23,10 @@ EXTRA_FLAGS = {"msa_scan.hip": ["-mllvm", "-enable-misched=false"]}
 # merge trees deeper than 96 (tests/test_merge_gpu.py::test_deep_tree_fallback_paths).  Never loaded by the product.
 TEST_LIB = os.path.join(HERE, "libedsx_smallstacks.so")
 TEST_FLAGS = {"merge_device.hip": ["-DEDSX_EXPERIMENTS", "-DEDSX_FW_STACK=256", "-DEDSX_FIN_STACK=2"]}
+# A third one, also for the tests only: every DevBuf between two 64 KiB zones of known bytes that are looked at after each
+# call (csrc/dev_alloc.hip with -DEDSX_GUARD, tests/test_guard_gpu.py).  Never loaded by the product.
+GUARD_LIB = os.path.join(HERE, "libedsx_guard.so")
+GUARD_FLAGS = {"dev_alloc.hip": ["-DEDSX_GUARD"]}
 
 
 def _headers():
@@ -68,14 +74,15 @@ def build(force=False, verbose=False):
             list(ex.map(lambda j: _compile(j[0], j[1], j[2], verbose), jobs))
     if force or _newer(LIB, objs):
         _link(objs, LIB, verbose)
-    tobjs = list(objs)
-    for name, extra in TEST_FLAGS.items():
-        src, obj = os.path.join(CSRC, name), os.path.join(OBJ, name.replace(".hip", ".smallstacks.o"))
-        tobjs[tobjs.index(os.path.join(OBJ, name.replace(".hip", ".o")))] = obj
-        if force or _newer(obj, [src] + hdrs):
-            _compile(src, obj, extra, verbose)
-    if force or _newer(TEST_LIB, tobjs):
-        _link(tobjs, TEST_LIB, verbose)
+    for lib, tag, flags in ((TEST_LIB, "smallstacks", TEST_FLAGS), (GUARD_LIB, "guard", GUARD_FLAGS)):
+        tobjs = list(objs)
+        for name, extra in flags.items():
+            src, obj = os.path.join(CSRC, name), os.path.join(OBJ, name.replace(".hip", ".%s.o" % tag))
+            tobjs[tobjs.index(os.path.join(OBJ, name.replace(".hip", ".o")))] = obj
+            if force or _newer(obj, [src] + hdrs):
+                _compile(src, obj, extra, verbose)
+        if force or _newer(lib, tobjs):
+            _link(tobjs, lib, verbose)
     return LIB
 
 

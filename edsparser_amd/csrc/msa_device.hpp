@@ -19,6 +19,13 @@ struct ParamError : std::runtime_error { using std::runtime_error::runtime_error
 // not a format error - the reference has no such limit
 struct LimitError : std::runtime_error { using std::runtime_error::runtime_error; };
 
+// Where device memory comes from (dev_alloc.hip): the only hipMalloc / hipFree of the library.  dev_alloc releases *ptr when
+// it is set, then allocates `bytes` rounded up to 256 and stores the pointer and the rounded size; a failure leaves *ptr
+// null and *cap 0 and throws OutOfDeviceMemory / DeviceError.  Hidden: not part of what the library exports.  The tests'
+// libedsx_guard.so links another definition of the two (the same file with -DEDSX_GUARD).
+__attribute__((visibility("hidden"))) void dev_alloc(size_t bytes, void** ptr, size_t* cap);
+__attribute__((visibility("hidden"))) void dev_free(void* ptr);
+
 // grow-only device allocation
 struct DevBuf {
     void* ptr = nullptr;
@@ -26,19 +33,9 @@ struct DevBuf {
     void ensure(size_t bytes)
     {
         if (bytes <= cap) return;
-        if (ptr) { (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-        size_t want = (bytes + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(&ptr, want);
-        if (e != hipSuccess) {
-            ptr = nullptr;
-            (void)hipGetLastError();                              // (the failure is reported here, not by the next launch check)
-            const std::string what = std::string("hipMalloc of ") + std::to_string(want) + " bytes: " + hipGetErrorString(e);
-            if (e == hipErrorOutOfMemory) throw OutOfDeviceMemory(what);
-            throw DeviceError(what);
-        }
-        cap = want;
+        dev_alloc(bytes, &ptr, &cap);
     }
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
+    void release() { if (ptr) dev_free(ptr); ptr = nullptr; cap = 0; }
     template <class T> T* as() const { return static_cast<T*>(ptr); }
     ~DevBuf() { release(); }
     DevBuf() = default;

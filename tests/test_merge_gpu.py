@@ -8,6 +8,7 @@ import pytest
 
 import oracle_lib as o
 from conftest import GOLDEN
+from merge_cases import big_eds as _big_eds, boundary_shifted, boundary_texts, long_leaf_eds as _long_leaf_eds
 
 pytestmark = pytest.mark.gpu
 
@@ -151,46 +152,6 @@ def test_random_larger_inputs_vs_oracle(ctx, with_src):
             got = _run(ctx, eds, seds, l, compact)
             got.pop("code", None)
             assert got == want, (it, n, l, compact)
-
-
-def _big_eds(rng, nsym, paths, compact_in, spacing):
-    """genrandomeds-like text of >= 1 MB: long common blocks, sites `spacing` symbols apart on average.
-    compact_in: non-degenerate symbols without braces (EDS::save COMPACT), plus whitespace noise."""
-    eds, seds = [], []
-    for i in range(nsym):
-        if i % 2 == 0:
-            s = "".join(rng.choice("ACGT") for _ in range(rng.randint(1, spacing)))
-            eds.append(s if compact_in else "{" + s + "}")
-            seds.append("{0}")
-        else:
-            k = rng.randint(2, 4)
-            alts = ["".join(rng.choice("ACGT") for _ in range(rng.randint(0, 3))) for _ in range(k)]
-            choice = [p if p < k else rng.randrange(k) for p in range(paths)]
-            eds.append("{" + ",".join(alts) + "}")
-            for a in range(k):
-                seds.append("{" + ",".join(str(p + 1) for p in range(paths) if choice[p] == a) + "}")
-        if compact_in and i % 97 == 0:
-            eds.append("\n" if i % 2 else " \t")
-            seds.append("\n")
-    return "".join(eds).encode(), "".join(seds).encode()
-
-
-def _long_leaf_eds(rng, nsym, paths, lens):
-    """variant sites between common strings whose lengths are drawn from `lens` (long leaves of the merge trees)"""
-    eds, seds = [], []
-    for i in range(nsym):
-        if i % 2 == 0:
-            n = rng.choice(lens)
-            eds.append("{" + "".join(rng.choice("ACGT") for _ in range(n)) + "}")
-            seds.append("{0}")
-        else:
-            k = rng.randint(2, 3)
-            alts = ["".join(rng.choice("ACGT") for _ in range(rng.randint(0, 2))) for _ in range(k)]
-            choice = [q if q < k else rng.randrange(k) for q in range(paths)]
-            eds.append("{" + ",".join(alts) + "}")
-            for a in range(k):
-                seds.append("{" + ",".join(str(q + 1) for q in range(paths) if choice[q] == a) + "}")
-    return "".join(eds).encode(), "".join(seds).encode()
 
 
 @pytest.mark.gpu
@@ -374,20 +335,7 @@ def test_device_tokeniser_block_and_thread_boundaries(ctx):
     """The device tokenisers work on 4 KB blocks of 256 x 16 bytes: every brace, comma, bare-run start and id of a text is
     moved across those boundaries (a bare prefix of p letters in the .eds, an id with p leading zeros in the .seds shift
     everything behind them by p), and the result is compared with the host tokenisers and the oracle."""
-    rng = random.Random(4096)
-    syms = []
-    for _ in range(900):
-        k = rng.choice([1, 1, 2, 3, 4])
-        strs = ["".join(rng.choice("ACGT") for _ in range(rng.choice([0, 1, 2, 5, 17]))) for _ in range(k)]
-        if k == 1 and not strs[0]:
-            strs[0] = "A"
-        syms.append(strs)
-    body = "".join("{" + ",".join(x) + "}" for x in syms)
-    # (the first string of every symbol is on all paths, so no merge comes out empty)
-    sbody = "".join("{" + (",".join(str(rng.randint(1, 1500)) for _ in range(rng.randint(1, 3))) if j else "0") + "}"
-                    for x in syms for j in range(len(x)))
-    assert len(body) > 3 * 4096 and len(sbody) > 3 * 4096
-    shifts = list(range(1, 18)) + [31, 32, 33] + list(range(4085, 4108, 2)) + [8191, 8192, 8193]
+    body, sbody, shifts = boundary_texts()
 
     def both_tokenisers(fn):
         got = fn()
@@ -401,8 +349,7 @@ def test_device_tokeniser_block_and_thread_boundaries(ctx):
         return got, host
 
     for p_ in shifts:
-        eds = ("A" * p_ + body).encode()
-        seds = ("{" + "0" * p_ + "}" + sbody).encode()
+        eds, seds = boundary_shifted(body, sbody, p_)
         got, host = both_tokenisers(lambda: _run(ctx, eds, seds, 4, True))
         assert got == host, p_
         # (without sources the merge is CARTESIAN and its output explodes: the tokenisers alone, through the statistics call)

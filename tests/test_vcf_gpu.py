@@ -8,6 +8,7 @@ import pytest
 
 import oracle_lib as o
 from conftest import GOLDEN
+from vcf_cases import large_key_vcf, random_vcf as _random_vcf, single_damage_files, text_length_files
 
 pytestmark = pytest.mark.gpu
 
@@ -59,30 +60,6 @@ def test_generated_reference_fixtures_round2(ctx):
     for c in cases:
         got = _run(ctx, c["vcf"].encode(), c["fasta"].encode(), c["l"])
         assert got == c["expect"], c["name"]
-
-
-def _random_vcf(rng, L, nvar, ns, lw):
-    ref = "".join(rng.choice("ACGT") for _ in range(L))
-    fasta = ">chr1 synthetic\n" + "\n".join(ref[i:i + lw] for i in range(0, L, lw)) + "\n"
-    pos = sorted(rng.sample(range(1, L + 1), nvar))
-    lines = ["##fileformat=VCFv4.2", "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] +
-                                                ["S%d" % i for i in range(ns)])]
-    for p in pos:
-        x = rng.random()
-        if x < 0.7:
-            r = ref[p - 1]
-            alts = [rng.choice([b for b in "ACGT" if b != r])]
-            if rng.random() < 0.1:
-                alts.append(rng.choice("ACGT"))
-        elif x < 0.85:
-            r = ref[p - 1]
-            alts = [r + "".join(rng.choice("ACGT") for _ in range(rng.randint(1, 10)))]
-        else:
-            r = ref[p - 1:p + rng.randint(1, 10)]
-            alts = [r[0]]
-        gts = ["|".join(str(rng.randint(0, len(alts)) if rng.random() < 0.3 else 0) for _ in range(2)) for _ in range(ns)]
-        lines.append("\t".join(["chr1", str(p), ".", r, ",".join(alts), ".", "PASS", ".", "GT"] + gts))
-    return ("\n".join(lines) + "\n").encode(), fasta.encode()
 
 
 @pytest.mark.parametrize("L,nvar,ns,lw,l", [(5000, 300, 8, 60, 0), (20000, 1500, 3, 70, 0), (3000, 200, 70, 3000, 0),
@@ -195,43 +172,13 @@ def test_device_tokeniser_single_damage_per_file(ctx):
     tokeniser: the result must equal the oracle's either way (a wrongly accepted line would show here, where no
     second oddity in the same file can trigger the fallback for it)."""
     rng = random.Random(808)
-    gts = ["./.", ".", "1", "0/1/2", "x|1", "1|", "|", "0|1:9:x", ":", "99999999999|0", "0|1\r", "+1|0", " 1|0", "01|1", "1x|0", "|1", "0||1", "0/1|1"]
-    alts = ["<DEL>", "<INS>", "<INV>", "A,<DEL>", "<DUP>,C", ",", "A,,C", "C,", "<>", "<", ".", "*", "<DEL>,<INS>", "ACGTACGT", "<DELX>", "<del>"]
-    poss = ["0", "-5", "+7", " 12", "12abc", "abc", "99999999999999999999999", "18446744073709551615", "0012", "1", "3000"]
-    wholes = ["", "#junk", "chr1", "\t\t\t", "chr1\t12\t.\tA", "chr1 14 . A G . PASS . GT 0|1 1|1", "chr1\t15\t.\tA\tG", "chr1\t16\t.\tA\tG\t.\tPASS\t.\tGT",
-              "\tchr1\t17\t.\tA\tG\t.\tPASS\t.\tGT\t0|1\t0|0", "chr1\t18\t.\tA\tG\t.\tPASS\t.\tGT\t0|1\t", "chr1\t19\t.\tA\tG\t\t.\tPASS\t.\tGT\t0|1"]
     taken = {True: 0, False: 0}
     n = 0
-    for kind, choices in (("gt", gts), ("alt", alts), ("pos", poss), ("line", wholes), ("cr", ["\r"]), ("tabs", ["x"])):
-        for ch in choices:
-            for ns in (0, 2):
-                vcf, fasta = _random_vcf(rng, 3000, 25, ns, 60)
-                lines = vcf.decode().split("\n")
-                i = rng.randrange(2, len(lines) - 1)
-                f = lines[i].split("\t")
-                if kind == "gt":
-                    if ns == 0:
-                        continue
-                    f[9 + rng.randrange(ns)] = ch
-                    lines[i] = "\t".join(f)
-                elif kind == "alt":
-                    f[4] = ch
-                    lines[i] = "\t".join(f)
-                elif kind == "pos":
-                    f[1] = ch
-                    lines[i] = "\t".join(f)
-                elif kind == "line":
-                    lines.insert(i, ch)
-                elif kind == "cr":
-                    lines[i] += "\r"
-                else:
-                    lines[i] = lines[i].replace("\t", "\t\t", 1)
-                for tail in ("\n", ""):
-                    v = ("\n".join(lines[:-1]) + tail).encode()
-                    got = _run(ctx, v, fasta, 0)
-                    assert got == _want(v, fasta), (kind, ch, ns, tail, lines[i])
-                    taken[ctx.vcf_tokenised_on_device()] += 1
-                    n += 1
+    for kind, ch, ns, tail, line, v, fasta in single_damage_files(rng):
+        got = _run(ctx, v, fasta, 0)
+        assert got == _want(v, fasta), (kind, ch, ns, tail, line)
+        taken[ctx.vcf_tokenised_on_device()] += 1
+        n += 1
     assert n > 150 and taken[True] > 20 and taken[False] > 60, taken
 
 
@@ -287,33 +234,30 @@ def test_text_length_every_remainder_mod_8_with_and_without_final_newline(ctx):
     may end anywhere inside its word.  Text lengths 0..7 modulo 8 (a comment line of adjustable length in front), with
     and without the final newline, last record with a long ALT, an <INS> (copies REF) and a <DEL>; and a text whose
     length is just below / at / above multiples of 256 (the allocation granule of the text buffer)."""
-    rng = random.Random(88)
-    base_vcf, fasta = _random_vcf(rng, 2000, 60, 4, 60)
-    lines = base_vcf.decode().split("\n")
-    head, body = lines[:2], [x for x in lines[2:] if x]
-    ref = "".join(fasta.decode().split("\n")[1:])
-    last_pos = 1990
-    tails = [
-        "chr1\t%d\t.\t%s\t%s\t.\tPASS\t.\tGT\t0|1\t1|1\t0|0\t1|0" % (last_pos, ref[last_pos - 1], ref[last_pos - 1] + "ACGTACGTAC"),
-        "chr1\t%d\t.\t%s\t<INS>\t.\tPASS\t.\tGT\t0|1\t1|1\t0|0\t1|0" % (last_pos, ref[last_pos - 1:last_pos + 4]),
-        "chr1\t%d\t.\t%s\t<DEL>\t.\tPASS\t.\tGT\t0|1\t1|1\t0|0\t1|0" % (last_pos, ref[last_pos - 1:last_pos + 2]),
-    ]
-    body = [b for b in body if int(b.split("\t")[1]) < last_pos - 12]
+    fasta, mod8, sized = text_length_files(random.Random(88))
     seen = set()
-    for tail in tails:
-        for pad in range(0, 8):
-            for nl in ("\n", ""):
-                vcf = ("\n".join([head[0], "##pad=" + "x" * pad, head[1]] + body + [tail]) + nl).encode()
-                seen.add((len(vcf) % 8, nl))
-                got = _run(ctx, vcf, fasta, 0)
-                assert ctx.vcf_tokenised_on_device()
-                assert got == _want(vcf, fasta), (tail[:30], pad, nl)
+    for tail, pad, nl, vcf in mod8:
+        seen.add((len(vcf) % 8, nl))
+        got = _run(ctx, vcf, fasta, 0)
+        assert ctx.vcf_tokenised_on_device()
+        assert got == _want(vcf, fasta), (tail[:30], pad, nl)
     assert len(seen) == 16
-    for target in (255, 256, 257, 511, 512, 513, 4095, 4096, 4097):
-        stem = "\n".join([head[0], head[1]] + body[:3] + [tails[0]])
-        padn = target - len(stem) - len("##pad=\n")
-        if padn < 0:
-            continue
-        vcf = ("\n".join([head[0], "##pad=" + "x" * padn, head[1]] + body[:3] + [tails[0]])).encode()
+    for target, vcf in sized:
         assert len(vcf) == target
         assert _run(ctx, vcf, fasta, 0) == _want(vcf, fasta), target
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 4097, 70000])
+def test_device_sort_large_keys_and_tile_edges(ctx, n):
+    """The device radix sort runs eight 8-bit passes over 64-bit keys, in tiles of 2048 records: shuffled files with
+    pairwise distinct positions of one tile less one record, exactly one, one more, two and one more, and 35 tiles; a
+    quarter of the positions have 8 to 19 digits (up to 9 * 10^18), so that every pass sees digits other than 0.
+    (The oracle takes 0.5 s for the 70 000 records.)"""
+    vcf, fasta = large_key_vcf(random.Random(n), n)
+    pos = [int(x.split(b"\t")[1]) for x in vcf.split(b"\n")[2:] if x]
+    assert len(set(pos)) == n == len(pos) and pos != sorted(pos)
+    assert all(any((p >> (8 * k)) & 0xFF for p in pos) for k in range(8)) and max(pos) <= 9 * 10 ** 18
+    want = _want(vcf, fasta)
+    assert "error" not in want and want["stats"]["processed_variants"] == n
+    assert _run(ctx, vcf, fasta, 0) == want
+    assert ctx.vcf_tokenised_on_device()
