@@ -91,6 +91,13 @@ class SubsetInfo(ctypes.Structure):
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
 
 
+class GfaInfo(ctypes.Structure):
+    """edsx_gfa_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_symbols", "n_strings", "n_segments", "n_empty_strings", "n_open_symbols",
+                                                "n_links", "header_bytes", "segment_bytes", "link_bytes")] + \
+               [("tokenised_on_device", ctypes.c_int)]
+
+
 class MsaInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("n_rows", "n_cols", "line_width", "n_variant_cols", "n_segments", "msa_bytes",
@@ -241,6 +248,11 @@ def load_library():
                                          P(_Buf), ctypes.c_void_p]
     lib.edsx_eds_subset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, P(_Buf), P(_Buf), P(SubsetInfo)]
+    lib.edsx_eds_gfa_graph.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, P(_Buf), P(GfaInfo)]
+    lib.edsx_paths_gfa_walks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p,
+                                         P(_Buf), ctypes.c_void_p, ctypes.c_void_p]
+    lib.edsx_eds_gfa.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64,
+                                 ctypes.c_char_p, P(_Buf), P(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -607,6 +619,25 @@ class Context(_Handle):
         del keep
         return self._take(e), self._take(s), _fields(info)
 
+    # ---- GFA export (eds2gfa)
+    def eds_gfa_graph(self, eds, max_links=0):
+        """The EDS as GFA 1.0 text without paths - header, S lines, L lines - and an info dict (edsx_eds_gfa_graph).
+        max_links: 0 = 2**32."""
+        g, info = _Buf(), GfaInfo()
+        ptr, n, keep = _input(eds)
+        self._check(self._lib.edsx_eds_gfa_graph(self._h, ptr, n, int(max_links), ctypes.byref(g), ctypes.byref(info)))
+        del keep
+        return self._take(g), _fields(info, flags=("tokenised_on_device",))
+
+    def eds_gfa(self, eds, seds=None, max_links=0, prefix=None):
+        """The graph, followed by one P line per path when seds is given (edsx_eds_gfa) -> (gfa bytes, info dict)."""
+        g, info = _Buf(), GfaInfo()
+        ptr, n, keep = _input(eds)
+        self._check(self._lib.edsx_eds_gfa(self._h, ptr, n, *_opt(seds), int(max_links),
+                                           prefix.encode() if prefix is not None else None, ctypes.byref(g), ctypes.byref(info)))
+        del keep
+        return self._take(g), _fields(info, flags=("tokenised_on_device",))
+
     def vcf_tokenised_on_device(self):
         return bool(self._lib.edsx_vcf_tokenised_on_device(self._h))
 
@@ -781,7 +812,7 @@ class PathSession(_Handle):
 
     @property
     def timing(self):
-        """Of the last lengths / spell: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
+        """Of the last lengths / spell / gfa_walks: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
         t = PathsTiming()
         self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
         return _fields(t, _raw)
@@ -821,6 +852,21 @@ class PathSession(_Handle):
             self._lib.edsx_buf_free(ctypes.byref(f))
             return out, miss[:n_out]
         return self._ctx._take(f), miss[:n_out]
+
+    def gfa_walks(self, paths=None, names=None, prefix=None):
+        """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths
+        1..P) over the segment ids of Context.eds_gfa_graph, and per path the missing count and the number of ids (numpy
+        uint64); a path without a step has no line (edsx_paths_gfa_walks)."""
+        import numpy as np
+        ids, nm, n_out = _path_args(paths, names)
+        if len(ids) == 0:
+            n_out = self.info["num_paths"]
+        miss, steps = np.zeros(max(n_out, 1), dtype=np.uint64), np.zeros(max(n_out, 1), dtype=np.uint64)
+        f = _Buf()
+        self._ctx._check(self._lib.edsx_paths_gfa_walks(self._h, ids.ctypes.data if len(ids) else None, len(ids), nm,
+                                                        prefix.encode() if prefix is not None else None, ctypes.byref(f),
+                                                        miss.ctypes.data, steps.ctypes.data))
+        return self._ctx._take(f), miss[:n_out], steps[:n_out]
 
 
 class VcfSession(_Handle):

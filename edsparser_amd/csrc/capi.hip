@@ -14,6 +14,7 @@
 #include "bgzf_device.hpp"
 #include "genrandom.hpp"
 #include "genvcf.hpp"
+#include "gfa_device.hpp"
 #include "locate_device.hpp"
 #include "merge_device.hpp"
 #include "merge_scan.hpp"
@@ -47,6 +48,7 @@ struct edsx_ctx {
     QueryPipeline query;                     // edsx_eds_genpatterns / edsx_eds_check_positions
     LocatePipeline locate;                   // edsx_eds_locate, over query's tables
     SubsetPipeline subset;                   // edsx_eds_subset
+    GfaPipeline gfa;                         // edsx_eds_gfa_graph
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -411,12 +413,14 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     if (!ctx) return;
     ctx->msa.set_timing(enabled != 0);
     ctx->subset.set_timing(enabled != 0);
+    ctx->gfa.set_timing(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
     if (!ctx) return 0;
-    const int n = ctx->msa.get_timing(names, total_ms, launches, cap);
-    return n + ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    int n = ctx->msa.get_timing(names, total_ms, launches, cap);
+    n += ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -959,6 +963,72 @@ int edsx_eds_subset(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
         if (info) std::memcpy(info, &si, sizeof(si));
         give(eds_out, e);
         give(seds_out, s);
+    });
+}
+
+// ---- eds2gfa (gfa_device.hip; the P lines: path_device.hip)
+int edsx_eds_gfa_graph(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t max_links, edsx_buf* gfa, edsx_gfa_info* info)
+{
+    clear(gfa);
+    zero(info);
+    return guarded(ctx, [&] {
+        if (!gfa || (!eds && eds_size)) throw ParamError("null argument");
+        static_assert(offsetof(edsx_gfa_info, tokenised_on_device) == sizeof(GfaInfo), "edsx_gfa_info begins with GfaInfo");
+        HostBytes g;
+        GfaInfo gi;
+        try { ctx->gfa.run(ctx->eds, or_empty(eds), eds_size, nullptr, 0, max_links, g, gi, nullptr); }
+        catch (const ParamError&) {                              // the link limit: the counts are known
+            if (info) { std::memcpy(info, &gi, sizeof(gi)); info->tokenised_on_device = ctx->eds.tokenised_on_device() ? 1 : 0; }
+            throw;
+        }
+        if (info) { std::memcpy(info, &gi, sizeof(gi)); info->tokenised_on_device = ctx->eds.tokenised_on_device() ? 1 : 0; }
+        give(gfa, g);
+    });
+}
+
+int edsx_paths_gfa_walks(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                         edsx_buf* lines, uint64_t* missing, uint64_t* steps)
+{
+    clear(lines);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!lines || (n && !ids)) throw ParamError("null argument");
+        std::vector<u64> all;
+        if (n == 0) {                                            // every path
+            if (names) throw ParamError("names need an explicit list of path ids");
+            all.resize(s->p.info().num_paths);
+            for (size_t k = 0; k < all.size(); k++) all[k] = k + 1;
+        }
+        if (names) for (size_t k = 0; k < n; k++) if (!names[k]) throw ParamError("null argument");
+        HostBytes out;
+        s->p.walks(n ? reinterpret_cast<const u64*>(ids) : all.data(), n ? n : all.size(), names, prefix, out,
+                   reinterpret_cast<u64*>(missing), reinterpret_cast<u64*>(steps), nullptr);
+        give(lines, out);
+    });
+}
+
+int edsx_eds_gfa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, uint64_t max_links,
+                 const char* prefix, edsx_buf* gfa, edsx_gfa_info* info)
+{
+    clear(gfa);
+    zero(info);
+    if (!seds) return edsx_eds_gfa_graph(ctx, eds, eds_size, max_links, gfa, info);
+    edsx_paths_session* s = nullptr;                             // first: a text that does not match its sources is an error
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close, [&] {
+        edsx_buf graph{nullptr, 0}, lines{nullptr, 0};
+        int rc = edsx_eds_gfa_graph(ctx, eds, eds_size, max_links, &graph, info);
+        if (rc == EDSX_OK) rc = edsx_paths_gfa_walks(s, nullptr, 0, nullptr, prefix, &lines, nullptr, nullptr);
+        if (rc == EDSX_OK)
+            rc = guarded(ctx, [&] {
+                if (!gfa) throw ParamError("null argument");
+                gfa->data = HostBytes::alloc(graph.size + lines.size);
+                gfa->size = graph.size + lines.size;
+                if (graph.size) std::memcpy(gfa->data, graph.data, graph.size);
+                if (lines.size) std::memcpy(gfa->data + graph.size, lines.data, lines.size);
+            });
+        edsx_buf_free(&graph);
+        edsx_buf_free(&lines);
+        return rc;
     });
 }
 

@@ -21,6 +21,17 @@
 //                            put in on the way (output byte o of a body holds sequence character
 //                            o - o / (line_width + 1)), one 16-byte load where the 16 bytes come out of one string,
 //                            and always one 16-byte store.
+//
+// GFA walks (edsx_paths_gfa_walks): the P line of a path lists the segment ids of its non-empty chosen
+// strings.  Its token text ("<id>+," per step) is laid out like the sequence above with token bytes in place of
+// characters (gfa_text.hpp), so the same tables carry it:
+//   first call k_path_tokfixed seg_rank (segment_ranks, shared with gfa_device.hip) and the token bytes of the fixed
+//                              symbols, scanned once (cum_tok) and kept with the session
+//   per batch  k_path_tok      after k_path_choose: token bytes per (path, choice symbol), scanned like the lengths; the
+//                              steps of a row are counted with one atomic per wave
+//              k_path_walk     the shape of k_path_copy: a workgroup per (16 KiB of a line, path), the symbol range by the
+//                              256-way search, 16 bytes per lane assembled in registers and stored at once; the last
+//                              comma of a line is a tab and "*\n" follows.  No LDS cache of the stretch's offsets
 #include "path_device.hpp"
 
 #include <chrono>
@@ -240,6 +251,93 @@ __global__ void __launch_bounds__(CP_THREADS) k_path_copy(CopyArgs a)
     }
 }
 
+// ---- GFA walks (P lines): the same tables over token bytes instead of characters (gfa_text.hpp) -----------------------
+// token bytes ("<id>+,") of every fixed symbol whose string is not empty, and a 1 for each such symbol
+__global__ void k_path_tokfixed(const u64* __restrict__ ent_off, const u32* __restrict__ elen, const u64* __restrict__ seg_rank,
+                                const u64* __restrict__ rank, u64 n, u64* __restrict__ tok, u64* __restrict__ cnt)
+{
+    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i <= n; i += (u64)gridDim.x * blockDim.x) {
+        u64 t = 0;
+        if (i < n && rank[i + 1] == rank[i]) { const u64 j = ent_off[i]; if (elen[j]) t = gfa::digits(seg_rank[j] + 1) + 2; }
+        tok[i] = t;
+        cnt[i] = t ? 1 : 0;
+    }
+}
+
+// token bytes per (path, choice symbol); cnt[k]: the tokens of row k (one atomic per wave where a wave lies in one row)
+__global__ void __launch_bounds__(256) k_path_tok(const u64* __restrict__ csid, u64 nc, u64 K, const u32* __restrict__ elen,
+                                                  const u64* __restrict__ seg_rank, u64* __restrict__ tlen, u64* __restrict__ cnt)
+{
+    const u64 total = K * nc;
+    for (u64 base = blockIdx.x * (u64)blockDim.x; base < total; base += (u64)gridDim.x * blockDim.x) {   // block-uniform
+        const u64 t = base + threadIdx.x;
+        const bool act = t < total;
+        u64 k = NONE, tl = 0;
+        if (act) {
+            k = t / nc;
+            const u64 sid = csid[t];
+            if (sid != NONE && elen[sid]) tl = gfa::digits(seg_rank[sid] + 1) + 2;
+            tlen[t] = tl;
+        }
+        const u64 k0 = __shfl(k, 0, 64);                              // (t ascends: lane 0 is active when any lane is)
+        const u64 has = ballot64(tl != 0);
+        if (__all(!act || k == k0)) {
+            if ((threadIdx.x & 63) == 0 && has) atomicAdd((unsigned long long*)&cnt[k0], (unsigned long long)__popcll(has));
+        } else if (tl) atomicAdd((unsigned long long*)&cnt[k], 1ull);
+    }
+}
+
+// T: the scanned token bytes of the rows (K * nc + 1 entries)
+__global__ void k_path_toktotals(const u64* __restrict__ T, u64 nc, u64 F, u64 K, u64* __restrict__ tot)
+{
+    const u64 k = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (k < K) tot[k] = F + (nc ? T[(k + 1) * nc] - T[k * nc] : 0);
+}
+
+struct WalkArgs { gfa::WalkTab tab; const PathRec* rec; u64 nrec, max_tiles; uint8_t* out; };
+
+// largest i in [0, n) with walk_pos(i) <= q, as block_find
+__device__ u64 walk_block_find(const gfa::WalkTab& a, u64 kb, u64 q)
+{
+    u64 lo = 0, hi = a.n;
+    while (hi - lo > 1) {
+        const u64 step = (hi - lo + CP_THREADS - 1) / CP_THREADS;
+        const u64 i = lo + threadIdx.x * step;
+        const int ok = i < hi && gfa::walk_pos(a, kb, i) <= q;
+        const int cnt = __syncthreads_count(ok);
+        lo += (u64)(cnt - 1) * step;
+        hi = min(hi, lo + step);
+    }
+    return lo;
+}
+
+// One workgroup per (16 KiB of a path's line behind its name, path), paths fastest as in k_path_copy.  The workgroup finds
+// the first and last symbol of its stretch by the 256-way search; a lane finds the token its 16 bytes start in by
+// bisection between them, assembles the 16 bytes in registers (rec.L: the token bytes T; the body is T + 2 bytes, the
+// last comma a tab, then "*\n") and stores them at once.
+__global__ void __launch_bounds__(CP_THREADS) k_path_walk(WalkArgs a)
+{
+    const u64 work = a.max_tiles * a.nrec;
+    for (u64 wi = blockIdx.x; wi < work; wi += gridDim.x) {
+        const PathRec rc = a.rec[wi % a.nrec];
+        const u64 o0 = (wi / a.nrec) * CP_TILE;
+        if (o0 >= rc.body) continue;
+        const u64 o1 = min(rc.body, o0 + (u64)CP_TILE), kb = rc.row * a.tab.nc, T = rc.L;
+        u64 iA = 0, iB = 0;
+        if (o0 < T) {
+            iA = walk_block_find(a.tab, kb, o0);
+            iB = walk_block_find(a.tab, kb, min(o1, T) - 1);
+        }
+        for (u64 o = o0 + (u64)threadIdx.x * 16; o < o1; o += (u64)CP_THREADS * 16) {
+            const u32 nb = (u32)min((u64)16, o1 - o);
+            const gfa::B16 x = gfa::walk_chunk(a.tab, kb, iA, iB, T, o, nb);
+            uint8_t* dst = a.out + rc.body_off + o;
+            if (nb == 16) store16u(dst, make_uint4((u32)x.lo, (u32)(x.lo >> 32), (u32)x.hi, (u32)(x.hi >> 32)));
+            else for (u32 b = 0; b < nb; b++) dst[b] = (uint8_t)((b < 8 ? x.lo >> (8u * b) : x.hi >> (8u * (b - 8u))) & 0xffu);
+        }
+    }
+}
+
 u64 free_hbm()
 {
     size_t free_b = 0, total_b = 0;
@@ -254,6 +352,7 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     if (!seds) throw ParamError("Path spelling needs sources (.seds)");
     info_ = PathInfo{};
     timing_ = PathTiming{};
+    walk_ready_ = false;
     const auto t0 = std::chrono::steady_clock::now();
     eds_.load(eds, eds_n, seds, seds_n, true, st);
     eds_.drop_scratch();                                                      // the session may live long
@@ -311,11 +410,11 @@ u64 PathPipeline::budget_override()
     return e ? std::strtoull(e, nullptr, 10) : 0;
 }
 
-// paths per choice table: 16 bytes per (path, choice symbol) within a quarter of the free HBM
-u64 PathPipeline::table_batch(size_t n) const
+// paths per choice table: 16 bytes per (path, choice symbol) within a quarter of the free HBM (24 with the token bytes)
+u64 PathPipeline::table_batch(size_t n, u64 cell_bytes) const
 {
     const u64 ov = budget_override(), budget = ov ? ov : free_hbm() / 4;
-    return std::max<u64>(1, std::min<u64>(n, budget / (16 * nc_ + 64)));
+    return std::max<u64>(1, std::min<u64>(n, budget / (cell_bytes * nc_ + 64)));
 }
 
 void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st)
@@ -444,6 +543,154 @@ void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, con
             const auto t0 = std::chrono::steady_clock::now();
             PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
             timing_.download_ms += since_ms(t0);
+            r0 = r1;
+        }
+    }
+}
+
+void PathPipeline::walk_open(hipStream_t st)
+{
+    if (walk_ready_ || n_ == 0) return;
+    const EdsView v = eds_.view();
+    seg_rank_.ensure(8 * (v.m + 1));
+    cum_tok_.ensure(8 * (n_ + 1));
+    cnt_.ensure(8 * (n_ + 1));
+    ctl_.ensure(8 * 8);
+    scan_tmp_.ensure(8 * 2 * (v.m / SCAN_TILE + n_ / SCAN_TILE + 8));
+    u64 h[6] = {v.m + 1, n_ + 1, 0, 0, 0, 0};
+    u64* ctl = ctl_.as<u64>();
+    EDSX_HIP(hipMemcpyAsync(ctl, h, sizeof(h), hipMemcpyHostToDevice, st));
+    segment_ranks(v, seg_rank_.as<u64>(), ctl, ctl + 2, scan_tmp_.as<u64>(), st);
+    u64 *ct = cum_tok_.as<u64>(), *cn = cnt_.as<u64>();
+    hipLaunchKernelGGL(k_path_tokfixed, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.ent_off, v.elen, seg_rank_.as<u64>(),
+                       rank_.as<u64>(), n_, ct, cn);
+    ScanSet<2> ss{{ct, cn}, {ct, cn}, {ctl + 3, ctl + 4}};
+    exclusive_scan_multi<2>(ss, ctl + 1, scan_tmp_.as<u64>(), st);
+    EDSX_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    Ftok_ = h[3]; Fcnt_ = h[4];
+    walk_ready_ = true;
+}
+
+void PathPipeline::walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std::vector<u64>& miss, std::vector<u64>& cnt, hipStream_t st)
+{
+    std::vector<u64> len;
+    tables(ids, K, len, miss, st);                               // csid_, the missing counts (and the lengths, not used here)
+    tok.assign(K, 0); cnt.assign(K, 0);
+    const u64 cells = K * nc_;
+    cnt_.ensure(8 * std::max<u64>(K, n_ + 1));
+    u64* cn = cnt_.as<u64>();
+    EDSX_HIP(hipMemsetAsync(cn, 0, 8 * K, st));
+    EventPair es;
+    if (nc_) {
+        tlen_.ensure(8 * (cells + 1));
+        EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &cells, 8, hipMemcpyHostToDevice, st));
+        const EdsView v = eds_.view();
+        EDSX_HIP(hipEventRecord(es.a, st));
+        hipLaunchKernelGGL(k_path_tok, dim3(grid_for(cells, 8192)), dim3(256), 0, st, csid_.as<u64>(), nc_, K, v.elen, seg_rank_.as<u64>(),
+                           tlen_.as<u64>(), cn);
+        exclusive_scan_u64(tlen_.as<u64>(), tlen_.as<u64>(), ctl_.as<u64>(), tlen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
+        EDSX_HIP(hipEventRecord(es.b, st));
+    }
+    hipLaunchKernelGGL(k_path_toktotals, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, tlen_.as<u64>(), nc_, Ftok_, K, tot_.as<u64>());
+    EDSX_HIP(hipMemcpyAsync(tok.data(), tot_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(cnt.data(), cn, 8 * K, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    EDSX_HIP(hipGetLastError());
+    for (u64 k = 0; k < K; k++) cnt[k] += Fcnt_;
+    if (nc_) timing_.scan_ms += es.ms();
+}
+
+void PathPipeline::walks(const u64* ids, size_t n, const char* const* names, const char* prefix, HostBytes& out, u64* missing,
+                         u64* steps, hipStream_t st)
+{
+    check_ids(ids, n);
+    const double tk = timing_.tokenise_ms;
+    timing_ = PathTiming{};
+    timing_.tokenise_ms = tk;
+    out.take(0);
+    if (n == 0) return;
+    // the texts in front of the walks: "P\t<name>\t"
+    std::string blob;
+    std::vector<u64> hoff(n + 1, 0);
+    const std::string pre = prefix ? prefix : "path";
+    for (size_t k = 0; k < n; k++) {
+        const std::string name = names ? std::string(names[k]) : pre + std::to_string(ids[k]);
+        if (name.empty() || name.find_first_of("\t\n ") != std::string::npos)
+            throw ParamError("Path name " + std::to_string(k) + " is not a GFA name");
+        blob += "P\t" + name + "\t";
+        hoff[k + 1] = blob.size();
+    }
+    walk_open(st);
+    const u64 KT = table_batch(n, 24);
+    const bool single = KT >= n;
+    std::vector<u64> tok(n), miss(n), cnt(n), bt, bm, bc;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const u64 K = std::min<u64>(KT, n - i0);
+        walk_tables(ids + i0, K, bt, bm, bc, st);
+        std::memcpy(tok.data() + i0, bt.data(), 8 * K);
+        std::memcpy(miss.data() + i0, bm.data(), 8 * K);
+        std::memcpy(cnt.data() + i0, bc.data(), 8 * K);
+    }
+    if (missing) std::memcpy(missing, miss.data(), 8 * n);
+    if (steps) std::memcpy(steps, cnt.data(), 8 * n);
+    std::vector<PathRec> rec(n);
+    std::vector<u64> host_off(n + 1, 0);                        // line starts in the caller's buffer; a path without a step has none
+    for (size_t k = 0; k < n; k++) {
+        PathRec& r = rec[k];
+        r.L = tok[k]; r.lw = 0;
+        r.body = r.L ? r.L + 2 : 0;
+        r.hdr_src = hoff[k];
+        r.row = k % KT;
+        host_off[k + 1] = host_off[k] + (r.L ? (hoff[k + 1] - hoff[k]) + r.body : 0);
+    }
+    const u64 total = host_off[n];
+    out.take(total);
+    timing_.bytes_written = total;
+    if (total == 0) return;
+    hdr_.ensure(blob.size());
+    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
+    std::vector<PathRec> batch;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const size_t i1 = std::min<size_t>(n, i0 + KT);
+        if (!single) walk_tables(ids + i0, i1 - i0, bt, bm, bc, st);
+        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many lines as the budget holds
+            size_t r1 = r0 + 1;
+            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
+            const u64 bytes = host_off[r1] - host_off[r0];
+            batch.clear();
+            u64 max_body = 0;
+            for (size_t k = r0; k < r1; k++) {
+                if (!rec[k].L) continue;
+                rec[k].rec_off = host_off[k] - host_off[r0];
+                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
+                max_body = std::max(max_body, rec[k].body);
+                batch.push_back(rec[k]);
+            }
+            if (!batch.empty()) {
+                const u64 nrec = batch.size();
+                out_.ensure(bytes + 16);                         // 16 bytes of slack behind the text, as every output buffer here
+                rec_.ensure(sizeof(PathRec) * nrec);
+                EDSX_HIP(hipMemcpyAsync(rec_.ptr, batch.data(), sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
+                const EdsView v = eds_.view();
+                WalkArgs a{gfa::WalkTab{v.sym.ent_off, seg_rank_.as<u64>(), cum_tok_.as<u64>(), rank_.as<u64>(),
+                                        nc_ ? csid_.as<u64>() : nullptr, nc_ ? tlen_.as<u64>() : nullptr, n_, nc_},
+                           rec_.as<PathRec>(), nrec, (max_body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>()};
+                EventPair ev;
+                EDSX_HIP(hipEventRecord(ev.a, st));
+                hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
+                const u64 work = a.max_tiles * nrec;
+                hipLaunchKernelGGL(k_path_walk, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
+                EDSX_HIP(hipEventRecord(ev.b, st));
+                EDSX_HIP(hipStreamSynchronize(st));
+                EDSX_HIP(hipGetLastError());
+                timing_.copy_ms += ev.ms();
+                const auto t0 = std::chrono::steady_clock::now();
+                PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
+                timing_.download_ms += since_ms(t0);
+            }
             r0 = r1;
         }
     }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "eds_device.hpp"
+#include "gfa_device.hpp"
 
 #include <vector>
 
@@ -13,7 +14,8 @@ struct PathInfo {
     bool tokenised_on_device = false;
 };
 
-// of the last lengths() / spell(): device events around the kernels, a host clock around the downloads
+// of the last lengths() / spell() / walks(): device events around the kernels, a host clock around the downloads (walks:
+// scan_ms holds both scans of a batch, copy_ms is k_path_walk)
 struct PathTiming {
     double tokenise_ms = 0, choose_ms = 0, scan_ms = 0, copy_ms = 0, download_ms = 0;
     u64 bytes_written = 0;
@@ -39,9 +41,19 @@ public:
     void spell(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, HostBytes& out,
                u64* missing, hipStream_t st);
 
+    // GFA P lines of the paths in request order: "P\t<name>\t<id>+,<id>+,...\t*\n" over the segment ids (segment_ranks) of
+    // the non-empty chosen strings.  steps[k] (nullable): the ids listed; a path with none gets no line.  names as in spell;
+    // a name that is empty or holds a tab, line feed or blank is a ParamError.
+    void walks(const u64* ids, size_t n, const char* const* names, const char* prefix, HostBytes& out, u64* missing, u64* steps,
+               hipStream_t st);
+
 private:
     void check_ids(const u64* ids, size_t n) const;
-    u64 table_batch(size_t n) const;
+    u64 table_batch(size_t n, u64 cell_bytes = 16) const;
+    // seg_rank and the token bytes of the fixed symbols: made by the first walks() of a session, kept until it closes
+    void walk_open(hipStream_t st);
+    // tables(), then the token bytes of every (path, choice symbol) and their scan; tok / cnt: token bytes and ids per path
+    void walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std::vector<u64>& miss, std::vector<u64>& cnt, hipStream_t st);
     static u64 budget_override();
     // choose + scan for ids[0..K): device tables for the copy kernel, host lengths and missing counts
     void tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st);
@@ -51,6 +63,9 @@ private:
     PathTiming timing_;
     u64 n_ = 0, nc_ = 0, F_ = 0;
     DevBuf cum_fixed_, rank_, cidx_, ctl_, scan_tmp_, ids_, csid_, clen_, tot_, miss_, rec_, hdr_, hoff_, out_;
+    bool walk_ready_ = false;
+    u64 Ftok_ = 0, Fcnt_ = 0;                                    // token bytes / ids of the fixed symbols
+    DevBuf seg_rank_, cum_tok_, tlen_, cnt_;
 };
 
 } // namespace edsx

@@ -85,6 +85,49 @@ void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_o
     }
 }
 
+void eds_to_gfa(std::istream& eds_in, std::istream* seds_in, std::ostream& gfa, const std::vector<int>& paths,
+                const std::vector<std::string>* names, const std::string& prefix, size_t max_links, GfaInfo* info)
+{
+    if (!seds_in && (!paths.empty() || names)) throw std::invalid_argument("eds_to_gfa: paths and names need sources");
+    if (names && (names->size() != paths.size() || paths.empty())) throw std::invalid_argument("eds_to_gfa: one name per requested path");
+    const std::string eds = detail::slurp(eds_in), seds = seds_in ? detail::slurp(*seds_in) : std::string();
+    edsx_ctx* ctx = detail::context();
+    edsx_paths_session* s = nullptr;
+    int rc = EDSX_OK;
+    if (seds_in) {                                               // first: a text that does not match its sources writes nothing
+        rc = edsx_paths_open(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                             reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), &s);
+        if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    }
+    detail::Buf graph, lines;
+    edsx_gfa_info gi;
+    rc = edsx_eds_gfa_graph(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(), max_links, &graph.b, &gi);
+    std::vector<uint64_t> miss, steps;
+    if (rc == EDSX_OK && s) {
+        std::vector<uint64_t> ids;
+        for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));  // (0 is out of range as well)
+        std::vector<const char*> np;
+        if (names) for (const auto& n : *names) np.push_back(n.c_str());
+        edsx_paths_info_t pi;
+        edsx_paths_info(s, &pi);
+        miss.resize(ids.empty() ? pi.num_paths : ids.size());
+        steps.resize(miss.size());
+        rc = edsx_paths_gfa_walks(s, ids.data(), ids.size(), np.empty() ? nullptr : np.data(), prefix.c_str(), &lines.b, miss.data(),
+                                  steps.data());
+    }
+    edsx_paths_close(s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    gfa.write(reinterpret_cast<const char*>(graph.b.data), static_cast<std::streamsize>(graph.b.size));
+    gfa.write(reinterpret_cast<const char*>(lines.b.data), static_cast<std::streamsize>(lines.b.size));
+    if (info) {
+        info->n_symbols = gi.n_symbols; info->n_strings = gi.n_strings; info->n_segments = gi.n_segments;
+        info->n_empty_strings = gi.n_empty_strings; info->n_open_symbols = gi.n_open_symbols; info->n_links = gi.n_links;
+        info->header_bytes = gi.header_bytes; info->segment_bytes = gi.segment_bytes; info->link_bytes = gi.link_bytes;
+        info->missing.assign(miss.begin(), miss.end());
+        info->steps.assign(steps.begin(), steps.end());
+    }
+}
+
 bool is_leds(const EDS& eds, Length context_length)
 {
     if (context_length == 0) return true;

@@ -47,6 +47,20 @@ struct SubsetInfo {
 void eds_subset(std::istream& eds, std::istream& seds, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids = false, SubsetInfo* info = nullptr);
 
+// eds2gfa: the EDS as GFA 1.0 text - header, one S line per non-empty string (ids from 1 in file order), the L lines of
+// adjacent symbols (across symbols that hold an empty string), and, when seds is given, one P line per path of `paths`
+// (empty: all paths 1..P) named (*names)[k], else prefix + id (edsx_eds_gfa_graph / edsx_paths_gfa_walks state the rules
+// in full).  max_links: 0 = 2^32.  std::invalid_argument for a graph of more links, a path outside 1..P, paths or names
+// without sources, or a name that is empty or holds a tab, line feed or blank.
+struct GfaInfo {
+    size_t n_symbols = 0, n_strings = 0, n_segments = 0, n_empty_strings = 0, n_open_symbols = 0, n_links = 0, header_bytes = 0,
+           segment_bytes = 0, link_bytes = 0;
+    std::vector<size_t> missing, steps;        // per requested path (with sources)
+};
+void eds_to_gfa(std::istream& eds, std::istream* seds, std::ostream& gfa, const std::vector<int>& paths = {},
+                const std::vector<std::string>* names = nullptr, const std::string& prefix = "path", size_t max_links = 0,
+                GfaInfo* info = nullptr);
+
 } // namespace edsparser
 
 #endif

@@ -464,7 +464,8 @@ int  edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, ui
  * missing (may be NULL): one count per record. */
 int  edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
                       uint64_t line_width, edsx_buf* fasta, uint64_t* missing);
-/* of the last edsx_paths_lengths / edsx_paths_spell (tokenise_ms: of edsx_paths_open) */
+/* of the last edsx_paths_lengths / edsx_paths_spell / edsx_paths_gfa_walks (tokenise_ms: of edsx_paths_open; walks:
+ * scan_ms holds both scans of a batch, copy_ms the walk kernel, bytes_written the P lines) */
 int  edsx_paths_last_timing(const edsx_paths_session* s, edsx_paths_timing* out);
 void edsx_paths_close(edsx_paths_session* s);
 /* open + spell + close */
@@ -502,8 +503,45 @@ int edsx_eds_subset(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
                     const uint64_t* ids, size_t n, int keep_ids, edsx_buf* eds_out, edsx_buf* seds_out,
                     edsx_subset_info* info);
 
+/* ---- eds2gfa: an EDS and its paths as a GFA 1.0 graph (gfa_device.hip, path_device.hip) ----
+ * The text is, in this order: the header line "H\tVN:Z:1.0", all S lines, all L lines, all P lines; fields are separated
+ * by a tab and every line ends with '\n'.  The .eds (+ .seds) is parsed exactly as edsx_leds_merge / edsx_paths_open
+ * parse it (same tokenisers, statuses and error texts).
+ *   Segments.  "S\t<id>\t<sequence>": every non-empty string of the EDS is one segment, in file order; its id is its
+ *      1-based rank among the non-empty strings, in decimal.  Equal texts are not merged, the bytes are copied verbatim,
+ *      and an empty string is no segment (GFA has no sequence of length 0).
+ *   Links.  "L\t<u>\t+\t<v>\t+\t0M": a symbol is OPEN when it has an empty string.  For i < j every segment of symbol i is
+ *      linked to every segment of symbol j iff every symbol k with i < k < j is open: the links of symbol i reach
+ *      i + 1, i + 2, ... up to and including the first symbol that is not open, or the last symbol.  Lines are ordered
+ *      by (u, v) ascending.  The links follow the language of the EDS, with or without sources: they are not restricted to
+ *      the pairs some path uses.  The sequences spelled by the walks that start at a segment with only open symbols in
+ *      front of it and end at one with only open symbols behind it are the language of the EDS (less the empty word).
+ *   Paths.  "P\t<name>\t<id>+,<id>+,...\t*": the segment ids of the non-empty chosen strings of path p (chosen as
+ *      edsx_paths_spell chooses them) in symbol order.  steps[k] is the number of ids and missing[k] is as in
+ *      edsx_paths_spell; a path with steps == 0 gets no line (GFA has no empty path).  With missing[k] == 0 every
+ *      consecutive pair of the line is a link; with missing[k] > 0 a pair may not be one - the line is written all the
+ *      same.  Names as in edsx_paths_spell: names[k], else prefix (NULL: "path") + id.  A name that is empty or holds a
+ *      tab, line feed or blank: EDSX_ERR_INVALID_PARAMETER, "Path name <k> is not a GFA name" (k: its place in the
+ *      request, from 0).
+ *   Limits.  max_links (0: 2^32) caps the number of links; more is EDSX_ERR_INVALID_PARAMETER, "Graph has <n> links,
+ *      above the limit of <cap>", raised from the counts before the text is allocated (info is filled in): a long run of
+ *      open symbols with many strings each is quadratic by nature.  All offsets and counts are 64-bit; 2^32 strings or
+ *      more are EDSX_ERR_BUILD_FAILED.  An EDS without a non-empty string gives the header line alone.
+ * edsx_eds_gfa_graph tokenises into the context's own tables, like edsx_eds_stats: path sessions are not touched. */
+typedef struct { uint64_t n_symbols, n_strings, n_segments, n_empty_strings, n_open_symbols, n_links,
+                 header_bytes, segment_bytes, link_bytes; int tokenised_on_device; } edsx_gfa_info;
+/* H + S + L; sources are not needed */
+int edsx_eds_gfa_graph(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, uint64_t max_links, edsx_buf* gfa,
+                       edsx_gfa_info* info);
+/* P lines of the requested paths in request order (n == 0: all paths 1..P); missing, steps: may be NULL, one per id */
+int edsx_paths_gfa_walks(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                         edsx_buf* lines, uint64_t* missing, uint64_t* steps);
+/* graph + walks of all paths when seds != NULL, the graph alone otherwise */
+int edsx_eds_gfa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                 uint64_t max_links, const char* prefix, edsx_buf* gfa, edsx_gfa_info* info);
+
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
- * accumulated over all plan/emit calls (and edsx_eds_subset calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
+ * accumulated over all plan/emit calls (and edsx_eds_subset / edsx_eds_gfa_graph calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
  * total_ms[i] / launches[i] is the average duration of kernel names[i].  Returns the entry count. */
 void edsx_set_timing(edsx_ctx* ctx, int enabled);
 int  edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap);
