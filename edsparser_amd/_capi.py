@@ -709,12 +709,21 @@ class Context(_Handle):
 
     # ---- device-resident entry points (pointers are ints: tensor.data_ptr())
     def msa_plan_device(self, d_msa, n, context_len=0, stream=0):
+        """Plan the alignment in the n device bytes at d_msa -> (eds_bytes, seds_bytes).  d_msa may be any byte address;
+        only [d_msa, d_msa + n) is read, and nothing around it needs to be readable.  stream: a hipStream_t as an int
+        (torch: stream.cuda_stream; 0: the default stream); the call waits for that stream (and only it) to hand the
+        sizes back.  The plan stays in the context until the next plan; the input must stay unchanged until the last
+        emit of it has completed."""
         E, Q = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.edsx_msa_plan_device(self._h, d_msa, n, context_len, stream,
                                                    ctypes.byref(E), ctypes.byref(Q)))
         return int(E.value), int(Q.value)
 
     def msa_emit_device(self, d_eds, d_seds, stream=0):
+        """Write the planned .eds / .seds text to device buffers of exactly the planned sizes (any byte address, no
+        slack: every byte of them is written and none outside).  Asynchronous; complete in `stream` order although
+        internal streams take part - a wait for `stream` alone, or later work on it, sees the whole text.  May be
+        repeated after one plan, without waiting in between; after a failed plan it raises (code 3)."""
         self._check(self._lib.edsx_msa_emit_device(self._h, d_eds, d_seds, stream))
 
     def msa_info(self):

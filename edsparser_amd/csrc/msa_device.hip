@@ -598,7 +598,9 @@ void MsaPipeline::emit(uint8_t* d_eds, uint8_t* d_seds, hipStream_t st)
     EDSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_emit_variant<false>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds_));
     auto launch_common = [&](hipStream_t s) {                 // the common segments: "{" reference text "}" and "{0}"
-        TIMED("k_emit_common_seg", s, hipLaunchKernelGGL(k_emit_common_seg, dim3(4096), dim3(256), 0, s, mv_, seg_start_p_, nseg_p_,
+        // (fewer than 12 columns: the instantiation that never loads past the end of the caller's input)
+        auto common_seg = h_.L < 12 ? k_emit_common_seg<true> : k_emit_common_seg<false>;
+        TIMED("k_emit_common_seg", s, hipLaunchKernelGGL(common_seg, dim3(4096), dim3(256), 0, s, mv_, seg_start_p_, nseg_p_,
                                                          eds_len_.as<u64>(), seds_len_.as<u64>(), d_eds, d_seds));
         TIMED("k_emit_common_long", s, hipLaunchKernelGGL(k_emit_common_long, dim3(512), dim3(256), 0, s, mv_, seg_start_p_,
                                                           eds_len_.as<u64>(), seds_len_.as<u64>(), long_list_.as<u64>(),

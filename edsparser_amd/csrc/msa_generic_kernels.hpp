@@ -343,6 +343,8 @@ template <int N> __device__ __forceinline__ void store_small(uint8_t* p, u64 v) 
 }
 __device__ __forceinline__ bool common_is_long(u64 ncol) { return ncol > LONG_COMMON; }
 
+// SHORT: an alignment of fewer than 12 columns, whose file may end less than 16 bytes behind a run of row 0 (see below).
+template <bool SHORT>
 __global__ void __launch_bounds__(256) k_emit_common_seg(MsaView mv, const u64* __restrict__ seg_start, const u64* __restrict__ nseg_ptr,
                                                          const u64* __restrict__ eds_off, const u64* __restrict__ seds_off,
                                                          uint8_t* __restrict__ eds, uint8_t* __restrict__ seds)
@@ -363,9 +365,11 @@ __global__ void __launch_bounds__(256) k_emit_common_seg(MsaView mv, const u64* 
                 store16u(e + 1 + oo, load16u(row0 + a + oo));
             }
         } else if (mv.lw == 0) {
-            // "{" + up to 15 letters: one 16-byte load (row 0 is followed by more of the file: never past its end), then
-            // the clen + 1 bytes as 16 / 8 + 4 + 2 + 1 byte stores
-            const uint4 v = load16u(row0 + a);
+            // "{" + up to 15 letters: one 16-byte load, then the clen + 1 bytes as 16 / 8 + 4 + 2 + 1 byte stores.  Behind
+            // row 0 the file holds at least "\n>\n" and a second row of L columns, 2 L + 3 bytes from the row's start: the
+            // load at a <= L - 1 stays inside the caller's buffer when L >= 12.  Shorter alignments (SHORT, chosen by the
+            // host) read the clen bytes alone.
+            const uint4 v = SHORT ? load_partial(row0 + a, (int)clen) : load16u(row0 + a);
             u64 lo = ((u64)v.y << 32) | v.x, hi = ((u64)v.w << 32) | v.z;
             hi = (hi << 8) | (lo >> 56); lo = (lo << 8) | (u64)'{';
             const u32 m = (u32)clen + 1u;

@@ -258,8 +258,8 @@ void msa_image_to_text(MsaPipeline& p, const DevBuf& d_img, size_t n, uint32_t l
 {
     uint64_t E = 0, Q = 0;
     p.plan(d_img.as<uint8_t>(), n, l, st, &E, &Q);
-    d_eds.ensure(E + 16);
-    d_seds.ensure(Q + 16);
+    d_eds.ensure(E);
+    d_seds.ensure(Q);
     p.emit(d_eds.as<uint8_t>(), d_seds.as<uint8_t>(), st);
     eds.take(E);
     seds.take(Q);
@@ -369,7 +369,7 @@ void MultiMsa::run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& 
             const uint8_t* img = me.d_img.as<uint8_t>();
             const u64 img_bytes = ri.bytes;
             me.slab.plan(img, img_bytes, 0, st, &E, &Q);
-            me.d_eds.ensure(E + 16); me.d_seds.ensure(Q + 16);
+            me.d_eds.ensure(E); me.d_seds.ensure(Q);
             me.slab.emit(me.d_eds.as<uint8_t>(), me.d_seds.as<uint8_t>(), st);
             const MsaPipeline::Edges e = me.slab.edge_info(st);
             mine = SlabEdges{e.nseg, ncols, E, Q, e.fvar, e.fcols, e.feds, e.fseds, e.lvar, e.lcols, e.leds, e.lseds};
@@ -427,7 +427,7 @@ void MultiMsa::run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& 
                     uint64_t e2 = 0, q2 = 0;
                     me.mini.plan(me.d_mini.as<uint8_t>(), mini.size(), 0, st, &e2, &q2);
                     DevBuf oe, oq;
-                    oe.ensure(e2 + 16); oq.ensure(q2 + 16);
+                    oe.ensure(e2); oq.ensure(q2);
                     me.mini.emit(oe.as<uint8_t>(), oq.as<uint8_t>(), st);
                     const size_t pe = extra_e.size(), pq = extra_s.size();
                     extra_e.resize(pe + e2); extra_s.resize(pq + q2);
@@ -516,7 +516,7 @@ void MultiMsa::run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, 
             EDSX_HIP(hipSetDevice(me.device));
             const RowImage ri = upload_row_image(fasta, lay, c0, c1, me.d_img, me.host_img, st);
             me.slab.plan(me.d_img.as<uint8_t>(), ri.bytes, l, st, &E, &Q);
-            me.d_eds.ensure(E + 16); me.d_seds.ensure(Q + 16);
+            me.d_eds.ensure(E); me.d_seds.ensure(Q);
             me.slab.emit(me.d_eds.as<uint8_t>(), me.d_seds.as<uint8_t>(), st);
             const MsaPipeline::Anchors a = me.slab.anchor_info(l, st);
             mine.cols = ncols; mine.eds_bytes = E; mine.seds_bytes = Q;
@@ -568,7 +568,7 @@ void MultiMsa::run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, 
                 uint64_t e2 = 0, q2 = 0;
                 me.mini.plan(me.d_mini.as<uint8_t>(), mini.size(), l, st, &e2, &q2);
                 DevBuf oe, oq;
-                oe.ensure(e2 + 16); oq.ensure(q2 + 16);
+                oe.ensure(e2); oq.ensure(q2);
                 me.mini.emit(oe.as<uint8_t>(), oq.as<uint8_t>(), st);
                 extra_e.resize(e2); extra_s.resize(q2);
                 EDSX_HIP(hipMemcpyAsync(extra_e.data(), oe.ptr, e2, hipMemcpyDeviceToHost, st));
@@ -645,7 +645,7 @@ bool msa_transform_batched(const BatchResources& R, const uint8_t* fasta, const 
         const RowImage ri = upload_row_image(fasta, lay, c0[r], c0[r + 1], *R.d_img, *R.host_tmp, st);
         uint64_t E = 0, Q = 0;
         R.slab->plan(R.d_img->as<uint8_t>(), ri.bytes, l, st, &E, &Q);
-        R.d_eds->ensure(E + 16); R.d_seds->ensure(Q + 16);
+        R.d_eds->ensure(E); R.d_seds->ensure(Q);
         R.slab->emit(R.d_eds->as<uint8_t>(), R.d_seds->as<uint8_t>(), st);
         if (l == 0) {
             const MsaPipeline::Edges e = R.slab->edge_info(st);
@@ -681,7 +681,7 @@ bool msa_transform_batched(const BatchResources& R, const uint8_t* fasta, const 
         uint64_t e2 = 0, q2 = 0;
         R.mini->plan(R.d_mini->as<uint8_t>(), mini.size(), l, st, &e2, &q2);
         DevBuf oe, oq;
-        oe.ensure(e2 + 16); oq.ensure(q2 + 16);
+        oe.ensure(e2); oq.ensure(q2);
         R.mini->emit(oe.as<uint8_t>(), oq.as<uint8_t>(), st);
         const size_t a = xe[owner].size(), b = xs[owner].size();
         xe[owner].resize(a + e2); xs[owner].resize(b + q2);

@@ -328,15 +328,31 @@ int edsx_genrandomeds(edsx_ctx* ctx, uint64_t total_bp, double variability, uint
                       uint32_t var_len_max, double snp_ratio, const char* alphabet, uint64_t min_context, uint64_t seed,
                       edsx_buf* eds, edsx_buf* seds, uint64_t* n_sites);
 
-/* ---- device-resident MSA path (inputs/outputs stay in HBM) ---- */
+/* ---- device-resident MSA path (inputs/outputs stay in HBM) ----
+ * The two calls below read and write memory the caller owns, on a stream the caller chooses (a hipStream_t; null: the
+ * default stream).  What they promise (pinned by tests/test_msa_resident_gpu.py on buffers between guard zones, except
+ * that a test cannot see a load whose value is discarded: that no byte outside the input is even loaded was established
+ * by reading the kernels):
+ *   - Pointers: any byte address.  No alignment is assumed for d_msa, d_eds or d_seds.
+ *   - Input: exactly the bytes [d_msa, d_msa + msa_size) are read.  Nothing in front of or behind them needs to be
+ *     readable, and no result or error text depends on what lies there.
+ *   - Outputs: exactly eds_bytes and seds_bytes bytes are written, every one of them, and none outside: buffers of
+ *     exactly the planned sizes are enough (no slack).
+ *   - Stream order: all work is ordered on `stream`.  emit also runs kernels on streams of its own, which it forks from
+ *     and joins back into `stream`: whatever the caller enqueues on `stream` after emit, or a wait for `stream` alone,
+ *     sees the complete outputs.  Work the caller has on OTHER streams is not waited for.
+ *   - The plan lives in the context until the next plan: emit may be called any number of times after one successful
+ *     plan (into the same or other buffers, on the same stream), without waiting in between.  A plan that fails leaves
+ *     the context without a plan: emit then returns EDSX_ERR_INVALID_PARAMETER. */
 
 /* Phase 1: index rows, scan columns, build the segment table and size the outputs.
- * d_msa must stay valid until the matching edsx_msa_emit_device returns.  Synchronises the
- * stream once to hand the sizes back. */
+ * d_msa must stay valid and unchanged until the last edsx_msa_emit_device of this plan has completed.  Synchronises
+ * `stream` (and only it) to hand the sizes back: once for the row index and once for the sizes, once more when the
+ * variant-column store had to grow.  Format errors are EDSX_ERR_INVALID_FORMAT with their text in edsx_last_error. */
 int edsx_msa_plan_device(edsx_ctx* ctx, const uint8_t* d_msa, size_t msa_size, uint32_t context_len,
                          void* stream, uint64_t* eds_bytes, uint64_t* seds_bytes);
-/* Phase 2: write the .eds / .seds text into caller-provided HBM buffers of at least the planned
- * sizes.  Asynchronous on `stream`. */
+/* Phase 2: write the .eds / .seds text into caller-provided HBM buffers of the planned sizes (d_eds and d_seds must not
+ * overlap).  Asynchronous: returns once the work is enqueued; complete in `stream` order. */
 int edsx_msa_emit_device(edsx_ctx* ctx, uint8_t* d_eds, uint8_t* d_seds, void* stream);
 
 /* Geometry of the last planned alignment (for reporting). */
@@ -557,7 +573,9 @@ int edsx_genvcf(edsx_ctx* ctx, uint64_t ref_len, uint64_t n_records, uint32_t n_
 /* ---- synthetic genrandomeds-shaped alignment, generated in HBM (bench / tests) ----
  * Rows 0..n_rows-1 of alignment columns [col0, col0+n_cols) of a virtual alignment, one line per
  * row, headers ">s<row>", trailing newline.  Bytes depend only on (seed, global column, row), so a
- * column slab generated on another GPU is bit-identical to the same columns of the whole. */
+ * column slab generated on another GPU is bit-identical to the same columns of the whole.
+ * Both generators write exactly the bytes [d_out, d_out + size) - every one of them, none outside, d_out at any byte
+ * address - asynchronously on `stream`; a capacity below the size is EDSX_ERR_INVALID_PARAMETER and writes nothing. */
 size_t edsx_msa_synth_size(uint32_t n_rows, uint64_t n_cols);
 int edsx_msa_synth_device(edsx_ctx* ctx, uint8_t* d_out, size_t capacity, uint32_t n_rows,
                           uint64_t col0, uint64_t n_cols, double variant_fraction, uint64_t seed,

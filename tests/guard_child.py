@@ -183,8 +183,8 @@ def msa():
 
     def resident(ctx):
         E, Q = ctx.msa_plan_device(buf.data_ptr(), n, 0)
-        d_eds = torch.empty(E + 16, dtype=torch.uint8, device="cuda:0")
-        d_seds = torch.empty(Q + 16, dtype=torch.uint8, device="cuda:0")
+        d_eds = torch.empty(E, dtype=torch.uint8, device="cuda:0")
+        d_seds = torch.empty(Q, dtype=torch.uint8, device="cuda:0")
         ctx.msa_emit_device(d_eds.data_ptr(), d_seds.data_ptr())
         torch.cuda.synchronize()
         return bytes(d_eds[:E].cpu().numpy()), bytes(d_seds[:Q].cpu().numpy())

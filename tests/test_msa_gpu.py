@@ -118,8 +118,8 @@ def test_synthetic_device_path(ctx, S, L, l):
     buf = torch.empty(n, dtype=torch.uint8, device="cuda:0")
     ctx.msa_synth_device(buf.data_ptr(), n, S, L, seed=42 + S)
     E, Q = ctx.msa_plan_device(buf.data_ptr(), n, l)
-    d_eds = torch.empty(E + 16, dtype=torch.uint8, device="cuda:0")
-    d_seds = torch.empty(Q + 16, dtype=torch.uint8, device="cuda:0")
+    d_eds = torch.empty(E, dtype=torch.uint8, device="cuda:0")
+    d_seds = torch.empty(Q, dtype=torch.uint8, device="cuda:0")
     ctx.msa_emit_device(d_eds.data_ptr(), d_seds.data_ptr())
     torch.cuda.synchronize()
     host = bytes(buf.cpu().numpy())
@@ -284,8 +284,8 @@ def test_host_buffer_path_large_outputs_equal_device_path(ctx, L):
     buf = torch.empty(n, dtype=torch.uint8, device="cuda:0")
     ctx.msa_synth_device(buf.data_ptr(), n, S, L, seed=L)
     E, Q = ctx.msa_plan_device(buf.data_ptr(), n, 0)
-    d_eds = torch.empty(E + 16, dtype=torch.uint8, device="cuda:0")
-    d_seds = torch.empty(Q + 16, dtype=torch.uint8, device="cuda:0")
+    d_eds = torch.empty(E, dtype=torch.uint8, device="cuda:0")
+    d_seds = torch.empty(Q, dtype=torch.uint8, device="cuda:0")
     ctx.msa_emit_device(d_eds.data_ptr(), d_seds.data_ptr())
     torch.cuda.synchronize()
     assert Q >= 16 << 20
@@ -411,8 +411,8 @@ def test_dense_variant_columns_grow_the_column_store(ctx, S, L, vf):
     fresh = edsparser_amd.Context(0)                       # a context whose buffers have not grown yet
     fresh.msa_synth_device(buf.data_ptr(), n, S, L, variant_fraction=vf, seed=7)
     E, Q = fresh.msa_plan_device(buf.data_ptr(), n, 0)
-    d_eds = torch.empty(E + 16, dtype=torch.uint8, device="cuda:0")
-    d_seds = torch.empty(Q + 16, dtype=torch.uint8, device="cuda:0")
+    d_eds = torch.empty(E, dtype=torch.uint8, device="cuda:0")
+    d_seds = torch.empty(Q, dtype=torch.uint8, device="cuda:0")
     fresh.msa_emit_device(d_eds.data_ptr(), d_seds.data_ptr())
     torch.cuda.synchronize()
     oe, os_ = o.msa(bytes(buf.cpu().numpy()), 0)
