@@ -43,7 +43,8 @@ void launch_scan_extract(const K1Params& p, int threads, bool hold, bool lane_ro
     if (lane_rows && rows64) launch_k1<512, 16, true, true, 4, true>(p, lds, st);    // one row per lane in the fused grouping
     else if (lane_rows && threads == 1024) launch_k1<1024, 16, true, true, 4>(p, lds, st);
     else if (lane_rows) launch_k1<512, 16, true, true, 4>(p, lds, st);
-    else if (hold) launch_k1<512, 16, true, false, 4>(p, lds, st);
+    // (held rows are always lane rows - the host keeps sixteen chunks per thread, so `hold` alone never comes and no
+    // instantiation is built for it; it would take the row loop below, which is right for any row count)
     else if (big) launch_k1<512, 16, false, false, 4, false, true>(p, lds, st);
     else launch_k1<512, 16, false, false, 4>(p, lds, st);
 }

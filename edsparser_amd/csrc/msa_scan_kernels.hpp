@@ -412,8 +412,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
             for (int i = 0; i < 8; i++) { d[2 * i] = load16u(f + rv[i].x + q); d[2 * i + 1] = load16u(f + rv[i].y + q); }
 #pragma unroll
             for (int it = 0; it < RPT; it++) {
-                acc.x |= d[it].x ^ ref.x; acc.y |= d[it].y ^ ref.y;
-                acc.z |= d[it].z ^ ref.z; acc.w |= d[it].w ^ ref.w;
+                acc_or_xor(acc, d[it], ref);
             }
         }
     } else if (full_tile) {                                    // non-zero iff some row differs there
@@ -423,14 +422,13 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
             const u32 r = row_of(it);
             d[HOLD ? it : 0] = load16u(f + rs[r < p.S ? r : Sm1] + q);   // clamped: rows past S re-read row S-1
             if constexpr (!HOLD) {
-                acc.x |= d[0].x ^ ref.x; acc.y |= d[0].y ^ ref.y; acc.z |= d[0].z ^ ref.z; acc.w |= d[0].w ^ ref.w;
+                acc_or_xor(acc, d[0], ref);
             }
         }
         if constexpr (HOLD) {
 #pragma unroll
             for (int it = 0; it < RPT; it++) {                 // a clamped duplicate changes nothing
-                acc.x |= d[it].x ^ ref.x; acc.y |= d[it].y ^ ref.y;
-                acc.z |= d[it].z ^ ref.z; acc.w |= d[it].w ^ ref.w;
+                acc_or_xor(acc, d[it], ref);
             }
         }
     } else {
@@ -441,7 +439,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
             uint4 v = ref;
             if (r < p.S && nb > 0) v = load_partial(f + rs[r] + q, nb);
             d[HOLD ? it : 0] = v;
-            acc.x |= v.x ^ ref.x; acc.y |= v.y ^ ref.y; acc.z |= v.z ^ ref.z; acc.w |= v.w ^ ref.w;
+            acc_or_xor(acc, v, ref);
         }
     }
     if constexpr (!HOLD) {                                     // S beyond the register budget
@@ -449,7 +447,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
             if (nb > 0) {
                 const uint8_t* src = f + rs[r] + q;
                 uint4 v = nb == 16 ? load16u(src) : load_partial(src, nb);
-                acc.x |= v.x ^ ref.x; acc.y |= v.y ^ ref.y; acc.z |= v.z ^ ref.z; acc.w |= v.w ^ ref.w;
+                acc_or_xor(acc, v, ref);
             }
         }
     }
@@ -498,15 +496,32 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
         w0 = wtot[0]; w1 = wtot[1]; w2 = wtot[2]; w3 = wtot[3];
         nv = w0 + w1 + w2 + w3;
     }
-    // (the slot atomic is issued now and its result is first needed after the extraction into LDS, which hides
-    // its ~1 us round trip)
+    // The slot atomic is issued now, from one lane, and its result is first looked at by publish_slot() behind the
+    // extraction into LDS and the run registration, which hide its 1 - 3 us round trip.  Two things keep it that way in
+    // the compiled code.  The counter is addressed through an offset the compiler cannot see through (a VGPR that holds
+    // 0): with an address it knows to be uniform the atomic optimiser rewrites the add as a wave reduction whose
+    // v_readfirstlane consumes the result at once.  And publish_slot() takes the result through an empty asm, or the
+    // overflow test base_r + nv > vc_cap_cols is hoisted in front of the extraction and the wait with it.
+    // (This rests on what the compiler does today, not on a guarantee: after a toolchain change, run the command in
+    // profiles/r04_scan_isa.md again and look for the s_waitcnt vmcnt(0) behind the registration loop.)
     auto pre_of = [&](u32 chunk) -> u32 {
         if (fastpre) return (u32)(prepk >> (8u * (chunk & 7u))) & 0xffu;
         const u32 cw = chunk >> 6;
         return pre[chunk] + (cw > 0 ? w0 : 0u) + (cw > 1 ? w1 : 0u) + (cw > 2 ? w2 : 0u);
     };
     u64 base_r = 0;
-    if (tid == 0 && nv) base_r = atomicAdd(&p.hdr->nv, (u64)nv);
+    if (tid == 0 && nv) {
+        u32 zero = 0;
+        asm volatile("" : "+v"(zero));
+        base_r = atomicAdd(&p.hdr->nv + zero, (u64)nv);
+    }
+    auto publish_slot = [&]() {                                // thread 0: first use of the atomic's result
+        u32 lo = (u32)base_r, hi = (u32)(base_r >> 32);
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        const u64 b = ((u64)hi << 32) | lo;
+        slot_base_sh = b;
+        if (b + nv > p.vc_cap_cols) atomicOr(&p.hdr->status, (u64)ST_VC_OVERFLOW);
+    };
 
     // extraction: variant bytes -> LDS (column-major) -> HBM, in batches of cap_cols columns
     u64 slot_base = 0;
@@ -564,10 +579,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
                     else if (dn == 0) { clist[atomicAdd(&ncand_sh, 1u)] = (uint16_t)(idx | ((up + dn) << 11)); atomicOr(&CS[ch], 1u << b); }
                 }
             }
-            if (tid == 0) {                                    // first use of the atomic's result
-                slot_base_sh = base_r;
-                if (base_r + nv > p.vc_cap_cols) atomicOr(&p.hdr->status, (u64)ST_VC_OVERFLOW);
-            }
+            if (tid == 0) publish_slot();
             __syncthreads();
             slot_base = slot_base_sh;
             overflow = slot_base + nv > p.vc_cap_cols;
@@ -607,10 +619,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
                     fused_group_run<ROWS64>(p, colbuf, uniform32((u32)clist[ci]), slot_base, lane, vmask, nl, loff);
             }
         } } else if constexpr (BIG) {
-            if (tid == 0) {
-                slot_base_sh = base_r;
-                if (base_r + nv > p.vc_cap_cols) atomicOr(&p.hdr->status, (u64)ST_VC_OVERFLOW);
-            }
+            if (tid == 0) publish_slot();
             __syncthreads();
             slot_base = slot_base_sh;
             overflow = slot_base + nv > p.vc_cap_cols;
@@ -713,10 +722,7 @@ __global__ void __launch_bounds__(T, MINW) k_scan_extract(K1Params p)
                     }
                 }
             }
-            if (b0 == 0 && tid == 0) {                         // first use of the atomic's result
-                slot_base_sh = base_r;
-                if (base_r + nv > p.vc_cap_cols) atomicOr(&p.hdr->status, (u64)ST_VC_OVERFLOW);
-            }
+            if (b0 == 0 && tid == 0) publish_slot();
             __syncthreads();
             if (b0 == 0) {
                 slot_base = slot_base_sh;

@@ -36,6 +36,16 @@ __device__ __forceinline__ u32 chunk_ne16(const uint4& a, const uint4& b)
     return ne_bytes4(a.x, b.x) | (ne_bytes4(a.y, b.y) << 4) | (ne_bytes4(a.z, b.z) << 8) |
            (ne_bytes4(a.w, b.w) << 12);
 }
+// acc |= row ^ ref, one v_bitop3_b32 per dword.  Bit (a << 2 | b << 1 | c) of the instruction's truth table is its
+// result for the input bits a, b, c, so the tables of the three operands themselves are 0xF0, 0xCC and 0xAA and the
+// table of a | (b ^ c) is the same expression over them: 0xF0 | (0xCC ^ 0xAA) = 0xF6.
+__device__ __forceinline__ void acc_or_xor(uint4& acc, const uint4& row, const uint4& ref)
+{
+    constexpr uint32_t TA = 0xF0u, TB = 0xCCu, TC = 0xAAu, TT = TA | (TB ^ TC);
+    static_assert(TT == 0xF6u, "a | (b ^ c)");
+    acc.x = __builtin_amdgcn_bitop3_b32(acc.x, row.x, ref.x, TT); acc.y = __builtin_amdgcn_bitop3_b32(acc.y, row.y, ref.y, TT);
+    acc.z = __builtin_amdgcn_bitop3_b32(acc.z, row.z, ref.z, TT); acc.w = __builtin_amdgcn_bitop3_b32(acc.w, row.w, ref.w, TT);
+}
 __device__ __forceinline__ u32 chunk_eq16(const uint4& a, uint32_t cccc)
 {
     return eq_byte4(a.x, cccc) | (eq_byte4(a.y, cccc) << 4) | (eq_byte4(a.z, cccc) << 8) |
