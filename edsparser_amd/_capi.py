@@ -98,6 +98,19 @@ class GfaInfo(ctypes.Structure):
                [("tokenised_on_device", ctypes.c_int)]
 
 
+class VcfExportOpts(ctypes.Structure):
+    """edsx_vcf_export_opts"""
+    _fields_ = [("chrom", ctypes.c_char_p), ("ref_path", ctypes.c_uint64), ("names", ctypes.POINTER(ctypes.c_char_p)),
+                ("n_names", ctypes.c_size_t), ("prefix", ctypes.c_char_p), ("line_width", ctypes.c_uint64),
+                ("max_bytes", ctypes.c_uint64)]
+
+
+class VcfExportInfo(ctypes.Structure):
+    """edsx_vcf_export_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("symbols", "strings", "paths", "records", "anchored", "overlapping", "ref_length",
+                                                "header_bytes", "body_bytes")] + [("tokenised_on_device", ctypes.c_int)]
+
+
 class MsaInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("n_rows", "n_cols", "line_width", "n_variant_cols", "n_segments", "msa_bytes",
@@ -253,6 +266,8 @@ def load_library():
                                          P(_Buf), ctypes.c_void_p, ctypes.c_void_p]
     lib.edsx_eds_gfa.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64,
                                  ctypes.c_char_p, P(_Buf), P(GfaInfo)]
+    lib.edsx_eds_vcf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                 P(VcfExportOpts), P(_Buf), P(_Buf), P(VcfExportInfo)]
     _LIB = lib
     return lib
 
@@ -637,6 +652,23 @@ class Context(_Handle):
                                            prefix.encode() if prefix is not None else None, ctypes.byref(g), ctypes.byref(info)))
         del keep
         return self._take(g), _fields(info, flags=("tokenised_on_device",))
+
+    # ---- VCF export (eds2vcf)
+    def eds_vcf(self, eds, seds=None, chrom=None, ref_path=0, names=None, prefix=None, line_width=60, max_bytes=0):
+        """The EDS as VCF 4.2 text - one record per symbol with two strings or more, with seds one genotype column per
+        path - and the reference FASTA its positions refer to (edsx_eds_vcf) -> (vcf bytes, fasta bytes, info dict).
+        ref_path: 0 = the first string of every symbol is REF, p = the string path p takes; names: one per path 1..P."""
+        enc = lambda x: None if x is None else (x.encode() if isinstance(x, str) else bytes(x))
+        opts = VcfExportOpts(enc(chrom), int(ref_path), None, 0, enc(prefix), int(line_width), int(max_bytes))
+        if names is not None:
+            arr = (ctypes.c_char_p * max(len(names), 1))(*[enc(x) for x in names])
+            opts.names, opts.n_names = arr, len(names)
+        v, f, info = _Buf(), _Buf(), VcfExportInfo()
+        ptr, n, keep = _input(eds)
+        self._check(self._lib.edsx_eds_vcf(self._h, ptr, n, *_opt(seds), ctypes.byref(opts), ctypes.byref(v), ctypes.byref(f),
+                                           ctypes.byref(info)))
+        del keep
+        return self._take(v), self._take(f), _fields(info, flags=("tokenised_on_device",))
 
     def vcf_tokenised_on_device(self):
         return bool(self._lib.edsx_vcf_tokenised_on_device(self._h))

@@ -26,6 +26,7 @@
 #include "synth.hpp"
 #include "vcf_contig.hpp"
 #include "vcf_device.hpp"
+#include "vcf_export_device.hpp"
 
 #include <cstddef>
 #include <cstdlib>
@@ -49,6 +50,7 @@ struct edsx_ctx {
     LocatePipeline locate;                   // edsx_eds_locate, over query's tables
     SubsetPipeline subset;                   // edsx_eds_subset
     GfaPipeline gfa;                         // edsx_eds_gfa_graph
+    VcfExportPipeline vcf_export;            // edsx_eds_vcf
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -414,13 +416,15 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->msa.set_timing(enabled != 0);
     ctx->subset.set_timing(enabled != 0);
     ctx->gfa.set_timing(enabled != 0);
+    ctx->vcf_export.set_timing(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
     if (!ctx) return 0;
     int n = ctx->msa.get_timing(names, total_ms, launches, cap);
     n += ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1029,6 +1033,37 @@ int edsx_eds_gfa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8
         edsx_buf_free(&graph);
         edsx_buf_free(&lines);
         return rc;
+    });
+}
+
+// ---- eds2vcf (vcf_export_device.hip)
+int edsx_eds_vcf(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                 const edsx_vcf_export_opts* opts, edsx_buf* vcf, edsx_buf* ref_fasta, edsx_vcf_export_info* info)
+{
+    clear(vcf, ref_fasta);
+    zero(info);
+    return guarded(ctx, [&] {
+        if (!vcf || (!eds && eds_size) || (opts && opts->n_names && !opts->names)) throw ParamError("null argument");
+        static_assert(offsetof(edsx_vcf_export_info, tokenised_on_device) == sizeof(VcfExportInfo),
+                      "edsx_vcf_export_info begins with VcfExportInfo");
+        VcfExportOpts o;
+        if (opts) {
+            if (opts->chrom) o.chrom = opts->chrom;
+            if (opts->prefix) o.prefix = opts->prefix;
+            o.ref_path = opts->ref_path; o.line_width = opts->line_width; o.max_bytes = opts->max_bytes;
+            o.names = opts->names; o.n_names = opts->names ? opts->n_names : 0;
+            for (size_t k = 0; k < o.n_names; k++) if (!o.names[k]) throw ParamError("null argument");
+        }
+        HostBytes v, f;
+        VcfExportInfo vi;
+        auto put_info = [&] {
+            if (info) { std::memcpy(info, &vi, sizeof(vi)); info->tokenised_on_device = ctx->eds.tokenised_on_device() ? 1 : 0; }
+        };
+        try { ctx->vcf_export.run(ctx->eds, or_empty(eds), eds_size, seds, seds_size, o, v, ref_fasta ? &f : nullptr, vi, nullptr); }
+        catch (const LimitError&) { put_info(); throw; }         // the byte limit: the counts are known
+        put_info();
+        give(vcf, v);
+        if (ref_fasta) give(ref_fasta, f);
     });
 }
 

@@ -556,8 +556,59 @@ int edsx_paths_gfa_walks(edsx_paths_session* s, const uint64_t* ids, size_t n, c
 int edsx_eds_gfa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                  uint64_t max_links, const char* prefix, edsx_buf* gfa, edsx_gfa_info* info);
 
+/* ---- eds2vcf: an EDS and its sources as VCF 4.2 text plus the reference FASTA (vcf_export_device.hip) ----
+ * The .eds (+ .seds) is parsed exactly as edsx_eds_gfa / edsx_paths_open parse it (same tokenisers, statuses and error
+ * texts).  n symbols, numbered from 0; P is the largest path id in the .seds.
+ *   Reference allele of symbol i.  ref_path == 0: the first string in file order (where vcf2eds puts REF).  ref_path ==
+ *      p >= 1: the string path p takes under the rule of edsx_paths_spell, the first string whose set holds p or 0; a
+ *      symbol where p takes none is EDSX_ERR_INVALID_PARAMETER, "Path <p> takes no string of symbol <i>" (the first such
+ *      i).  p > P: EDSX_ERR_INVALID_PARAMETER, "Path id <p> out of range (1..<P>)"; p without a .seds:
+ *      EDSX_ERR_INVALID_PARAMETER, "A reference path needs sources (.seds)".
+ *   Reference sequence.  The reference strings end to end, length L; refpos[i] is the sum of their lengths before i.
+ *   Records.  One per symbol with two strings or more, in symbol order; a one-string symbol gives none.  Allele 0 is the
+ *      reference string, the other strings follow in file order as alleles 1..k-1.  Equal texts are not merged and
+ *      nothing is trimmed, as in eds2gfa.
+ *   Anchor.  A record with an empty string is anchored.  If refpos[i] > 0 every allele gets the reference base at 0-based
+ *      refpos[i] - 1 in front, and POS = refpos[i].  Otherwise every allele gets, behind it, the reference base that follows
+ *      the symbol's reference string, and POS = 1; when there is no such base (the reference ends with this symbol's
+ *      reference string) the call is EDSX_ERR_INVALID_FORMAT, "Symbol <i> has an empty string and no reference base to
+ *      anchor it".  A record without an empty string: POS = refpos[i] + 1, alleles verbatim.
+ *   Line.  CHROM \t POS \t . \t REF \t ALT1,ALT2,... \t . \t . \t .   and, with sources, \t GT and one cell per path 1..P,
+ *      each behind a tab.  The cell of path p holds the numbers of the alleles whose set holds p or 0, ascending, joined
+ *      by '/' (an .seds has no phase); no allele at all gives ".".
+ *   Header.  "##fileformat=VCFv4.2", "##source=eds2vcf", "##contig=<ID=<chrom>,length=<L>>", with sources
+ *      "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">", then the tab-separated "#CHROM POS ID REF ALT QUAL
+ *      FILTER INFO" line, with sources followed by FORMAT and the sample names: names[k] for path k + 1 when names is
+ *      given (n_names must be P: "Expected <P> sample names, got <n>"), else prefix (NULL: "path") + id, as
+ *      edsx_paths_spell names its records.  A name that is empty or holds a tab or line feed: "Sample name <k> is not a
+ *      VCF sample name".  chrom NULL: "eds"; empty or holding whitespace: "Chromosome name is empty or holds whitespace".
+ *      All three are EDSX_ERR_INVALID_PARAMETER.
+ *   Reference FASTA (ref_fasta may be NULL).  ">" chrom "\n", then the reference sequence in lines of line_width
+ *      characters, each ended by '\n' (0: one line; an empty sequence has no line): for ref_path = p the body edsx_paths_spell
+ *      gives for p.
+ *   info (may be NULL).  anchored: records with an anchor base.  overlapping: records whose POS is not behind the last
+ *      reference base of the record before them, which anchoring next to another degenerate symbol can cause.
+ *   max_bytes.  0: no limit beyond what can be allocated.  The body (all record lines) is sized exactly from scanned counts
+ *      before it is allocated; a body above the limit is EDSX_ERR_BUILD_FAILED, "VCF body of <n> bytes is above the limit
+ *      of <max>", with info filled in.  There is no path selection: edsx_eds_subset does that and renumbers densely.
+ * opts == NULL: all defaults (line_width 60).  A zeroed opts differs from that only in line_width 0.
+ * The call tokenises into the context's own tables, like edsx_eds_stats: path sessions are not touched. */
+typedef struct {
+    const char* chrom;              /* NULL: "eds" */
+    uint64_t ref_path;              /* 0: the first string of every symbol */
+    const char* const* names;       /* NULL, or n_names sample names */
+    size_t n_names;
+    const char* prefix;             /* NULL: "path" */
+    uint64_t line_width;            /* of the reference FASTA; 0: one line */
+    uint64_t max_bytes;             /* 0: no limit */
+} edsx_vcf_export_opts;
+typedef struct { uint64_t symbols, strings, paths, records, anchored, overlapping, ref_length, header_bytes, body_bytes;
+                 int tokenised_on_device; } edsx_vcf_export_info;
+int edsx_eds_vcf(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                 const edsx_vcf_export_opts* opts, edsx_buf* vcf, edsx_buf* ref_fasta, edsx_vcf_export_info* info);
+
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
- * accumulated over all plan/emit calls (and edsx_eds_subset / edsx_eds_gfa_graph calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
+ * accumulated over all plan/emit calls (and edsx_eds_subset / edsx_eds_gfa_graph / edsx_eds_vcf calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
  * total_ms[i] / launches[i] is the average duration of kernel names[i].  Returns the entry count. */
 void edsx_set_timing(edsx_ctx* ctx, int enabled);
 int  edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap);
