@@ -86,6 +86,11 @@ class PathsTiming(ctypes.Structure):
                [("bytes_written", ctypes.c_uint64)]
 
 
+class AlignInfo(ctypes.Structure):
+    """edsx_align_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_symbols", "n_columns", "n_zero_width_symbols", "widest_symbol", "num_paths")]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -268,6 +273,12 @@ def load_library():
                                  ctypes.c_char_p, P(_Buf), P(GfaInfo)]
     lib.edsx_eds_vcf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                  P(VcfExportOpts), P(_Buf), P(_Buf), P(VcfExportInfo)]
+    lib.edsx_paths_align_info.argtypes = [ctypes.c_void_p, P(AlignInfo)]
+    lib.edsx_paths_align.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p,
+                                     ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, P(_Buf), ctypes.c_void_p]
+    lib.edsx_eds_msa.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                 ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p, ctypes.c_uint64,
+                                 ctypes.c_int, ctypes.c_uint64, P(_Buf), ctypes.c_void_p, P(AlignInfo)]
     _LIB = lib
     return lib
 
@@ -620,6 +631,23 @@ class Context(_Handle):
                                                    ctypes.byref(f), miss.ctypes.data))
         return self._take(f), miss[:n_out]
 
+    # ---- alignment export (eds2msa)
+    def eds_msa(self, eds, seds, paths=None, line_width=60, names=None, prefix=None, gap="-", max_bytes=0):
+        """One-shot edsx_eds_msa: the requested paths (None or empty: all paths 1..P) as rows of one alignment, FASTA ->
+        (fasta bytes, missing counts as numpy uint64, info dict of the column layout)."""
+        import numpy as np
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        ids, nm, n_out = _path_args(paths, names)
+        if paths is None or len(ids) == 0:                       # all paths: P records, learnt from the text
+            n_out = max([int(x) for x in _re_ids(sb)] + [0]) if sb else 0
+        miss = np.zeros(max(n_out, 1), dtype=np.uint64)
+        f, info = _Buf(), AlignInfo()
+        self._check(self._lib.edsx_eds_msa(self._h, eds, len(eds), sb, sn, ids.ctypes.data if len(ids) else None, len(ids), nm,
+                                           prefix.encode() if prefix is not None else None, int(line_width), _gap(gap),
+                                           int(max_bytes), ctypes.byref(f), miss.ctypes.data, ctypes.byref(info)))
+        return self._take(f), miss[:n_out], _fields(info)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -833,6 +861,16 @@ def _path_args(paths, names):
     return ids, nm, len(ids)
 
 
+def _gap(gap):
+    """The gap parameter of the align calls as the C int: one character or byte, or its value (0: the default '-')."""
+    if isinstance(gap, int):
+        return gap
+    g = gap.encode("latin-1") if isinstance(gap, str) else bytes(gap)
+    if len(g) != 1:
+        raise ValueError("the gap is one byte")
+    return g[0]
+
+
 class PathSession(_Handle):
     """An EDS with sources kept tokenised in HBM (edsx_paths_*): the sequence of every path as FASTA.  The session owns its
     device tables: other calls on the context do not invalidate it."""
@@ -853,7 +891,7 @@ class PathSession(_Handle):
 
     @property
     def timing(self):
-        """Of the last lengths / spell / gfa_walks: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
+        """Of the last lengths / spell / gfa_walks / align: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
         t = PathsTiming()
         self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
         return _fields(t, _raw)
@@ -886,6 +924,34 @@ class PathSession(_Handle):
         self._ctx._check(self._lib.edsx_paths_spell(self._h, ids.ctypes.data if len(ids) else None, len(ids), nm,
                                                     prefix.encode() if prefix is not None else None, int(line_width),
                                                     ctypes.byref(f), miss.ctypes.data))
+        if as_numpy:
+            out = np.empty(f.size, dtype=np.uint8)
+            if f.size:
+                ctypes.memmove(out.ctypes.data, f.data, f.size)
+            self._lib.edsx_buf_free(ctypes.byref(f))
+            return out, miss[:n_out]
+        return self._ctx._take(f), miss[:n_out]
+
+    def align_info(self):
+        """The column layout of align(): n_symbols, n_columns (W), n_zero_width_symbols, widest_symbol, num_paths."""
+        i = AlignInfo()
+        self._ctx._check(self._lib.edsx_paths_align_info(self._h, ctypes.byref(i)))
+        return _fields(i)
+
+    def align(self, paths=None, line_width=60, names=None, prefix=None, gap="-", max_bytes=0, as_numpy=False):
+        """(fasta, missing): the requested paths (None or empty: all paths 1..P) as rows of one alignment, FASTA in request
+        order.  Every symbol owns as many columns as its longest string has characters; a row holds the path's strings
+        left-justified there and `gap` elsewhere, so all rows have align_info()["n_columns"] characters whatever paths
+        are asked for (edsx_paths_align).  max_bytes: 0 = no limit.  as_numpy as in spell()."""
+        import numpy as np
+        ids, nm, n_out = _path_args(paths, names)
+        if len(ids) == 0:
+            n_out = self.info["num_paths"]
+        miss = np.zeros(max(n_out, 1), dtype=np.uint64)
+        f = _Buf()
+        self._ctx._check(self._lib.edsx_paths_align(self._h, ids.ctypes.data if len(ids) else None, len(ids), nm,
+                                                    prefix.encode() if prefix is not None else None, int(line_width),
+                                                    _gap(gap), int(max_bytes), ctypes.byref(f), miss.ctypes.data))
         if as_numpy:
             out = np.empty(f.size, dtype=np.uint8)
             if f.size:

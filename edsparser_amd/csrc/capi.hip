@@ -1036,6 +1036,57 @@ int edsx_eds_gfa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8
     });
 }
 
+// ---- eds2msa (path_device.hip)
+int edsx_paths_align_info(edsx_paths_session* s, edsx_align_info* out)
+{
+    zero(out);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!out) throw ParamError("null argument");
+        static_assert(sizeof(AlignInfo) == sizeof(edsx_align_info) && offsetof(AlignInfo, num_paths) == offsetof(edsx_align_info, num_paths),
+                      "edsx_align_info is AlignInfo");
+        std::memcpy(out, &s->p.align_info(nullptr), sizeof(*out));
+    });
+}
+
+int edsx_paths_align(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                     uint64_t line_width, int gap, uint64_t max_bytes, edsx_buf* fasta, uint64_t* missing)
+{
+    clear(fasta);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!fasta || (n && !ids)) throw ParamError("null argument");
+        std::vector<u64> all;
+        if (n == 0) {                                            // every path
+            if (names) throw ParamError("names need an explicit list of path ids");
+            all.resize(s->p.info().num_paths);
+            for (size_t k = 0; k < all.size(); k++) all[k] = k + 1;
+        }
+        if (names) for (size_t k = 0; k < n; k++) if (!names[k]) throw ParamError("null argument");
+        if (gap < 0 || gap > 255) throw ParamError("Gap character is not usable in an alignment");
+        HostBytes out;
+        s->p.align(n ? reinterpret_cast<const u64*>(ids) : all.data(), n ? n : all.size(), names, prefix, line_width,
+                   gap ? (uint8_t)gap : (uint8_t)'-', max_bytes, out, reinterpret_cast<u64*>(missing), nullptr);
+        give(fasta, out);
+    });
+}
+
+int edsx_eds_msa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                 size_t n, const char* const* names, const char* prefix, uint64_t line_width, int gap, uint64_t max_bytes,
+                 edsx_buf* fasta, uint64_t* missing, edsx_align_info* info)
+{
+    clear(fasta);
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close, [&] {
+        edsx_align_info ai;
+        const int rc = edsx_paths_align_info(s, &ai);
+        if (rc != EDSX_OK) return rc;
+        if (info) *info = ai;
+        return edsx_paths_align(s, ids, n, names, prefix, line_width, gap, max_bytes, fasta, missing);
+    });
+}
+
 // ---- eds2vcf (vcf_export_device.hip)
 int edsx_eds_vcf(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                  const edsx_vcf_export_opts* opts, edsx_buf* vcf, edsx_buf* ref_fasta, edsx_vcf_export_info* info)

@@ -32,6 +32,14 @@
 //              k_path_walk     the shape of k_path_copy: a workgroup per (16 KiB of a line, path), the symbol range by the
 //                              256-way search, 16 bytes per lane assembled in registers and stored at once; the last
 //                              comma of a line is a tab and "*\n" follows.  No LDS cache of the stretch's offsets
+//
+// Alignment rows (edsx_paths_align): symbol i owns w[i] columns, the length of its longest string; a row holds
+// the chosen strings left-justified in their columns and the gap byte elsewhere, so every row has W = sum w[i] characters:
+//   first call k_align_width   w, scanned once (col) and kept with the session
+//   per batch  k_path_choose   as above (the chosen strings and the missing counts; the scanned lengths are not used)
+//              k_path_align    the shape of k_path_copy over columns instead of characters: col does not depend on the
+//                              path, so the symbol range of a step needs no table row; 2000 symbols per step in LDS,
+//                              those behind them from global memory; gap runs are stores without a load
 #include "path_device.hpp"
 
 #include <chrono>
@@ -251,6 +259,187 @@ __global__ void __launch_bounds__(CP_THREADS) k_path_copy(CopyArgs a)
     }
 }
 
+// ---- alignment rows (eds2msa): every symbol owns as many columns as its longest string has characters --------
+// w[i] into col[i] (scanned in place afterwards; col[n] = 0 becomes W); stat[0]: symbols of width 0, stat[1]: the widest
+__global__ void __launch_bounds__(256) k_align_width(const u64* __restrict__ size, const u64* __restrict__ ent_off,
+                                                     const u64* __restrict__ str_off, u64 n, u64* __restrict__ col,
+                                                     u64* __restrict__ stat)
+{
+    u64 zero = 0, widest = 0;
+    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i <= n; i += (u64)gridDim.x * blockDim.x) {
+        u64 w = 0;
+        if (i < n) {
+            const u64 e0 = ent_off[i], e1 = e0 + size[i];
+            for (u64 j = e0; j < e1; j++) w = max(w, str_off[j + 1] - str_off[j]);
+            if (w == 0) zero++;
+            widest = max(widest, w);
+        }
+        col[i] = w;
+    }
+    for (int sh = 32; sh > 0; sh >>= 1) {
+        zero += __shfl_xor(zero, sh, 64);
+        widest = max(widest, (u64)__shfl_xor(widest, sh, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (zero) atomicAdd((unsigned long long*)&stat[0], (unsigned long long)zero);
+        if (widest) atomicMax((unsigned long long*)&stat[1], (unsigned long long)widest);
+    }
+}
+
+constexpr u32 AL_SYMS = 2000;        // symbols whose columns, string ends and pool bases are kept in LDS per step: 16 B each,
+                                     // 2000 so that five workgroups fit the 160 KiB of a CU (2048 leaves room for four)
+
+struct AlignArgs {
+    const u64* ent_off; const u64* str_off; const uint8_t* chars;
+    const u64* col; const u64* rank;           // n + 1 entries each
+    const u64* csid; u64 n, nc;                // the chosen strings (null when nc == 0)
+    const PathRec* rec; u64 nrec, max_tiles;
+    uint8_t* out; u32 gap;
+};
+
+// symbol i on the path of table row kb / nc: its first column, where its chosen string ends (no string: at once), and the
+// pool offset of the string minus the first column (column c of the string is chars[base + c])
+__device__ __forceinline__ void align_load(const AlignArgs& a, u64 kb, u64 i, u64& c0, u64& send, u64& base)
+{
+    const u64 r = a.rank[i];
+    c0 = a.col[i];
+    const u64 sid = a.rank[i + 1] != r ? a.csid[kb + r] : a.ent_off[i];
+    if (sid == NONE) { send = c0; base = 0; return; }
+    const u64 s0 = a.str_off[sid];
+    send = c0 + (a.str_off[sid + 1] - s0);
+    base = s0 - c0;
+}
+
+// largest i in [0, n) with col[i] <= q (col[0] = 0), as block_find.  For q < W that symbol has a column: symbols of
+// width 0 share their col with the next one, which is then the larger i
+__device__ u64 align_block_find(const u64* __restrict__ col, u64 n, u64 q)
+{
+    u64 lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const u64 step = (hi - lo + CP_THREADS - 1) / CP_THREADS;
+        const u64 i = lo + threadIdx.x * step;
+        const int ok = i < hi && col[i] <= q;
+        const int cnt = __syncthreads_count(ok);
+        lo += (u64)(cnt - 1) * step;
+        hi = min(hi, lo + step);
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void put16(uint8_t* dst, u128 x, u32 nb)
+{
+    if (nb == 16) {
+        const u64 lo = (u64)x, hi = (u64)(x >> 64);
+        store16u(dst, make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)));
+    } else {
+        for (u32 b = 0; b < nb; b++) dst[b] = (uint8_t)(x >> (8u * b));
+    }
+}
+
+// One workgroup per (16 KiB of a row's FASTA body, path), paths fastest as in k_path_copy.  The columns do not depend on
+// the path: the symbol range of a step comes from col alone, and the step keeps, for its first AL_SYMS symbols, the first
+// column (relative to the step's first, saturated), the end of the chosen string (the same) and the pool base in LDS;
+// symbols behind those are looked up in global memory.  A lane assembles 16 output bytes: where they lie inside one
+// symbol, one 16-byte load out of the string (the pool ends in 16 bytes of slack) with the bytes behind the string's
+// end replaced by the gap byte, or no load at all when they lie behind it; otherwise byte by byte.
+__global__ void __launch_bounds__(CP_THREADS) k_path_align(AlignArgs a)
+{
+    __shared__ u32 scol[AL_SYMS + 1];
+    __shared__ u32 send[AL_SYMS];
+    __shared__ u64 sbase[AL_SYMS];
+    const u64 work = a.max_tiles * a.nrec;
+    const u128 gaps = (u128)(0x0101010101010101ull * a.gap) << 64 | (u128)(0x0101010101010101ull * a.gap);
+    for (u64 wi = blockIdx.x; wi < work; wi += gridDim.x) {
+        const PathRec rc = a.rec[wi % a.nrec];
+        const u64 o0 = (wi / a.nrec) * CP_TILE;
+        if (o0 >= rc.body) continue;
+        const u64 o1 = min(rc.body, o0 + (u64)CP_TILE), per = rc.lw + 1, kb = rc.row * a.nc, last = rc.body - 1;
+        const u64 q0 = o0 - o0 / per, q1 = min(rc.L, o1 - o1 / per);      // this step writes columns [q0, q1)
+        u64 iA = 0, iB = 0;
+        u32 cnt = 0;
+        __syncthreads();                                                  // the last step's readers of the tables are through
+        if (q0 < q1) {
+            iA = align_block_find(a.col, a.n, q0);
+            iB = align_block_find(a.col, a.n, q1 - 1);
+            cnt = (u32)min((u64)AL_SYMS, iB - iA + 1);
+            for (u32 j = threadIdx.x; j <= cnt; j += CP_THREADS) {
+                u64 c0;
+                if (j < cnt) {
+                    u64 se, base;
+                    align_load(a, kb, iA + j, c0, se, base);
+                    send[j] = se <= q0 ? 0u : (u32)min(se - q0, 0xffffffffull);
+                    sbase[j] = base;
+                } else c0 = a.col[iA + j];
+                scol[j] = c0 <= q0 ? 0u : (u32)min(c0 - q0, 0xffffffffull);
+            }
+            __syncthreads();
+        }
+        auto find = [&](u64 q) -> u64 {                                    // symbol of column q, q0 <= q < q1
+            const u64 rel = q - q0;
+            if (rel < (u64)scol[cnt]) {
+                u32 lo = 0, hi = cnt;
+                while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if ((u64)scol[mid] <= rel) lo = mid; else hi = mid; }
+                return iA + lo;
+            }
+            u64 lo = iA + cnt, hi = iB + 1;
+            while (hi - lo > 1) { const u64 mid = lo + ((hi - lo) >> 1); if (a.col[mid] <= q) lo = mid; else hi = mid; }
+            return lo;
+        };
+        auto sym = [&](u64 i, u64& end, u64& se, u64& base) {              // symbol i: behind its last column, behind its string
+            const u64 j = i - iA;
+            if (j < cnt) { end = q0 + scol[j + 1]; se = q0 + send[j]; base = sbase[j]; return; }
+            u64 c0;
+            align_load(a, kb, i, c0, se, base);
+            end = a.col[i + 1];
+        };
+        for (u64 o = o0 + (u64)threadIdx.x * 16; o < o1; o += (u64)CP_THREADS * 16) {
+            const u32 nb = (u32)min((u64)16, o1 - o);
+            uint8_t* dst = a.out + rc.body_off + o;
+            u64 q = o - o / per;                                           // first column at or behind output byte o
+            const u64 nl1 = min((o / per + 1) * per - 1, last);            // first line feed at or behind o
+            u32 nn = 0;
+            if (nl1 < o + nb) {
+                nn = 1;
+                if (nl1 < last && min(nl1 + per, last) < o + nb) nn = 2;
+            }
+            if (nn == 1 && nb == 1) { dst[0] = '\n'; continue; }
+            u64 i = find(q), end, se, base;
+            sym(i, end, se, base);
+            if (nn <= 1 && q + (nb - nn) <= end) {                         // the chunk lies in one symbol
+                u128 x = gaps;
+                if (q < se) {
+                    const uint4 v = load16u(a.chars + (base + q));
+                    x = ((u128)(((u64)v.w << 32) | v.z) << 64) | (((u64)v.y << 32) | v.x);
+                    if (se - q < 16) {                                     // the string ends inside: gaps behind it
+                        const u128 keep = ((u128)1 << (8u * (u32)(se - q))) - 1;
+                        x = (x & keep) | (gaps & ~keep);
+                    }
+                }
+                if (nn) {
+                    const u32 sh = 8u * (u32)(nl1 - o);
+                    const u128 mask = ((u128)1 << sh) - 1;
+                    x = (x & mask) | ((u128)'\n' << sh) | ((x & ~mask) << 8);
+                }
+                put16(dst, x, nb);
+                continue;
+            }
+            u64 nl = nl1;                                                  // byte by byte across symbols and short lines
+            u128 x = 0;
+            for (u32 b = 0; b < nb; b++) {
+                u32 c = '\n';
+                if (o + b == nl) nl = nl == last ? NONE : min(nl + per, last);
+                else {
+                    while (q >= end && i + 1 < a.n) { i++; sym(i, end, se, base); }
+                    c = q < se ? a.chars[(u64)(base + q)] : a.gap;
+                    q++;
+                }
+                x |= (u128)c << (8u * b);
+            }
+            put16(dst, x, nb);
+        }
+    }
+}
+
 // ---- GFA walks (P lines): the same tables over token bytes instead of characters (gfa_text.hpp) -----------------------
 // token bytes ("<id>+,") of every fixed symbol whose string is not empty, and a 1 for each such symbol
 __global__ void k_path_tokfixed(const u64* __restrict__ ent_off, const u32* __restrict__ elen, const u64* __restrict__ seg_rank,
@@ -345,6 +534,20 @@ u64 free_hbm()
     return free_b;
 }
 
+// the header lines ">name\n" of n records laid end to end in blob (names[k], else prefix - null: "path" - + id); -> where each begins
+std::vector<u64> fasta_headers(const u64* ids, size_t n, const char* const* names, const char* prefix, std::string& blob)
+{
+    std::vector<u64> hoff(n + 1, 0);
+    const std::string pre = prefix ? prefix : "path";
+    for (size_t k = 0; k < n; k++) {
+        blob += '>';
+        if (names) blob += names[k]; else blob += pre + std::to_string(ids[k]);
+        blob += '\n';
+        hoff[k + 1] = blob.size();
+    }
+    return hoff;
+}
+
 } // namespace
 
 void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, hipStream_t st)
@@ -353,6 +556,7 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     info_ = PathInfo{};
     timing_ = PathTiming{};
     walk_ready_ = false;
+    align_ready_ = false;
     const auto t0 = std::chrono::steady_clock::now();
     eds_.load(eds, eds_n, seds, seds_n, true, st);
     eds_.drop_scratch();                                                      // the session may live long
@@ -474,16 +678,8 @@ void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, con
     timing_.tokenise_ms = tok;
     out.take(0);
     if (n == 0) return;
-    // header texts
     std::string blob;
-    std::vector<u64> hoff(n + 1, 0);
-    const std::string pre = prefix ? prefix : "path";
-    for (size_t k = 0; k < n; k++) {
-        blob += '>';
-        if (names) blob += names[k]; else blob += pre + std::to_string(ids[k]);
-        blob += '\n';
-        hoff[k + 1] = blob.size();
-    }
+    const std::vector<u64> hoff = fasta_headers(ids, n, names, prefix, blob);
     // lengths of all requested paths; one table batch: its tables stay for the copy
     const u64 KT = table_batch(n);
     const bool single = KT >= n;
@@ -536,6 +732,112 @@ void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, con
             hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
             const u64 work = a.max_tiles * nrec;
             if (work) hipLaunchKernelGGL(k_path_copy, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
+            EDSX_HIP(hipEventRecord(ev.b, st));
+            EDSX_HIP(hipStreamSynchronize(st));
+            EDSX_HIP(hipGetLastError());
+            timing_.copy_ms += ev.ms();
+            const auto t0 = std::chrono::steady_clock::now();
+            PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
+            timing_.download_ms += since_ms(t0);
+            r0 = r1;
+        }
+    }
+}
+
+void PathPipeline::align_open(hipStream_t st)
+{
+    if (align_ready_) return;
+    ainfo_ = AlignInfo{};
+    ainfo_.n_symbols = n_; ainfo_.num_paths = info_.num_paths;
+    if (n_) {
+        const EdsView v = eds_.view();
+        col_.ensure(8 * (n_ + 1));
+        ctl_.ensure(8 * 8);
+        scan_tmp_.ensure(8 * (n_ / SCAN_TILE + 4));
+        u64 h[4] = {n_ + 1, 0, 0, 0};                            // count; W; symbols of width 0; the widest
+        u64* ctl = ctl_.as<u64>();
+        EDSX_HIP(hipMemcpyAsync(ctl, h, sizeof(h), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_align_width, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, n_,
+                           col_.as<u64>(), ctl + 2);
+        exclusive_scan_u64(col_.as<u64>(), col_.as<u64>(), ctl, ctl + 1, scan_tmp_.as<u64>(), st);
+        EDSX_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+        EDSX_HIP(hipStreamSynchronize(st));
+        EDSX_HIP(hipGetLastError());
+        ainfo_.n_columns = h[1]; ainfo_.n_zero_width_symbols = h[2]; ainfo_.widest_symbol = h[3];
+    }
+    align_ready_ = true;
+}
+
+void PathPipeline::align(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, uint8_t gap,
+                         u64 max_bytes, HostBytes& out, u64* missing, hipStream_t st)
+{
+    check_ids(ids, n);
+    if (std::strchr(">\n\r {},", gap)) throw ParamError("Gap character is not usable in an alignment");   // (and 0)
+    const double tok = timing_.tokenise_ms;
+    timing_ = PathTiming{};
+    timing_.tokenise_ms = tok;
+    out.take(0);
+    if (n == 0) return;
+    align_open(st);
+    // header texts, and the size of the whole: every row has W columns, so the counts give it
+    const u64 W = ainfo_.n_columns;
+    const u64 lw = (line_width == 0 || line_width > W) ? std::max<u64>(W, 1) : line_width;
+    const u64 body = W ? W + (W + lw - 1) / lw : 0;
+    std::string blob;
+    const std::vector<u64> hoff = fasta_headers(ids, n, names, prefix, blob);
+    const unsigned __int128 total128 = (unsigned __int128)body * n + blob.size();
+    if ((max_bytes && total128 > max_bytes) || total128 > ~0ull) {
+        const std::string cap = std::to_string(max_bytes ? max_bytes : ~0ull);
+        const std::string have = total128 > ~0ull ? "more than " + std::to_string(~0ull) : std::to_string((u64)total128);
+        throw ParamError("Alignment has " + have + " bytes, above the limit of " + cap);
+    }
+    const u64 total = (u64)total128;
+    // the missing counts of all requested paths; one table batch: its table stays for the rows
+    const u64 KT = table_batch(n);
+    const bool single = KT >= n;
+    std::vector<u64> miss(n), bl, bm;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const u64 K = std::min<u64>(KT, n - i0);
+        tables(ids + i0, K, bl, bm, st);
+        std::memcpy(miss.data() + i0, bm.data(), 8 * K);
+    }
+    if (missing) std::memcpy(missing, miss.data(), 8 * n);
+    std::vector<PathRec> rec(n);
+    std::vector<u64> host_off(n + 1, 0);                        // record starts in the caller's buffer
+    for (size_t k = 0; k < n; k++) {
+        PathRec& r = rec[k];
+        r.L = W; r.lw = lw; r.body = body;
+        r.hdr_src = hoff[k];
+        r.row = k % KT;
+        host_off[k + 1] = host_off[k] + (hoff[k + 1] - hoff[k]) + body;
+    }
+    out.take(total);
+    timing_.bytes_written = total;
+    hdr_.ensure(blob.size());
+    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const size_t i1 = std::min<size_t>(n, i0 + KT);
+        if (!single) tables(ids + i0, i1 - i0, bl, bm, st);
+        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many records as the budget holds
+            size_t r1 = r0 + 1;
+            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
+            const u64 bytes = host_off[r1] - host_off[r0], nrec = r1 - r0;
+            for (size_t k = r0; k < r1; k++) {
+                rec[k].rec_off = host_off[k] - host_off[r0];
+                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
+            }
+            out_.ensure(bytes + 16);                             // 16 bytes of slack behind the text, as every output buffer here
+            rec_.ensure(sizeof(PathRec) * nrec);
+            EDSX_HIP(hipMemcpyAsync(rec_.ptr, rec.data() + r0, sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
+            const EdsView v = eds_.view();
+            AlignArgs a{v.sym.ent_off, v.str_off, v.chars, col_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, n_, nc_,
+                        rec_.as<PathRec>(), nrec, (body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>(), gap};
+            EventPair ev;
+            EDSX_HIP(hipEventRecord(ev.a, st));
+            hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
+            const u64 work = a.max_tiles * nrec;
+            if (work) hipLaunchKernelGGL(k_path_align, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
             EDSX_HIP(hipEventRecord(ev.b, st));
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());

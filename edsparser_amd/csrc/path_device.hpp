@@ -14,8 +14,8 @@ struct PathInfo {
     bool tokenised_on_device = false;
 };
 
-// of the last lengths() / spell() / walks(): device events around the kernels, a host clock around the downloads (walks:
-// scan_ms holds both scans of a batch, copy_ms is k_path_walk)
+// of the last lengths() / spell() / walks() / align(): device events around the kernels, a host clock around the downloads
+// (walks: scan_ms holds both scans of a batch, copy_ms is k_path_walk; align: copy_ms is k_path_align)
 struct PathTiming {
     double tokenise_ms = 0, choose_ms = 0, scan_ms = 0, copy_ms = 0, download_ms = 0;
     u64 bytes_written = 0;
@@ -25,6 +25,9 @@ struct PathTiming {
 // text lies in the header blob, its length, the line width in force (>= 1), the body bytes (characters + newlines) and
 // its row of the choice tables
 struct PathRec { u64 rec_off, body_off, hdr_src, L, lw, body, row; };
+
+// the column layout of the session's alignment view (align): W = n_columns
+struct AlignInfo { u64 n_symbols = 0, n_columns = 0, n_zero_width_symbols = 0, widest_symbol = 0, num_paths = 0; };
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -47,6 +50,14 @@ public:
     void walks(const u64* ids, size_t n, const char* const* names, const char* prefix, HostBytes& out, u64* missing, u64* steps,
                hipStream_t st);
 
+    // The paths as rows of one alignment: symbol i owns w[i] columns, the length of its longest string, and
+    // holds the chosen string of the path left-justified and filled up with `gap`; every row has W = sum w[i] characters,
+    // whatever paths are asked for.  FASTA as spell() writes it.  max_bytes (0: none): ParamError, from the counts and
+    // before any table or text is made, when the text is larger.
+    const AlignInfo& align_info(hipStream_t st) { align_open(st); return ainfo_; }
+    void align(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, uint8_t gap, u64 max_bytes,
+               HostBytes& out, u64* missing, hipStream_t st);
+
 private:
     void check_ids(const u64* ids, size_t n) const;
     u64 table_batch(size_t n, u64 cell_bytes = 16) const;
@@ -54,6 +65,9 @@ private:
     void walk_open(hipStream_t st);
     // tables(), then the token bytes of every (path, choice symbol) and their scan; tok / cnt: token bytes and ids per path
     void walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std::vector<u64>& miss, std::vector<u64>& cnt, hipStream_t st);
+    // col (the exclusive scan of the symbol widths, n + 1 entries): made by the first align() or align_info() of a
+    // session, kept until it closes
+    void align_open(hipStream_t st);
     static u64 budget_override();
     // choose + scan for ids[0..K): device tables for the copy kernel, host lengths and missing counts
     void tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st);
@@ -66,6 +80,9 @@ private:
     bool walk_ready_ = false;
     u64 Ftok_ = 0, Fcnt_ = 0;                                    // token bytes / ids of the fixed symbols
     DevBuf seg_rank_, cum_tok_, tlen_, cnt_;
+    bool align_ready_ = false;
+    AlignInfo ainfo_;
+    DevBuf col_;
 };
 
 } // namespace edsx

@@ -62,6 +62,38 @@ void eds_to_fasta(std::istream& eds_in, std::istream& seds_in, std::ostream& out
     if (missing) missing->assign(miss.begin(), miss.end());
 }
 
+void eds_to_msa(std::istream& eds_in, std::istream& seds_in, std::ostream& out, const std::vector<int>& paths, size_t line_width,
+                const std::vector<std::string>* names, const std::string& prefix, char gap, size_t max_bytes, AlignInfo* info)
+{
+    if (names && names->size() != paths.size()) throw std::invalid_argument("eds_to_msa: one name per requested path");
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    std::vector<const char*> np;
+    if (names) for (const auto& s : *names) np.push_back(s.c_str());
+    edsx_ctx* ctx = detail::context();
+    edsx_paths_session* s = nullptr;
+    int rc = edsx_paths_open(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                             reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), &s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    edsx_align_info ai;
+    rc = edsx_paths_align_info(s, &ai);
+    std::vector<uint64_t> miss(ids.empty() ? ai.num_paths : ids.size());
+    detail::Buf fasta;
+    // (a gap of 0 would mean the default: hand the C ABI a value it refuses instead)
+    if (rc == EDSX_OK)
+        rc = edsx_paths_align(s, ids.data(), ids.size(), names && !np.empty() ? np.data() : nullptr, prefix.c_str(), line_width,
+                              gap ? static_cast<unsigned char>(gap) : 256, max_bytes, &fasta.b, miss.data());
+    edsx_paths_close(s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    out.write(reinterpret_cast<const char*>(fasta.b.data), static_cast<std::streamsize>(fasta.b.size));
+    if (info) {
+        info->n_symbols = ai.n_symbols; info->n_columns = ai.n_columns; info->n_zero_width_symbols = ai.n_zero_width_symbols;
+        info->widest_symbol = ai.widest_symbol; info->num_paths = ai.num_paths;
+        info->missing.assign(miss.begin(), miss.end());
+    }
+}
+
 void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
 {

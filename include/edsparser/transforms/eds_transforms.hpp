@@ -34,6 +34,20 @@ void eds_to_fasta(std::istream& eds, std::istream& seds, std::ostream& out, cons
                   size_t line_width = 60, const std::vector<std::string>* names = nullptr,
                   std::vector<size_t>* missing = nullptr);
 
+// eds2msa: the given paths (empty: all paths 1..P) as rows of one alignment, FASTA in request order.  Symbol i owns as
+// many columns as its longest string has characters; a row holds the string the path takes there (as eds_to_fasta
+// chooses it) left-justified and `gap` in the other columns, so every row has info->n_columns characters whatever paths
+// are asked for, and rows of separate calls stack into one alignment (edsx_paths_align states the rules in full).
+// line_width 0: one line per row.  max_bytes 0: no limit.  std::invalid_argument for a path outside 1..P, a gap that is
+// '>', a line feed, a carriage return, a blank, a brace or a comma, and a text above max_bytes.
+struct AlignInfo {
+    size_t n_symbols = 0, n_columns = 0, n_zero_width_symbols = 0, widest_symbol = 0, num_paths = 0;
+    std::vector<size_t> missing;               // per requested path
+};
+void eds_to_msa(std::istream& eds, std::istream& seds, std::ostream& out, const std::vector<int>& paths = {},
+                size_t line_width = 0, const std::vector<std::string>* names = nullptr, const std::string& prefix = "path",
+                char gap = '-', size_t max_bytes = 0, AlignInfo* info = nullptr);
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

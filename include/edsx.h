@@ -480,8 +480,9 @@ int  edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, ui
  * missing (may be NULL): one count per record. */
 int  edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
                       uint64_t line_width, edsx_buf* fasta, uint64_t* missing);
-/* of the last edsx_paths_lengths / edsx_paths_spell / edsx_paths_gfa_walks (tokenise_ms: of edsx_paths_open; walks:
- * scan_ms holds both scans of a batch, copy_ms the walk kernel, bytes_written the P lines) */
+/* of the last edsx_paths_lengths / edsx_paths_spell / edsx_paths_gfa_walks / edsx_paths_align (tokenise_ms: of
+ * edsx_paths_open; walks: scan_ms holds both scans of a batch, copy_ms the walk kernel, bytes_written the P lines; align:
+ * copy_ms the alignment kernel, bytes_written the alignment) */
 int  edsx_paths_last_timing(const edsx_paths_session* s, edsx_paths_timing* out);
 void edsx_paths_close(edsx_paths_session* s);
 /* open + spell + close */
@@ -606,6 +607,34 @@ typedef struct { uint64_t symbols, strings, paths, records, anchored, overlappin
                  int tokenised_on_device; } edsx_vcf_export_info;
 int edsx_eds_vcf(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                  const edsx_vcf_export_opts* opts, edsx_buf* vcf, edsx_buf* ref_fasta, edsx_vcf_export_info* info);
+
+/* ---- eds2msa: the paths of an EDS with sources as the rows of one alignment (path_device.hip) ----
+ * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them; n symbols, P the largest path id.
+ *   Width.  w[i] is the length of the longest string of symbol i - over all its strings, not over those the requested
+ *      paths take - col[i] the exclusive prefix sum of w, W = sum w[i].  Widths do not depend on the request, so rows
+ *      written by separate calls stack into one alignment.
+ *   Row of path p.  Symbol i occupies columns col[i] .. col[i] + w[i] - 1 and holds the string edsx_paths_spell chooses
+ *      for p there, left-justified and filled up with the gap byte; a symbol at which p has no string is w[i] gap bytes
+ *      and counts in missing.  Every row has exactly W characters; a symbol of width 0 occupies no column.
+ *   Text.  FASTA, one record per requested path in request order (n == 0: all paths 1..P); headers, names and prefix as
+ *      in edsx_paths_spell; the row in lines of line_width characters, each ended by '\n' (0: one line; W == 0: no line).
+ *   Gap byte.  gap == 0 means '-'; otherwise any byte value except '>', '\n', '\r', blank, '{', '}' and ',' - anything
+ *      else is EDSX_ERR_INVALID_PARAMETER, "Gap character is not usable in an alignment".  Strings are copied verbatim: a
+ *      string that itself holds the gap byte is the caller's business.
+ *   Limit.  max_bytes == 0: none; a larger text is EDSX_ERR_INVALID_PARAMETER, "Alignment has <n> bytes, above the limit
+ *      of <cap>", raised from the counts before anything is allocated for the text (an alignment is P x W bytes however
+ *      small the EDS is).
+ *   Errors.  Path ids, a missing .seds and names give the statuses and texts of edsx_paths_spell.
+ * The column table (8 bytes per symbol) is made by the first of these calls on a session and kept until it closes. */
+typedef struct { uint64_t n_symbols, n_columns /* W */, n_zero_width_symbols, widest_symbol, num_paths; } edsx_align_info;
+int edsx_paths_align_info(edsx_paths_session* s, edsx_align_info* out);
+/* missing (may be NULL): one count per record */
+int edsx_paths_align(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
+                     uint64_t line_width, int gap, uint64_t max_bytes, edsx_buf* fasta, uint64_t* missing);
+/* open + align + close; info (may be NULL) is filled as soon as the column table is known, so also when the limit refuses */
+int edsx_eds_msa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                 size_t n, const char* const* names, const char* prefix, uint64_t line_width, int gap, uint64_t max_bytes,
+                 edsx_buf* fasta, uint64_t* missing, edsx_align_info* info);
 
 /* Per-kernel device time, measured with HIP events on the stream each kernel is launched on and
  * accumulated over all plan/emit calls (and edsx_eds_subset / edsx_eds_gfa_graph / edsx_eds_vcf calls) since edsx_set_timing(ctx, 1).  Arrays of capacity cap;
