@@ -38,16 +38,17 @@ def random_msa(rng, S=None, L=None, lw=None, trailing_newline=True, p_var=0.08, 
 CAMPAIGN_ALPHABETS = ["ACGT", "ACGTN", "ACGTacgtN", "ACDEFGHIKLMNPQRSTVWY", "AC"]
 
 
-def campaign_msa(rng):
+def campaign_msa(rng, max_cells=3_000_000):
     """One alignment of the randomized parity campaign: row counts around every kernel switch (rows per
     lane, S <= 256 instantiations, the 1024 fast/generic limit), column counts around tile edges, DNA /
     lower-case / protein alphabets, site and gap densities from 0 to 1, wrapped lines, header styles,
-    missing or doubled final newline.  Returns (bytes, description)."""
+    missing or doubled final newline.  max_cells caps rows x columns by cutting the columns (the default is the cap it always had).
+    Returns (bytes, description)."""
     S = rng.choice([2, 3, 5, 17, 33, 64, 65, 100, 130, 256, 257, 400, 513, 700, 960, 1000, 1024, 1025, 1100,
                     rng.randint(2, 1200)])
     L = rng.choice([1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 300, 1000, 2047, 2048, 2049, rng.randint(1, 6000)])
-    if S * L > 3_000_000:
-        L = max(1, 3_000_000 // S)
+    if S * L > max_cells:
+        L = max(1, max_cells // S)
     alph = rng.choice(CAMPAIGN_ALPHABETS)
     p_var = rng.choice([0.0, 0.01, 0.05, 0.2, 0.6, 1.0])
     p_gap = rng.choice([0.0, 0.1, 0.5])
