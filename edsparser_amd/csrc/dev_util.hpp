@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "draw.hpp"
+#include "byte_ops.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -165,28 +166,12 @@ __device__ __forceinline__ uint4 load_partial(const uint8_t* p, int n)
     return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
 }
 
-// per-byte "a != b" mask of a dword pair as 4 bits
-__device__ __forceinline__ u32 ne_bytes4(uint32_t a, uint32_t b)
-{
-    uint32_t x = a ^ b;
-    // byte != 0  <=>  ((x & 0x7f7f7f7f) + 0x7f7f7f7f | x) & 0x80808080
-    uint32_t t = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
-    // gather bits 7,15,23,31 -> 0..3
-    return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u);
-}
-__device__ __forceinline__ u32 eq_byte4(uint32_t a, uint32_t cccc) { return 0xFu ^ ne_bytes4(a, cccc); }
+// ne_bytes4 / eq_byte4 (per-byte compare masks of a dword) and ndigits: byte_ops.hpp, shared with host-compiled code
 
 __device__ __forceinline__ u32 byte_of(const uint4& v, int i)
 {
     uint32_t w = (i < 8) ? ((i < 4) ? v.x : v.y) : ((i < 12) ? v.z : v.w);
     return (w >> ((i & 3) * 8)) & 0xffu;
-}
-
-// decimal digits of v (v >= 1)
-__device__ __forceinline__ u32 ndigits(u32 v)
-{
-    return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) +
-           (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) + (v >= 1000000000u);
 }
 
 // ---- device-wide scans on u64 arrays, element count read from device memory -----------------

@@ -20,6 +20,7 @@
 //                   bit matrix.
 #include "vcf_device.hpp"
 #include "vcf_text_kernels.hpp"
+#include "vcf_walk.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -29,50 +30,15 @@
 
 namespace edsx {
 
-struct VcfDev {
-    // reference
-    const uint8_t* fasta; u64 fasta_n; u64 seq_start, seq_size, lw;   // fasta[i]: file byte cbase + i
-    const uint8_t* refc; u64 refc_n; const u64* blkpre;
-    u64 cbase, wend;               // file offsets: refc / blkpre begin at cbase (seq_start, or the window's first byte), the
-                                   // device holds the file up to wend (fasta_n, or the window's end)
-    u64* oob;                      // window mode: a read outside the window is reported here (file offset | flags), not clamped
-    // records
-    u64 nrec; const u64* start; const u64* reflen; const u64* alt0; const u64* altstr_off; const uint8_t* altchars;
-    const u64* pair0;          // per record: first (record,sample) pair; pair0[nrec] = #pairs
-    const u64* pair_a0;        // per pair: first allele; pair_a0[#pairs] = #alleles
-    const int* alleles;
-    // groups
-    u64 ngrp; const u64* grp_r0;   // first record of group g, grp_r0[ngrp] = nrec
-    const u64* incl_end;           // inclusive max-scan of record ends
-    u64 cur0;                      // reference position the walk starts at (0 unless this is a later position range)
-};
+// VcfDev, fa_cpos and the bodies of the thread-per-item kernels below: vcf_walk.hpp
 
-__device__ __forceinline__ u64 fa_cpos(const VcfDev& d, u64 file_off)
-{   // position in refc of file offset file_off (>= cbase); offsets past EOF map to refc_n
-    if (file_off >= d.fasta_n) return d.refc_n;
-    if (file_off < d.cbase || file_off >= d.wend) {      // (whole file: never)
-        if (d.oob && file_off != d.wend) *d.oob = file_off | (1ull << 63);
-        return d.refc_n;
-    }
-    const u64 rel = file_off - d.cbase;
-    u64 c = d.blkpre[rel >> 8];
-    // sequence bytes in [block start, file_off): eight bytes per (unaligned) load, line breaks counted with an exact
-    // SWAR zero-byte test; the buffer has 16 bytes of slack behind wend, bytes at or past file_off are masked out
-    u64 f = rel & ~255ull;
-    u64 breaks = 0;
-    while (f < rel) {
-        u64 w;
-        __builtin_memcpy(&w, d.fasta + f, 8);
-        const u64 left = rel - f;
-        const u64 keep = left >= 8 ? ~0ull : ((1ull << (8 * left)) - 1ull);
-        const u64 a = w ^ 0x0a0a0a0a0a0a0a0aull, b = w ^ 0x0d0d0d0d0d0d0d0dull;
-        const u64 nza = (((a & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | a) & 0x8080808080808080ull;   // high bit = byte != '\n'
-        const u64 nzb = (((b & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | b) & 0x8080808080808080ull;
-        breaks += __builtin_popcountll(~(nza & nzb) & 0x8080808080808080ull & keep);
-        f += 8;
-    }
-    return c + (rel - (rel & ~255ull)) - breaks;
-}
+struct WalkGrid {                                            // the grid of a thread-per-item kernel, as its body asks for it
+    u32 bi, bd, ti, gd;                                      // (read in the kernel itself; the products are taken where the body uses them)
+    __device__ __forceinline__ u64 first() const { return bi * (u64)bd + ti; }
+    __device__ __forceinline__ u64 stride() const { return (u64)gd * bd; }
+    __device__ __forceinline__ bool lead() const { return bi == 0 && ti == 0; }
+};
+#define WALK_THREAD WalkGrid{blockIdx.x, blockDim.x, threadIdx.x, gridDim.x}      /* last argument of every body */
 
 // ---- reference stream ---------------------------------------------------------------------------
 __global__ void k_fa_count(const uint8_t* __restrict__ f, u64 n, u64 seq_start, u64* __restrict__ blkcnt, u64 nblk)
@@ -112,10 +78,7 @@ __global__ void k_fa_compact(const uint8_t* __restrict__ f, u64 n, u64 seq_start
 // as in the reference's getline loop).
 __global__ void k_fa_record_end(const uint8_t* __restrict__ f, u64 n, u64 from, u64* __restrict__ rec_end)
 {
-    u64 best = ~0ull;
-    for (u64 i = from + blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-        if (f[i] == '>' && f[i - 1] == '\n') { best = i; break; }
-    if (best != ~0ull) atomicMin((unsigned long long*)rec_end, (unsigned long long)best);
+    fa_record_end_body(f, n, from, rec_end, WALK_THREAD);
 }
 __global__ void k_fa_seq_bytes(const uint8_t* __restrict__ f, u64 from, const u64* __restrict__ rec_end, u64* __restrict__ count)
 {
@@ -166,204 +129,23 @@ __global__ void k_fa_slice_scan(const uint8_t* __restrict__ s, u64 s0, u64 a, u6
 // ---- grouping -------------------------------------------------------------------------------------
 __global__ void k_rec_ends(const u64* __restrict__ start, const u64* __restrict__ reflen, u64 n, u64* __restrict__ ends)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x)
-        ends[j] = start[j] + reflen[j];
+    rec_ends_body(start, reflen, n, ends, WALK_THREAD);
 }
-// a record opens a group iff its start is not below the largest end seen before it (:510)
 __global__ void k_mark_groups(const u64* __restrict__ start, const u64* __restrict__ incl_end, u64 n, u64* __restrict__ flag)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x)
-        flag[j] = (j == 0) || !(start[j] < incl_end[j - 1]);
+    mark_groups_body(start, incl_end, n, flag, WALK_THREAD);
 }
 __global__ void k_group_firsts(const u64* __restrict__ flag, const u64* __restrict__ gidx, u64 n, u64* __restrict__ grp_r0,
                                const u64* __restrict__ ngrp)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x)
-        if (flag[j]) grp_r0[gidx[j]] = j;
-    if (blockIdx.x == 0 && threadIdx.x == 0) grp_r0[*ngrp] = n;
+    group_firsts_body(flag, gidx, n, grp_r0, ngrp, WALK_THREAD);
 }
 
-// ---- per group: thread per group ---------------------------------------------------------------------
-struct GrpArrays {
-    u64* gs; u64* spanlen; u64* cs;          // span start (sequence position), clamped length, refc position
-    u64* nraw; u64* rawchars;                // raw haplotypes (1 + sum of alts) and their total length
-    u64* ndist;                              // distinct haplotypes
-    u64* bitwords;                           // ndist * sample words
-    u64* eds_len; u64* seds_len;             // group symbol + preceding common region
-    u64* commonlen; u64* cur_after;          // common region before the group, reference position after it
-    u64* err;                                // [0] first failing group, [1] offset, [2] span length
-};
-
-// apply_variant_to_span :356-390: span.substr(0, off) + alt + (off + |ref| < |span| ? span.substr(off + |ref|) : "").
-// substr(0, n) never throws: an offset beyond the span (records at or below POS 0 with a long REF, groups
-// past the end of the reference) just takes the whole span; off + reflen wraps like the reference's size_t.
-__device__ __forceinline__ u64 hap_len(u64 off, u64 altlen, u64 reflen, u64 spanlen)
-{
-    u64 len = (off < spanlen ? off : spanlen) + altlen;
-    if (off + reflen < spanlen) len += spanlen - (off + reflen);
-    return len;
-}
-
-__global__ void k_grp_count(VcfDev d, GrpArrays a)
-{
-    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < d.ngrp; g += (u64)gridDim.x * blockDim.x) {
-        const u64 r0 = d.grp_r0[g], r1 = d.grp_r0[g + 1];
-        const u64 gs = d.start[r0], ge = d.incl_end[r1 - 1];
-        u64 spanlen = 0, cs = d.refc_n;
-        if (gs < d.seq_size) {                                 // read_fasta_region :102-109
-            u64 length = ge - gs;
-            if (gs + length > d.seq_size) length = d.seq_size - gs;
-            cs = fa_cpos(d, d.seq_start + gs + gs / d.lw);
-            spanlen = length < d.refc_n - cs ? length : d.refc_n - cs;
-            if (d.oob && spanlen < length) *d.oob = (d.seq_start + gs + gs / d.lw) | (1ull << 62);   // the window is too short
-        }
-        a.gs[g] = gs; a.spanlen[g] = spanlen; a.cs[g] = cs;
-        u64 nraw = 1, chars = spanlen;
-        for (u64 v = r0; v < r1; v++) {
-            const u64 off = d.start[v] - gs;
-            const u64 nalt = d.alt0[v + 1] - d.alt0[v];
-            for (u64 x = d.alt0[v]; x < d.alt0[v + 1]; x++)
-                chars += hap_len(off, d.altstr_off[x + 1] - d.altstr_off[x], d.reflen[v], spanlen);
-            nraw += nalt;
-        }
-        a.nraw[g] = nraw; a.rawchars[g] = chars;
-    }
-}
-
-struct HapArrays {
-    const u64* raw0; const u64* rawc0;       // exclusive scans of nraw / rawchars
-    u64* rawlen; u64* rawoff; u32* canon;    // per raw haplotype: length, offset in hapchars, canonical index
-    uint8_t* hapchars;
-    const u64* bit0;                         // exclusive scan of bitwords
-    u64* carried;                            // bit matrix [canonical hap][sample word]
-    u32 sw;                                  // sample words = ceil(max_samples / 64)
-};
-
-// materialise the raw haplotypes (span first, then every ALT applied alone: :416-435) and
-// deduplicate them keeping the first occurrence
-__global__ void k_grp_haps(VcfDev d, GrpArrays a, HapArrays h)
-{
-    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < d.ngrp; g += (u64)gridDim.x * blockDim.x) {
-        const u64 r0 = d.grp_r0[g], r1 = d.grp_r0[g + 1];
-        const u64 gs = a.gs[g], spanlen = a.spanlen[g], cs = a.cs[g];
-        const uint8_t* span = d.refc + cs;
-        u64 hi = h.raw0[g];
-        u64 co = h.rawc0[g];
-        // raw hap 0 = the reference span
-        h.rawlen[hi] = spanlen; h.rawoff[hi] = co;
-        for (u64 i = 0; i < spanlen; i++) h.hapchars[co + i] = span[i];
-        co += spanlen; hi++;
-        const u64 nraw = a.nraw[g];
-        for (u64 v = r0; v < r1 && hi < h.raw0[g] + nraw; v++) {
-            const u64 off = d.start[v] - gs, rl = d.reflen[v];
-            for (u64 x = d.alt0[v]; x < d.alt0[v + 1]; x++) {
-                const u64 al = d.altstr_off[x + 1] - d.altstr_off[x];
-                const u64 len = hap_len(off, al, rl, spanlen);
-                h.rawlen[hi] = len; h.rawoff[hi] = co;
-                uint8_t* dst = h.hapchars + co;
-                const u64 pre = off < spanlen ? off : spanlen;
-                for (u64 i = 0; i < pre; i++) *dst++ = span[i];
-                for (u64 i = 0; i < al; i++) *dst++ = d.altchars[d.altstr_off[x] + i];
-                if (off + rl < spanlen) for (u64 i = off + rl; i < spanlen; i++) *dst++ = span[i];
-                co += len; hi++;
-            }
-        }
-        // dedup, first occurrence wins
-        const u64 h0 = h.raw0[g];
-        u32 nd = 0;
-        for (u64 x = 0; x < nraw; x++) {
-            u32 c = 0xffffffffu;
-            for (u64 y = 0; y < x; y++) {
-                if (h.rawlen[h0 + y] != h.rawlen[h0 + x] || h.canon[h0 + y] & 0x80000000u) continue;
-                const uint8_t* p = h.hapchars + h.rawoff[h0 + x];
-                const uint8_t* q = h.hapchars + h.rawoff[h0 + y];
-                bool eq = true;
-                for (u64 i = 0; i < h.rawlen[h0 + x]; i++) if (p[i] != q[i]) { eq = false; break; }
-                if (eq) { c = h.canon[h0 + y]; break; }
-            }
-            // bit 31 marks "duplicate of an earlier one" so that only first occurrences are compared against
-            h.canon[h0 + x] = c == 0xffffffffu ? nd++ : (c | 0x80000000u);
-        }
-        a.ndist[g] = nd;
-        a.bitwords[g] = (u64)nd * h.sw;
-    }
-}
-
-// which samples carry which haplotype (:438-473) and the text sizes (:570-651)
-__global__ void k_grp_samples(VcfDev d, GrpArrays a, HapArrays h)
-{
-    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < d.ngrp; g += (u64)gridDim.x * blockDim.x) {
-        const u64 r0 = d.grp_r0[g], r1 = d.grp_r0[g + 1];
-        const u64 h0 = h.raw0[g];
-        const u64 nd = a.ndist[g];
-        u64* bits = h.carried + h.bit0[g];
-        for (u64 i = 0; i < nd * h.sw; i++) bits[i] = 0;
-        const u64 nsamp = d.pair0[r0 + 1] - d.pair0[r0];       // samples of the group's first record (:407)
-        for (u64 s = 0; s < nsamp; s++) {
-            bool any = false;
-            u64 rawbase = 1;
-            for (u64 v = r0; v < r1; v++) {
-                const u64 nalt = d.alt0[v + 1] - d.alt0[v];
-                const u64 ns_v = d.pair0[v + 1] - d.pair0[v];
-                if (s < ns_v) {
-                    const u64 pr = d.pair0[v] + s;
-                    for (u64 t = d.pair_a0[pr]; t < d.pair_a0[pr + 1]; t++) {
-                        const int al = d.alleles[t];
-                        u32 idx = 0;                           // allele 0 or out of range -> the span
-                        if (al >= 1 && (u64)al <= nalt) idx = h.canon[h0 + rawbase + (u64)(al - 1)] & 0x7fffffffu;
-                        bits[(u64)idx * h.sw + (s >> 6)] |= 1ull << (s & 63);
-                        any = true;
-                    }
-                }
-                rawbase += nalt;
-            }
-            if (!any) bits[(s >> 6)] |= 1ull << (s & 63);      // no allele at all: reference (:466-468)
-        }
-        // sizes
-        const u64 gs = a.gs[g], spanlen = a.spanlen[g];
-        u64 eds = 2, seds = 0, nemit = 0;
-        if (nsamp == 0) {                                      // no genotype columns: all haplotypes, one {0} (:603-615)
-            for (u64 x = 0; x < a.nraw[g]; x++)
-                if (!(h.canon[h0 + x] & 0x80000000u)) { eds += h.rawlen[h0 + x]; nemit++; }
-            seds = 3;
-        } else {
-            for (u64 x = 0; x < a.nraw[g]; x++) {
-                const u32 c = h.canon[h0 + x];
-                if (c & 0x80000000u) continue;
-                u64 cnt = 0, digits = 0;
-                for (u64 s = 0; s < nsamp; s++)
-                    if (bits[(u64)c * h.sw + (s >> 6)] >> (s & 63) & 1) { cnt++; digits += ndigits((u32)s + 1); }
-                if (!cnt) continue;
-                eds += h.rawlen[h0 + x]; nemit++;
-                seds += 2 + digits + (cnt - 1);
-            }
-        }
-        eds += nemit ? nemit - 1 : 0;
-        a.eds_len[g] = eds; a.seds_len[g] = seds;
-        a.cur_after[g] = gs + spanlen;                         // group.end_pos (:404)
-    }
-}
-
-// the reference flushed before group g: [end of group g-1, gs) (:570-578); thread per group, after k_grp_samples
-__global__ void k_grp_common(VcfDev d, GrpArrays a)
-{
-    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < d.ngrp; g += (u64)gridDim.x * blockDim.x) {
-        const u64 cur = g ? a.cur_after[g - 1] : d.cur0;
-        const u64 gs = a.gs[g];
-        u64 clen = 0;
-        if (gs > cur && cur < d.seq_size) {
-            u64 length = gs - cur;
-            if (cur + length > d.seq_size) length = d.seq_size - cur;
-            const u64 c0 = fa_cpos(d, d.seq_start + cur + cur / d.lw);
-            clen = length < d.refc_n - c0 ? length : d.refc_n - c0;
-            if (d.oob && clen < length) *d.oob = (d.seq_start + cur + cur / d.lw) | (1ull << 62);
-        }
-        a.commonlen[g] = clen;
-        if (clen) { a.eds_len[g] += clen + 2; a.seds_len[g] += 3; }
-    }
-}
-
-struct EmitArrays { const u64* eds_off; const u64* seds_off; uint8_t* eds; uint8_t* seds; };
+// ---- per group: thread per group (bodies and the arrays' meaning: vcf_walk.hpp) ------------------------------
+__global__ void k_grp_count(VcfDev d, GrpArrays a) { grp_count_body(d, a, WALK_THREAD); }
+__global__ void k_grp_haps(VcfDev d, GrpArrays a, HapArrays h) { grp_haps_body(d, a, h, WALK_THREAD); }
+__global__ void k_grp_samples(VcfDev d, GrpArrays a, HapArrays h) { grp_samples_body(d, a, h, WALK_THREAD); }
+__global__ void k_grp_common(VcfDev d, GrpArrays a) { grp_common_body(d, a, WALK_THREAD); }
 
 // common text in front of every group (the bandwidth part of the output).  A wave takes 64 consecutive groups: every
 // lane fetches the numbers of one group (length, offsets, position in refc - one round of dependent loads for 64
@@ -408,218 +190,27 @@ __global__ void __launch_bounds__(256) k_grp_emit_common(VcfDev d, GrpArrays a, 
     }
 }
 
-// the group symbols: short texts behind a chain of dependent loads, so one THREAD per group — a million independent
-// chains in flight hide the latency that one lane per wave could not (3.7 ms -> see DESIGN section 5)
-__global__ void __launch_bounds__(256) k_grp_emit(VcfDev d, GrpArrays a, HapArrays h, EmitArrays e)
-{
-    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < d.ngrp; g += (u64)gridDim.x * blockDim.x) {
-        uint8_t* eo = e.eds + e.eds_off[g];
-        uint8_t* so = e.seds + e.seds_off[g];
-        const u64 clen = a.commonlen[g];
-        if (clen) { eo += clen + 2; so += 3; }
-        const u64 r0 = d.grp_r0[g];
-        const u64 h0 = h.raw0[g];
-        const u64 nsamp = d.pair0[r0 + 1] - d.pair0[r0];
-        const u64* bits = h.carried + h.bit0[g];
-        *eo++ = '{';
-        bool first = true;
-        for (u64 x = 0; x < a.nraw[g]; x++) {
-            const u32 c = h.canon[h0 + x];
-            if (c & 0x80000000u) continue;
-            // carriers of this haplotype: one load per 64 samples (a per-sample load could not be kept in a register
-            // across the byte stores below, which may alias it as far as the compiler knows)
-            const u64* bw = bits + (u64)c * h.sw;
-            const u32 nw = (u32)((nsamp + 63) >> 6);
-            u64 cnt = 0;
-            if (nsamp) {
-                for (u32 w = 0; w < nw; w++) {
-                    const u64 rem = nsamp - 64ull * w;
-                    cnt += __builtin_popcountll(bw[w] & (rem >= 64 ? ~0ull : ((1ull << rem) - 1ull)));
-                }
-                if (!cnt) continue;
-            }
-            if (!first) *eo++ = ',';
-            first = false;
-            const uint8_t* src = h.hapchars + h.rawoff[h0 + x];
-            for (u64 i = 0; i < h.rawlen[h0 + x]; i++) *eo++ = src[i];
-            if (nsamp) {
-                *so++ = '{';
-                for (u32 w = 0; w < nw; w++) {
-                    const u64 rem = nsamp - 64ull * w;
-                    u64 v = bw[w] & (rem >= 64 ? ~0ull : ((1ull << rem) - 1ull));
-                    while (v) {
-                        const u32 id = w * 64u + (u32)__builtin_ctzll(v) + 1u, nd = ndigits(id);
-                        v &= v - 1;
-                        u32 xx = id;
-                        for (int dd = (int)nd - 1; dd >= 0; dd--) { so[dd] = (uint8_t)('0' + xx % 10); xx /= 10; }
-                        so += nd;
-                        *so++ = ',';
-                    }
-                }
-                so[-1] = '}';
-            }
-        }
-        *eo++ = '}';
-        if (!nsamp) { so[0] = '{'; so[1] = '0'; so[2] = '}'; }
-    }
-}
+__global__ void __launch_bounds__(256) k_grp_emit(VcfDev d, GrpArrays a, HapArrays h, EmitArrays e) { grp_emit_body(d, a, h, e, WALK_THREAD); }
+__global__ void k_cpos(VcfDev d, u64 file_off, u64* out) { cpos_body(d, file_off, out, WALK_THREAD); }
+__global__ void k_tail(VcfDev d, u64 cur, u64 clen, uint8_t* eo, uint8_t* so) { tail_body(d, cur, clen, eo, so, WALK_THREAD); }
 
-__global__ void k_cpos(VcfDev d, u64 file_off, u64* out) { *out = fa_cpos(d, file_off); }
-
-// tail flush (:658-665)
-__global__ void k_tail(VcfDev d, u64 cur, u64 clen, uint8_t* eo, uint8_t* so)
-{
-    const u64 c0 = fa_cpos(d, d.seq_start + cur + cur / d.lw);
-    const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (t == 0) { eo[0] = '{'; eo[clen + 1] = '}'; so[0] = '{'; so[1] = '0'; so[2] = '}'; }
-    for (u64 i = t; i < clen; i += (u64)gridDim.x * blockDim.x) eo[1 + i] = d.refc[c0 + i];
-}
-
-
-// ---- device tokeniser (parse_vcf_line :232-326, parse_alt_field :142-176, parse_genotype :190-216) -------
-// The VCF text goes to HBM as it is; record lines are found with a flag scan, a thread per record line walks its
-// fields twice (count, then fill in sorted order) and writes the record SoA above — no host records, no uploads
-// of eight arrays.  The kernels accept the *plain* spelling only: tab-separated lines without empty fields and
-// with at least five of them, POS all digits (<= 19), no symbolic ALT other than <DEL>/<INS>, genotype alleles
-// that are "." or all digits (<= 9), no '\r'.  Anything else — the whitespace-separated fallback of :262-279,
-// malformed lines, unsupported structural variants (their warnings are in file order), signs or junk that
-// std::stoull/stoi would swallow, POS 0 — raises `bad`, and the host tokeniser takes the whole file.
-
-struct VtSink {                      // fill pass: where record j's pieces go
-    u64* altoff; u64 altc_base; uint8_t* altchars; u64* pa0; u64 all_base; int* alleles;
-};
-struct VtCounts { u64 pos; u64 reflen, nalt, altc, ngt, nall; };
-
-
-template <bool FILL>
-__device__ bool vt_parse(ByteWindow& raw, u64 lo, u64 hi, VtCounts& c, const VtSink& k)
-{
-    c = VtCounts{0, 0, 0, 0, 0, 0};
-    u64 fs = lo, ref_lo = 0;
-    int f = 0;
-    for (u64 i = lo; i <= hi; i++) {
-        if (i < hi && raw[i] != '\t') continue;
-        const u64 fe = i;
-        if (fe == fs) return false;                                      // empty token: the reference drops it (:262-268)
-        if (f == 1) {
-            if (fe - fs > 19) return false;
-            u64 v = 0;
-            for (u64 t = fs; t < fe; t++) { const uint8_t ch = raw[t]; if (ch < '0' || ch > '9') return false; v = v * 10 + (ch - '0'); }
-            c.pos = v;
-        } else if (f == 3) { ref_lo = fs; c.reflen = fe - fs; }
-        else if (f == 4) {
-            u64 t = fs;
-            while (t < fe) {                                             // std::getline(ss, a, ',')
-                u64 e = t;
-                while (e < fe && raw[e] != ',') e++;
-                const u64 len = e - t;
-                u64 src = t;                                             // index of the allele's first byte in the text
-                u64 alen = len;
-                if (len && raw[t] == '<' && raw[e - 1] == '>') {
-                    if (len == 5 && raw[t + 1] == 'D' && raw[t + 2] == 'E' && raw[t + 3] == 'L') alen = 0;
-                    else if (len == 5 && raw[t + 1] == 'I' && raw[t + 2] == 'N' && raw[t + 3] == 'S') { src = ref_lo; alen = c.reflen; }
-                    else return false;                                   // unsupported SV: warning + skip on the host
-                }
-                if (FILL) {
-                    k.altoff[c.nalt] = k.altc_base + c.altc;
-                    for (u64 x = 0; x < alen; x++) k.altchars[k.altc_base + c.altc + x] = raw[src + x];
-                }
-                c.nalt++; c.altc += alen;
-                t = e + 1;
-            }
-        } else if (f >= 9) {
-            u64 ge = fs;
-            bool slash = false;
-            while (ge < fe && raw[ge] != ':') { slash |= raw[ge] == '/'; ge++; }
-            const uint8_t delim = slash ? '/' : '|';
-            if (FILL) k.pa0[c.ngt] = k.all_base + c.nall;
-            u64 t = fs;
-            while (t < ge) {
-                u64 e = t;
-                while (e < ge && raw[e] != delim) e++;
-                const u64 len = e - t;
-                if (len && !(len == 1 && raw[t] == '.')) {
-                    if (len > 9) return false;
-                    int v = 0;
-                    for (u64 x = t; x < e; x++) { const uint8_t ch = raw[x]; if (ch < '0' || ch > '9') return false; v = v * 10 + (ch - '0'); }
-                    if (FILL) k.alleles[k.all_base + c.nall] = v;
-                    c.nall++;
-                }
-                t = e + 1;
-            }
-            c.ngt++;
-        }
-        f++;
-        fs = i + 1;
-    }
-    return f >= 5;
-}
-
-__device__ __forceinline__ u64 vt_line_end(ByteWindow& raw, u64 lo, u64 n)
-{
-    u64 hi = lo;
-    while (hi < n && raw[hi] != '\n') hi++;
-    return hi;
-}
-struct VtRec { u64* pos; u64* reflen; u64* nalt; u64* altc; u64* ngt; u64* nall; u64* linelen; /* may be null */ };
+// ---- device tokeniser: vt_parse and the bodies are in vcf_walk.hpp ---------------------------------------------
 __global__ void k_vt_count(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ lstart, u64 nrec, VtRec r, VtCtl* ctl)
 {
-    bool bad = false;
-    u64 mx = 0;
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
-        ByteWindow win(raw, n);
-        const u64 lo = lstart[j], hi = vt_line_end(win, lo, n);
-        VtCounts c;
-        if (lo >= n) { ctl->oob = lo | (1ull << 62); bad = true; continue; }
-        if (!vt_parse<false>(win, lo, hi, c, VtSink{})) bad = true;
-        if (win.oob) ctl->oob = win.oob;
-        if (r.linelen) r.linelen[j] = hi - lo;                               // index pass of a partitioned run
-        else if (c.pos == 0 || c.pos - 1 + c.reflen < c.pos - 1) bad = true; // wrapped positions: host sweep (see run)
-        r.pos[j] = c.pos; r.reflen[j] = c.reflen; r.nalt[j] = c.nalt; r.altc[j] = c.altc; r.ngt[j] = c.ngt; r.nall[j] = c.nall;
-        mx = c.ngt > mx ? c.ngt : mx;
-    }
-    if (bad) ctl->bad = 1;
-    if (mx) atomicMax((unsigned long long*)&ctl->max_samples, (unsigned long long)mx);
+    vt_count_body(raw, n, lstart, nrec, r, ctl, WALK_THREAD);
 }
-// strictly ascending positions: the reference's std::sort leaves such an array as it is (no two keys compare equal,
-// so its result is THE sorted order) and the host sort, with its two PCIe trips, is skipped
-__global__ void k_vt_ascending(const u64* __restrict__ pos, u64 nrec, VtCtl* ctl)
-{
-    bool un = false;
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j + 1 < nrec; j += (u64)gridDim.x * blockDim.x) un |= pos[j] >= pos[j + 1];
-    if (un) ctl->t_alt = 1;                                      // scratch until the offset scans overwrite it
-}
-// counts in sorted order (inputs of the four offset scans)
+__global__ void k_vt_ascending(const u64* __restrict__ pos, u64 nrec, VtCtl* ctl) { vt_ascending_body(pos, nrec, ctl, WALK_THREAD); }
 __global__ void k_vt_gather(VtRec r, const u32* __restrict__ order, u64 nrec, u64* __restrict__ a, u64* __restrict__ b,
                             u64* __restrict__ c, u64* __restrict__ d)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
-        const u64 i = order ? order[j] : j;
-        a[j] = r.nalt[i]; b[j] = r.altc[i]; c[j] = r.ngt[i]; d[j] = r.nall[i];
-    }
+    vt_gather_body(r, order, nrec, a, b, c, d, WALK_THREAD);
 }
-struct VtOut { u64* start; u64* reflen; u64* alt0; u64* altoff; uint8_t* altchars; u64* pair0; u64* pa0; int* alleles;
-               const u64* altc0; const u64* gtc0; };
 __global__ void k_vt_fill(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ lstart, const u32* __restrict__ order,
                           u64 nrec, VtOut o, VtCtl* ctl)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
-        const u64 lo = lstart[order ? order[j] : j];
-        VtCounts c;
-        VtSink k{o.altoff + o.alt0[j], o.altc0[j], o.altchars, o.pa0 + o.pair0[j], o.gtc0[j], o.alleles};
-        ByteWindow win(raw, n);
-        const u64 hi = vt_line_end(win, lo, n);
-        if (lo < n) vt_parse<true>(win, lo, hi, c, k);
-        else ctl->oob = lo | (1ull << 62);
-        if (win.oob) ctl->oob = win.oob;
-        o.start[j] = c.pos - 1;
-        o.reflen[j] = c.reflen;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        o.alt0[nrec] = ctl->t_alt; o.altoff[ctl->t_alt] = ctl->t_altc;
-        o.pair0[nrec] = ctl->t_pair; o.pa0[ctl->t_pair] = ctl->t_all;
-    }
+    vt_fill_body(raw, n, lstart, order, nrec, o, ctl, WALK_THREAD);
 }
+#undef WALK_THREAD
 
 // ---- host ------------------------------------------------------------------------------------------
 namespace {
@@ -846,11 +437,11 @@ bool VcfPipeline::tokenize_device(const uint8_t* vcf, size_t n, bool presorted, 
     { const char* e = getenv("EDSX_HOST_TOKENIZER"); if (e && atoi(e)) return false; }      // A/B switch for the parity tests
     nrec = 0; max_samples = 0;
     if (n == 0 || !device_scratch_fits(6 * n)) return false;   // raw text + the record arrays (a dozen u64 per record line)
-    vt_raw_.ensure(n + 16);
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
-    vt_idx_.ensure(8 * (nblk + 2));                            // line starts per 1 KB block of the text
+    vt_raw_.ensure(vcf_size::text(n));
+    const u64 nblk = vcf_size::line_blocks(n);
+    vt_idx_.ensure(vcf_size::line_counts(nblk));                            // line starts per 1 KB block of the text
     scan_tmp_.ensure(8 * ((n + 2) / SCAN_TILE + 4));
-    ctl_.ensure(8 * 32);
+    ctl_.ensure(vcf_size::ctl());
     VtCtl* ctl = reinterpret_cast<VtCtl*>(ctl_.as<u64>() + 16);
     VtCtl h{};
     h.n = nblk;                                                // element count of the block scan
@@ -865,7 +456,7 @@ bool VcfPipeline::tokenize_device(const uint8_t* vcf, size_t n, bool presorted, 
     if (h.bad || h.nrec >= 0xffffffffull) return false;
     const u64 nr = h.nrec;
     if (nr) {
-        vt_lstart_.ensure(8 * (nr + 1));
+        vt_lstart_.ensure(vcf_size::line_starts(nr));
         hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_idx_.as<u64>(), vt_lstart_.as<u64>());
     }
     return tokenize_lines(raw, n, vt_lstart_.as<u64>(), nr, presorted, st, nrec, max_samples, stats);
@@ -882,11 +473,11 @@ bool VcfPipeline::tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u
     if (nr == 0) return true;
     if (nr >= 0xffffffffull) return false;
     scan_tmp_.ensure(8 * ((nr + 2) / SCAN_TILE + 4));
-    ctl_.ensure(8 * 32);
+    ctl_.ensure(vcf_size::ctl());
     VtCtl* ctl = reinterpret_cast<VtCtl*>(ctl_.as<u64>() + 16);
     VtCtl h{};
     EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
-    for (DevBuf* b : {&vt_pos_, &vt_reflen_, &vt_nalt_, &vt_altc_, &vt_ngt_, &vt_nall_, &vt_s1_, &vt_s2_, &vt_s3_, &vt_s4_}) b->ensure(8 * (nr + 2));
+    for (DevBuf* b : {&vt_pos_, &vt_reflen_, &vt_nalt_, &vt_altc_, &vt_ngt_, &vt_nall_, &vt_s1_, &vt_s2_, &vt_s3_, &vt_s4_}) b->ensure(vcf_size::per_record(nr));
     VtRec rec{vt_pos_.as<u64>(), vt_reflen_.as<u64>(), vt_nalt_.as<u64>(), vt_altc_.as<u64>(), vt_ngt_.as<u64>(), vt_nall_.as<u64>(), nullptr};
     TraceSpan count_span(st, "tokeniser count pass", 0);
     hipLaunchKernelGGL(k_vt_count, dim3(2048), dim3(256), 0, st, raw, (u64)n, lstart, nr, rec, ctl);
@@ -906,7 +497,7 @@ bool VcfPipeline::tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u
         // Not ascending.  If the positions are pairwise distinct there is exactly one sorted order, so a device radix
         // sort gives the reference's permutation; equal positions (checked on the sorted keys) need the host's
         // std::sort, whose unstable permutation of them is part of the output.
-        vt_s2_.ensure(8 * (nr + 2)); vt_order_.ensure(4 * (nr + 1));
+        vt_s2_.ensure(vcf_size::per_record(nr)); vt_order_.ensure(vcf_size::order(nr));
         {   // eight passes: positions -> tmp -> (vt_s2_, vt_order_) -> tmp ... the last pass ends in (vt_s2_, vt_order_)
             const u64 ntiles = (nr + RS_TILE - 1) / RS_TILE, nbins = 256 * ntiles;
             vt_sorttmp_.ensure(12 * (nr + 2) + 8 * (nbins + 2) + 64);
@@ -942,7 +533,7 @@ bool VcfPipeline::tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u
         { const char* e = getenv("EDSX_TRACE");
           if (e && atoi(e)) fprintf(stderr, "[edsx vcf]   std::sort of %llu positions %8.3f ms\n", (unsigned long long)nr,
                                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count()); }
-        vt_order_.ensure(4 * (nr + 1));
+        vt_order_.ensure(vcf_size::order(nr));
         EDSX_HIP(hipMemcpyAsync(vt_order_.ptr, order.data(), 4 * nr, hipMemcpyHostToDevice, st));
         d_order = vt_order_.as<u32>();
     }
@@ -950,14 +541,15 @@ bool VcfPipeline::tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u
     EDSX_HIP(hipMemcpyAsync(&ctl->n, &h.n, 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_vt_gather, dim3(2048), dim3(256), 0, st, rec, d_order, nr, vt_s1_.as<u64>(), vt_s2_.as<u64>(),
                        vt_s3_.as<u64>(), vt_s4_.as<u64>());
-    alt0_.ensure(8 * (nr + 2)); pair0_.ensure(8 * (nr + 2)); start_.ensure(8 * (nr + 2)); reflen_.ensure(8 * (nr + 2));
+    for (DevBuf* b : {&alt0_, &pair0_, &start_, &reflen_}) b->ensure(vcf_size::per_record(nr));
     exclusive_scan_u64(vt_s1_.as<u64>(), alt0_.as<u64>(), &ctl->n, &ctl->t_alt, scan_tmp_.as<u64>(), st);
     exclusive_scan_u64(vt_s2_.as<u64>(), vt_s2_.as<u64>(), &ctl->n, &ctl->t_altc, scan_tmp_.as<u64>(), st);
     exclusive_scan_u64(vt_s3_.as<u64>(), pair0_.as<u64>(), &ctl->n, &ctl->t_pair, scan_tmp_.as<u64>(), st);
     exclusive_scan_u64(vt_s4_.as<u64>(), vt_s4_.as<u64>(), &ctl->n, &ctl->t_all, scan_tmp_.as<u64>(), st);
     EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));                          // also: `order` stays alive until its upload is done
-    altoff_.ensure(8 * (h.t_alt + 2)); altchars_.ensure(h.t_altc + 16); pa0_.ensure(8 * (h.t_pair + 2)); alleles_.ensure(4 * (h.t_all + 4));
+    altoff_.ensure(vcf_size::altoff(h.t_alt)); altchars_.ensure(vcf_size::altchars(h.t_altc)); pa0_.ensure(vcf_size::pa0(h.t_pair));
+    alleles_.ensure(vcf_size::alleles(h.t_all));
     VtOut o{start_.as<u64>(), reflen_.as<u64>(), alt0_.as<u64>(), altoff_.as<u64>(), altchars_.as<uint8_t>(), pair0_.as<u64>(),
             pa0_.as<u64>(), alleles_.as<int>(), vt_s2_.as<u64>(), vt_s4_.as<u64>()};
     hipLaunchKernelGGL(k_vt_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, lstart, d_order, nr, o, ctl);
@@ -979,11 +571,11 @@ bool VcfPipeline::index_device(const uint8_t* vcf, size_t n, hipStream_t st, std
 {
     { const char* e = getenv("EDSX_HOST_TOKENIZER"); if (e && atoi(e)) return false; }
     if (n == 0 || !device_scratch_fits(6 * n)) return false;
-    vt_raw_.ensure(n + 16);
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
-    vt_idx_.ensure(8 * (nblk + 2));                            // line starts per 1 KB block of the text
+    vt_raw_.ensure(vcf_size::text(n));
+    const u64 nblk = vcf_size::line_blocks(n);
+    vt_idx_.ensure(vcf_size::line_counts(nblk));                            // line starts per 1 KB block of the text
     scan_tmp_.ensure(8 * ((n + 2) / SCAN_TILE + 4));
-    ctl_.ensure(8 * 32);
+    ctl_.ensure(vcf_size::ctl());
     VtCtl* ctl = reinterpret_cast<VtCtl*>(ctl_.as<u64>() + 16);
     VtCtl h{};
     h.n = nblk;                                                // element count of the block scan
@@ -1000,9 +592,9 @@ bool VcfPipeline::index_device(const uint8_t* vcf, size_t n, hipStream_t st, std
     stats.total_variants = stats.processed_variants = nr;
     pos.assign(nr, 0); reflen.assign(nr, 0); line_off.assign(nr, 0); line_len.assign(nr, 0);
     if (nr == 0) return true;
-    vt_lstart_.ensure(8 * (nr + 1));
+    vt_lstart_.ensure(vcf_size::line_starts(nr));
     hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_idx_.as<u64>(), vt_lstart_.as<u64>());
-    for (DevBuf* b : {&vt_pos_, &vt_reflen_, &vt_nalt_, &vt_altc_, &vt_ngt_, &vt_nall_, &vt_s1_}) b->ensure(8 * (nr + 2));
+    for (DevBuf* b : {&vt_pos_, &vt_reflen_, &vt_nalt_, &vt_altc_, &vt_ngt_, &vt_nall_, &vt_s1_}) b->ensure(vcf_size::per_record(nr));
     VtRec rec{vt_pos_.as<u64>(), vt_reflen_.as<u64>(), vt_nalt_.as<u64>(), vt_altc_.as<u64>(), vt_ngt_.as<u64>(), vt_nall_.as<u64>(),
               vt_s1_.as<u64>()};
     hipLaunchKernelGGL(k_vt_count, dim3(2048), dim3(256), 0, st, raw, (u64)n, vt_lstart_.as<u64>(), nr, rec, ctl);
@@ -1129,18 +721,18 @@ bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
     }
     const u64 up_n = up1 - up0, cbase = window ? up0 : seq_start;
     if (!fasta_resident) {
-        d_fasta_.ensure(up_n + 16);
+        d_fasta_.ensure(vcf_size::fasta(up_n));
         if (up_n) EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta + up0, up_n, hipMemcpyHostToDevice, st));
         fasta_h2d_ = up_n;
     }
     const uint8_t* const dfa = fasta_resident ? res->d_fasta : d_fasta_.as<uint8_t>();
     const u64 body = window ? up_n : fasta_n > seq_start ? fasta_n - seq_start : 0;
-    const u64 nblk = (body + 255) / 256;
-    ctl_.ensure(8 * 32);
+    const u64 nblk = vcf_size::ref_blocks(body);
+    ctl_.ensure(vcf_size::ctl());
     u64* ctl = ctl_.as<u64>();
-    blkpre_.ensure(8 * (nblk + 2));
+    blkpre_.ensure(vcf_size::blkpre(nblk));
     scan_tmp_.ensure(8 * ((std::max<u64>(nblk, nrec) + 2) / SCAN_TILE + 4));
-    refc_.ensure(body + 16);
+    refc_.ensure(vcf_size::refc(body));
     u64 hctl[32] = {0};
     hctl[0] = nblk; hctl[10] = ~0ull;
     hctl[12] = fasta_n;                                      // record end (atomicMin), [13] bytes of the later lines
@@ -1234,7 +826,7 @@ bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         d.altchars = altchars_.as<uint8_t>(); d.pair0 = pair0_.as<u64>(); d.pair_a0 = pa0_.as<u64>(); d.alleles = alleles_.as<int>();
 
         // ---- groups
-        ends_.ensure(8 * (nrec + 2)); flag_.ensure(8 * (nrec + 2)); gidx_.ensure(8 * (nrec + 2)); grp_r0_.ensure(8 * (nrec + 2));
+        for (DevBuf* b : {&ends_, &flag_, &gidx_, &grp_r0_}) b->ensure(vcf_size::per_record(nrec));
         hctl[0] = nrec;
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, 8, hipMemcpyHostToDevice, st));
         // The parallel rule "a record opens a group iff its start is not below the largest end seen so far" equals
@@ -1270,12 +862,11 @@ bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
 
         // ---- per group
         for (DevBuf* b : {&g_gs_, &g_spanlen_, &g_cs_, &g_nraw_, &g_rawchars_, &g_ndist_, &g_bitwords_, &g_eds_, &g_seds_,
-                          &g_common_, &g_cur_}) b->ensure(8 * (ngrp + 2));
+                          &g_common_, &g_cur_, &raw0_, &rawc0_, &bit0_}) b->ensure(vcf_size::per_group(ngrp));
         ga = GrpArrays{g_gs_.as<u64>(), g_spanlen_.as<u64>(), g_cs_.as<u64>(), g_nraw_.as<u64>(), g_rawchars_.as<u64>(),
                      g_ndist_.as<u64>(), g_bitwords_.as<u64>(), g_eds_.as<u64>(), g_seds_.as<u64>(), g_common_.as<u64>(),
                        g_cur_.as<u64>(), ctl + 10};
         scan_tmp_.ensure(8 * ((ngrp + 2) / SCAN_TILE + 4));
-        raw0_.ensure(8 * (ngrp + 2)); rawc0_.ensure(8 * (ngrp + 2)); bit0_.ensure(8 * (ngrp + 2));
         hctl[0] = ngrp;
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_grp_count, dim3(1024), dim3(256), 0, st, d, ga);
@@ -1285,15 +876,15 @@ bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         EDSX_HIP(hipStreamSynchronize(st));
         const u64 nraw_total = hctl[4], rawchars_total = hctl[5];
         const u32 sw = (u32)std::max<u64>(1, (max_samples + 63) / 64);
-        rawlen_.ensure(8 * (nraw_total + 2)); rawoff_.ensure(8 * (nraw_total + 2)); canon_.ensure(4 * (nraw_total + 2));
-        hapchars_.ensure(rawchars_total + 16);
+        rawlen_.ensure(vcf_size::per_raw(nraw_total)); rawoff_.ensure(vcf_size::per_raw(nraw_total)); canon_.ensure(vcf_size::canon(nraw_total));
+        hapchars_.ensure(vcf_size::hapchars(rawchars_total));
         ha = HapArrays{raw0_.as<u64>(), rawc0_.as<u64>(), rawlen_.as<u64>(), rawoff_.as<u64>(), canon_.as<u32>(),
                        hapchars_.as<uint8_t>(), bit0_.as<u64>(), nullptr, sw};
         hipLaunchKernelGGL(k_grp_haps, dim3(1024), dim3(256), 0, st, d, ga, ha);
         exclusive_scan_u64(ga.bitwords, bit0_.as<u64>(), ctl + 0, ctl + 6, scan_tmp_.as<u64>(), st);
         EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
-        carried_.ensure(8 * (hctl[6] + 2));
+        carried_.ensure(vcf_size::carried(hctl[6]));
         ha.carried = carried_.as<u64>();
         hipLaunchKernelGGL(k_grp_samples, dim3(1024), dim3(256), 0, st, d, ga, ha);
         hipLaunchKernelGGL(k_grp_common, dim3(1024), dim3(256), 0, st, d, ga);
@@ -1324,7 +915,7 @@ bool VcfPipeline::run(const uint8_t* vcf, size_t vcf_n, const uint8_t* fasta, si
         if (window && tail < length) window_check((seq_start + cur + cur / lw) | (1ull << 62));
     }
     const u64 Etot = E + (tail ? tail + 2 : 0), Qtot = Q + (tail ? 3 : 0);
-    d_eds_.ensure(Etot + 16); d_seds_.ensure(Qtot + 16);
+    d_eds_.ensure(vcf_size::eds(Etot)); d_seds_.ensure(vcf_size::eds(Qtot));
     if (ngrp) {
         EmitArrays ea{g_eds_.as<u64>(), g_seds_.as<u64>(), d_eds_.as<uint8_t>(), d_seds_.as<uint8_t>()};
         hipLaunchKernelGGL(k_grp_emit_common, dim3(2048), dim3(256), 0, st, d, ga, ea);

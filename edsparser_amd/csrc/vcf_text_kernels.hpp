@@ -4,49 +4,13 @@
 #pragma once
 
 #include "dev_util.hpp"
+#include "vcf_walk.hpp"
 
 namespace edsx {
 
-struct VtCtl { u64 n, bad, nrec, max_samples, t_alt, t_altc, t_pair, t_all, oob; };
-
-// The bytes of the VCF text through 8-byte aligned loads.  A thread walks its line from left to right, so seven of
-// eight byte reads come out of the register window instead of a one-byte load each (k_vt_count 0.80 -> 0.65 ms,
-// k_vt_fill 0.96 -> 0.75 ms per 10^6 records, round 2).  Bounds: the text buffer starts 256-byte aligned (hipMalloc) and
-// is allocated with at least 16 bytes of slack behind its n bytes (vt_raw_.ensure(n + 16)), so the aligned word that
-// holds a byte i < n - the only bytes ever asked for - ends at most 7 bytes behind n, inside the allocation.
-struct ByteWindow {
-    const u64* words; u64 nbytes; u64 at = ~0ull; u64 v = 0; u64 oob = 0;
-    __device__ __forceinline__ ByteWindow(const uint8_t* raw, u64 n) : words(reinterpret_cast<const u64*>(raw)), nbytes(n) {}
-    __device__ __forceinline__ uint8_t operator[](u64 i)
-    {
-        if (i >= nbytes) { oob = i | (1ull << 63); return (uint8_t)'\n'; }   // never asked for by a correct walk: reported, not read
-        const u64 wi = i >> 3;
-        if (wi != at) { at = wi; v = words[wi]; }
-        return (uint8_t)(v >> ((i & 7u) * 8u));
-    }
-};
-
-// Record-line starts without a flag and an index word per input BYTE (that scratch, 16 B per byte, sent VCFs of more than
-// a few GB to the host tokeniser): a wave owns 1024 bytes of the text (16 per lane); pass 1 counts the line starts of
-// every such block, a scan over the BLOCK counts (8 B per KB of text) numbers them, pass 2 finds them again and writes
-// their positions.  A byte starts a record line iff it follows a newline (or is the first byte) and is neither a
-// newline nor '#'.
-constexpr u64 VT_BLOCK = 1024;
-__device__ __forceinline__ u32 chunk_eq16b(const uint4& a, uint32_t cccc)      // bit i: byte i equals c
-{
-    return eq_byte4(a.x, cccc) | (eq_byte4(a.y, cccc) << 4) | (eq_byte4(a.z, cccc) << 8) | (eq_byte4(a.w, cccc) << 12);
-}
-__device__ __forceinline__ u32 vt_line_start_mask(const uint8_t* __restrict__ raw, u64 n, u64 i0, bool& saw_cr)
-{
-    if (i0 >= n) return 0;
-    const uint4 v = *reinterpret_cast<const uint4*>(raw + i0);            // (the text buffer is 256-byte aligned, 16 bytes of slack)
-    const u32 nl = chunk_eq16b(v, 0x0a0a0a0au), hash = chunk_eq16b(v, 0x23232323u);
-    if (chunk_eq16b(v, 0x0d0d0d0du) & (n - i0 >= 16 ? 0xffffu : (1u << (n - i0)) - 1u)) saw_cr = true;
-    const u32 prev_nl = ((nl << 1) | (i0 == 0 || raw[i0 - 1] == '\n' ? 1u : 0u)) & 0xffffu;
-    u32 m = prev_nl & ~nl & ~hash;
-    if (n - i0 < 16) m &= (1u << (n - i0)) - 1u;
-    return m;
-}
+// VtCtl, ByteWindow (the text through 8-byte aligned loads), VT_BLOCK and vt_line_start_mask: vcf_walk.hpp, which the
+// host twin compiles too.  A wave owns VT_BLOCK bytes of the text (16 per lane); pass 1 counts the line starts of every
+// such block, a scan over the block counts numbers them, pass 2 finds them again and writes their positions.
 static __global__ void __launch_bounds__(256) k_vt_line_count(const uint8_t* __restrict__ raw, u64 n, u64* __restrict__ cnt, VtCtl* ctl)
 {
     const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;

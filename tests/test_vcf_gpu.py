@@ -230,7 +230,7 @@ def test_large_outputs_every_size_remainder(ctx):
 
 
 def test_text_length_every_remainder_mod_8_with_and_without_final_newline(ctx):
-    """The device tokeniser reads the text through aligned 8-byte words (ByteWindow, csrc/vcf_device.hip): the last line
+    """The device tokeniser reads the text through aligned 8-byte words (ByteWindow, csrc/vcf_walk.hpp): the last line
     may end anywhere inside its word.  Text lengths 0..7 modulo 8 (a comment line of adjustable length in front), with
     and without the final newline, last record with a long ALT, an <INS> (copies REF) and a <DEL>; and a text whose
     length is just below / at / above multiples of 256 (the allocation granule of the text buffer)."""

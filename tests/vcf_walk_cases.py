@@ -1,0 +1,248 @@
+"""Inputs of the host twin of the VCF transform (tests/cpp/test_vcf_walk.cpp: the device's per-thread code, csrc/vcf_walk.hpp,
+run on the CPU under the address and undefined-behaviour sanitizers) and the twin itself: case files, the build, the
+results.  No oracle imports: tests/test_vcf_walk_cpu.py and tests/test_vcf_walk_gpu.py bring the expected bytes."""
+import json
+import os
+import random
+import struct
+import subprocess
+
+import vcf_cases as vc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+FILLS = (0x00, 0x0A, 0xFF, 0x09)                 # what a fresh buffer may hold: NUL, line feeds, 0xFF, tabs
+FULL, COUNT, CPOS_WINDOW, CPOS_FILE = 0, 1, 2, 3
+ACCEPTED, NOT_PLAIN, EQUAL_POS, OOB, REFUSED, CPOS_DIFFERS = 0, 1, 2, 3, 4, 5
+HEAD = ["##fileformat=VCFv4.2", "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"])]
+
+
+# ---- the program ---------------------------------------------------------------------------------------------------
+def build_test_vcf_walk(root, out, sanitize=True):
+    """tests/cpp/test_vcf_walk.cpp (host code only: no device library) with the address and undefined-behaviour sanitizers,
+    or plain (sanitize=False: for a caller that wants the program's verdicts only, as the GPU tests do)."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan"] if sanitize else []
+    cmd = ["g++", "-std=c++17", "-O1", "-g"] + san + ["-I", root + "/edsparser_amd/csrc", root + "/tests/cpp/test_vcf_walk.cpp", "-o", out]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+def write_cases(path, cases):
+    """cases: (mode, fills, name, vcf, fasta[, up0, up1])"""
+    with open(path, "wb") as f:
+        for c in cases:
+            mode, fills, name, vcf, fasta = c[:5]
+            up0, up1 = (c[5], c[6]) if len(c) > 5 else (0, 0)
+            nm = name.encode()
+            f.write(struct.pack("<II", mode, len(fills)) + bytes(fills) + struct.pack("<I", len(nm)) + nm +
+                    struct.pack("<Q", len(vcf)) + vcf + struct.pack("<Q", len(fasta)) + fasta + struct.pack("<QQ", up0, up1))
+
+
+def read_results(path):
+    """{name: [(fill, verdict, detail, eds, seds)]} in fill order"""
+    data = open(path, "rb").read()
+    at, out = 0, {}
+    while at < len(data):
+        (nl,) = struct.unpack_from("<I", data, at); at += 4
+        name = data[at:at + nl].decode(); at += nl
+        fill, verdict, detail, en = struct.unpack_from("<IIQQ", data, at); at += 24
+        eds = data[at:at + en]; at += en
+        (sn,) = struct.unpack_from("<Q", data, at); at += 8
+        seds = data[at:at + sn]; at += sn
+        out.setdefault(name, []).append((fill, verdict, detail, eds, seds))
+    return out
+
+
+def run_twin(exe, workdir, cases, tag="cases"):
+    """Runs the cases; a sanitizer report ends the program with a non-zero status, which fails here with the report."""
+    names = [c[2] for c in cases]
+    assert len(set(names)) == len(names), "case names must be unique"
+    cf, rf = os.path.join(workdir, tag + ".bin"), os.path.join(workdir, tag + ".out")
+    write_cases(cf, cases)
+    r = subprocess.run([exe, cf, rf], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-6000:]
+    res = read_results(rf)
+    assert sum(len(v) for v in res.values()) == sum(len(c[1]) for c in cases)
+    return res
+
+
+def positions(vcf):
+    """POS of every line the twin would take for a record, where it is a number"""
+    out = []
+    for line in vcf.split(b"\n"):
+        if line and not line.startswith(b"#"):
+            f = line.split(b"\t")
+            if len(f) > 1 and f[1].isdigit():
+                out.append(int(f[1]))
+    return out
+
+
+def distinct_positions(vcf):
+    p = positions(vcf)
+    return len(set(p)) == len(p)
+
+
+# ---- cases ---------------------------------------------------------------------------------------------------------
+def fixture_cases():
+    """every input of tests/golden/gen_vcf.json and gen2_vcf.json: (name, vcf, fasta)"""
+    out = []
+    for fn in ("gen_vcf.json", "gen2_vcf.json"):
+        for i, c in enumerate(json.load(open(os.path.join(GOLDEN, fn)))["cases"]):
+            out.append(("%s/%d/%s" % (fn, i, c.get("name", "")), c["vcf"].encode(), c["fasta"].encode()))
+    return out
+
+
+def _fasta(ref, lw, end="\n", eol="\n"):
+    return (">chr1 synthetic" + eol + eol.join(ref[i:i + lw] for i in range(0, len(ref), lw)) + end).encode()
+
+
+def _body(rng, ref, n, ns, top=None):
+    """n record lines at pairwise distinct positions below `top`"""
+    recs = vc.random_records(rng, ref[:top or len(ref)], n, ns)
+    return ["\t".join(["chr1", str(p), ".", r, a, ".", "PASS", ".", "GT"] + g) for p, r, a, g in recs]
+
+
+def _head(ns):
+    return [HEAD[0], HEAD[1] + "".join("\tS%d" % i for i in range(ns))]
+
+
+def sized_texts(rng):
+    """(name, vcf, fasta): text lengths n with n mod 16 in {0, 1, 15} and n mod 1024 in {0, 1, 1023}, with and without the
+    final newline (a comment line of adjustable length in front, as vcf_cases.text_length_files does it)"""
+    ref = "".join(rng.choice("ACGT") for _ in range(3000))
+    fasta = _fasta(ref, 60)
+    body = _body(rng, ref, 40, 3)
+    out = []
+    for target in (1023, 1024, 1025, 2047, 2048, 2049, 3071, 3072, 3073, 1455, 1456, 1457, 2655, 2656, 2657):
+        for nl in ("\n", ""):
+            head = _head(3)
+            k = len(body)
+            while True:
+                stem = "\n".join([head[0], "##pad=", head[1]] + body[:k]) + nl
+                if len(stem) <= target:
+                    break
+                k -= 1
+            vcf = ("\n".join([head[0], "##pad=" + "x" * (target - len(stem)), head[1]] + body[:k]) + nl).encode()
+            assert len(vcf) == target and k >= 3
+            out.append(("sized/%d/%s" % (target, "nl" if nl else "open"), vcf, fasta))
+    assert {len(v) % 16 for _, v, _ in out} == {0, 1, 15} and {len(v) % 1024 for _, v, _ in out} >= {0, 1, 1023}
+    return out
+
+
+def open_ended_texts(rng):
+    """(name, vcf, fasta): the last line has no newline and ends in a tab, in a ',' inside ALT, in '<', or in ':' inside a
+    genotype; the text ends at every offset inside a 16-byte chunk"""
+    ref = "".join(rng.choice("ACGT") for _ in range(1500))
+    fasta = _fasta(ref, 60)
+    body = _body(rng, ref, 12, 2, top=1400)
+    b = ref[1449]
+    lasts = {"tab": "chr1\t1450\t.\t%s\tG\t.\tPASS\t.\tGT\t0|1\t" % b, "comma": "chr1\t1450\t.\t%s\tGA," % b,
+             "lt": "chr1\t1450\t.\t%s\t<" % b, "colon": "chr1\t1450\t.\t%s\tGT\t.\tPASS\t.\tGT\t0|1\t1|0:" % b}
+    out = []
+    for what, last in lasts.items():
+        for pad in range(16):
+            head = _head(2)
+            vcf = "\n".join([head[0], "##pad=" + "x" * pad, head[1]] + body + [last]).encode()
+            out.append(("open/%s/%d" % (what, pad), vcf, fasta))
+        assert {len(v) % 16 for n, v, _ in out if n.startswith("open/" + what)} == set(range(16))
+    return out
+
+
+SAMPLES = (0, 1, 2, 63, 64, 65, 129)
+WIDTHS = (1, 7, 60, 255, 256, 257)
+FEATURES = ("last_base", "ref_past_end", "pos_beyond", "allele_above", "fewer_columns", "one_group", "empty_alts")
+
+
+def random_family(rng, ns, lw, ending, shuffle, features):
+    """One plain VCF with pairwise distinct positions and its FASTA.  ending: "nl" / "open" / "crlf" (the FASTA's);
+    features: which of FEATURES to build in; returns (vcf, fasta, the features the file really shows) - genotype features
+    need sample columns."""
+    shown = set()
+    L = rng.randint(300, 1200)
+    ref = "".join(rng.choice("ACGT") for _ in range(L))
+    fasta = _fasta(ref, lw, *{"nl": ("\n", "\n"), "open": ("", "\n"), "crlf": ("\r\n", "\r\n")}[ending])
+    n = rng.randint(6, 24)
+    recs = vc.random_records(rng, ref[:L - 40], n, ns)
+    recs = [list(r) for r in recs]
+    if "one_group" in features:                              # the first record's REF covers all the others
+        recs[0][1] = ref[recs[0][0] - 1:L - 30]
+        shown.add("one_group")
+    if "empty_alts" in features:
+        for r in rng.sample(recs, 3):
+            r[2] = rng.choice(["A,,C", ",", "C,", ",G", "A,,", ",,"])
+        shown.add("empty_alts")
+    if "allele_above" in features and ns:
+        for r in rng.sample(recs, 3):
+            r[3][rng.randrange(ns)] = "%d|%d" % (r[2].count(",") + 2, rng.randint(0, 9))
+        shown.add("allele_above")
+    if "fewer_columns" in features and ns >= 2:
+        for r in recs[1:]:
+            if rng.random() < 0.5:
+                r[3] = r[3][:rng.randint(1, ns - 1)]
+                shown.add("fewer_columns")
+    gt = lambda: ["|".join(str(rng.randint(0, 1)) for _ in range(2)) for _ in range(ns)]
+    if "last_base" in features:
+        recs.append([L, ref[L - 1], "G" if ref[L - 1] != "G" else "T", gt()])
+        shown.add("last_base")
+    if "ref_past_end" in features:
+        recs.append([L - 3, ref[L - 4:] + "ACGTAC", "A", gt()])
+        shown.add("ref_past_end")
+    if "pos_beyond" in features:
+        recs.append([L + rng.randint(1, 500), "A", "C", gt()])
+        recs.append([L + 1000, "ACG", "<DEL>,T", gt()])
+        shown.add("pos_beyond")
+    body = ["\t".join(["chr1", str(p), ".", r, a, ".", "PASS", ".", "GT"][:9 if ns else 8] + g) for p, r, a, g in recs]
+    if shuffle:
+        rng.shuffle(body)
+    vcf = ("\n".join(_head(ns) + body) + rng.choice(["\n", ""])).encode()
+    assert distinct_positions(vcf)
+    return vcf, fasta, shown
+
+
+def random_families(seed=4242):
+    """(name, vcf, fasta): every sample count x line width x FASTA ending, sorted and shuffled, every feature in turn; the
+    name lists the features the file really shows"""
+    rng = random.Random(seed)
+    out, k = [], 0
+    for ns in SAMPLES:
+        for lw in WIDTHS:
+            for ending in ("nl", "open", "crlf"):
+                for shuffle in (False, True):
+                    feats = {FEATURES[k % len(FEATURES)], FEATURES[(k // len(FEATURES) + 3) % len(FEATURES)]}
+                    vcf, fasta, shown = random_family(rng, ns, lw, ending, shuffle, feats)
+                    out.append(("random/s%d/w%d/%s/%s/%s" % (ns, lw, ending, "shuffled" if shuffle else "sorted", "+".join(sorted(shown))),
+                                vcf, fasta))
+                    k += 1
+    return out
+
+
+def cpos_windows(rng):
+    """(mode, name, fasta, up0, up1): up0 at every residue mod 256 and up1 - up0 at every residue mod 8, windows ending at
+    the end of the file and one byte before it; the whole file with and without its final newline and with CRLF"""
+    ref = "".join(rng.choice("ACGT") for _ in range(800))
+    fasta = _fasta(ref, 60)
+    seq_start, n = fasta.index(b"\n") + 1, len(fasta)
+    out = []
+    for a in range(256):
+        up0 = seq_start + a
+        for k in range(8):
+            length = 248 + (3 * a % 41) // 8 * 8 + k
+            out.append((CPOS_WINDOW, "cpos/%d/+%d" % (up0, length), fasta, up0, up0 + length))
+        out.append((CPOS_WINDOW, "cpos/%d/end" % up0, fasta, up0, n))
+        out.append((CPOS_WINDOW, "cpos/%d/end-1" % up0, fasta, up0, n - 1))
+    assert {(c[3] % 256, (c[4] - c[3]) % 8) for c in out} >= {(a, k) for a in range(256) for k in range(8)}
+    for lw in WIDTHS:
+        for ending in ("nl", "open", "crlf"):
+            f = _fasta(ref, lw, *{"nl": ("\n", "\n"), "open": ("", "\n"), "crlf": ("\r\n", "\r\n")}[ending])
+            out.append((CPOS_FILE, "cposfile/w%d/%s" % (lw, ending), f, 0, len(f)))
+    return out
+
+
+def call_on_record():
+    """the input of tests/test_vcf_shard_gpu.py::test_larger_sharded_equals_unpartitioned: seed 11, 10 Mb reference, 10^5
+    records, 8 samples"""
+    rng = random.Random(11)
+    L, n = 10_000_000, 100_000
+    ref = "".join(rng.choices("ACGT", k=L))
+    recs = vc.random_records(rng, ref, n, 8)
+    return vc.records_vcf(ref, recs, 8)
