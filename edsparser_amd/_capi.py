@@ -279,12 +279,29 @@ def load_library():
     lib.edsx_eds_msa.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                  ctypes.c_void_p, ctypes.c_size_t, P(ctypes.c_char_p), ctypes.c_char_p, ctypes.c_uint64,
                                  ctypes.c_int, ctypes.c_uint64, P(_Buf), ctypes.c_void_p, P(AlignInfo)]
+    V = ctypes.c_void_p
+    lib.edsx_paths_lift_sites.argtypes = [V, ctypes.c_size_t, V, V, V, V]
+    lib.edsx_paths_lift_place.argtypes = [V, ctypes.c_size_t, V, V, V, V, V, V]
+    lib.edsx_paths_lift.argtypes = [V, ctypes.c_size_t, V, V, V, V, V, V]
+    lib.edsx_eds_lift.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, V, V, V, V, V, V]
     _LIB = lib
     return lib
 
 
 # edsx_locate_hit as a numpy structured dtype
 LOCATE_HIT = [("common_pos", "<u8"), ("symbol", "<u8"), ("string", "<u8"), ("offset", "<u8")]
+# edsx_lift_site likewise, and the statuses of a lift
+LIFT_SITE = [("symbol", "<u8"), ("string", "<u8"), ("offset", "<u8"), ("column", "<u8"), ("common_pos", "<u8")]
+LIFT_SAME, LIFT_ALIGNED, LIFT_GAP, LIFT_MISSING, LIFT_RANGE = 0, 1, 2, 3, 4
+
+
+def _u64s(*cols):
+    """Contiguous uint64 arrays of one length."""
+    import numpy as np
+    out = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in cols]
+    if any(len(c) != len(out[0]) for c in out):
+        raise ValueError("the query columns differ in length")
+    return out
 
 
 def _take(lib, b):
@@ -648,6 +665,19 @@ class Context(_Handle):
                                            int(max_bytes), ctypes.byref(f), miss.ctypes.data, ctypes.byref(info)))
         return self._take(f), miss[:n_out], _fields(info)
 
+    # ---- coordinate lift (edsparser-lift)
+    def eds_lift(self, eds, seds, src, pos, dst, with_sites=False):
+        """One-shot edsx_eds_lift: PathSession.lift on a session opened and closed for this call."""
+        import numpy as np
+        eds = bytes(eds)
+        src, pos, dst = _u64s(src, pos, dst)
+        n = len(src)
+        out, st = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        sites = np.zeros(n, dtype=LIFT_SITE) if with_sites else None
+        self._check(self._lib.edsx_eds_lift(self._h, eds, len(eds), *_opt(seds), n, src.ctypes.data, pos.ctypes.data, dst.ctypes.data,
+                                            out.ctypes.data, st.ctypes.data, sites.ctypes.data if with_sites else None))
+        return (out, st, sites) if with_sites else (out, st)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -891,7 +921,7 @@ class PathSession(_Handle):
 
     @property
     def timing(self):
-        """Of the last lengths / spell / gfa_walks / align: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
+        """Of the last lengths / spell / gfa_walks / align / lift*: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
         t = PathsTiming()
         self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
         return _fields(t, _raw)
@@ -959,6 +989,42 @@ class PathSession(_Handle):
             self._lib.edsx_buf_free(ctypes.byref(f))
             return out, miss[:n_out]
         return self._ctx._take(f), miss[:n_out]
+
+    def lift_sites(self, paths, pos):
+        """(sites, status): where character pos[q] of path paths[q] lies in the EDS (LIFT_SITE: symbol, string = index within
+        the symbol, offset, alignment column, common_pos or 2**64-1), status 0, or LIFT_RANGE with every field 2**64-1 when
+        the path has no such character (edsx_paths_lift_sites).  Any order, duplicates allowed."""
+        import numpy as np
+        paths, pos = _u64s(paths, pos)
+        n = len(paths)
+        sites, st = np.zeros(n, dtype=LIFT_SITE), np.zeros(n, dtype=np.uint8)
+        self._ctx._check(self._lib.edsx_paths_lift_sites(self._h, n, paths.ctypes.data, pos.ctypes.data, sites.ctypes.data, st.ctypes.data))
+        return sites, st
+
+    def lift_place(self, symbol, string, offset, dst):
+        """(pos, status): where character `offset` of string `string` of symbol `symbol` lies on path dst[q] - LIFT_SAME: the
+        very character; LIFT_ALIGNED: another in the same alignment column; LIFT_GAP: the next character to the right;
+        LIFT_MISSING: the path has no string there; LIFT_RANGE (pos 2**64-1): no such character (edsx_paths_lift_place).
+        Takes the symbol / string / offset columns of an eds_locate hit array as they are."""
+        import numpy as np
+        symbol, string, offset, dst = _u64s(symbol, string, offset, dst)
+        n = len(dst)
+        out, st = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        self._ctx._check(self._lib.edsx_paths_lift_place(self._h, n, symbol.ctypes.data, string.ctypes.data, offset.ctypes.data,
+                                                         dst.ctypes.data, out.ctypes.data, st.ctypes.data))
+        return out, st
+
+    def lift(self, src, pos, dst, with_sites=False):
+        """(dst_pos, status[, sites]): the place on path dst[q] of character pos[q] of path src[q]; the sites stay on the
+        device in between (edsx_paths_lift)."""
+        import numpy as np
+        src, pos, dst = _u64s(src, pos, dst)
+        n = len(src)
+        out, st = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        sites = np.zeros(n, dtype=LIFT_SITE) if with_sites else None
+        self._ctx._check(self._lib.edsx_paths_lift(self._h, n, src.ctypes.data, pos.ctypes.data, dst.ctypes.data, out.ctypes.data,
+                                                   st.ctypes.data, sites.ctypes.data if with_sites else None))
+        return (out, st, sites) if with_sites else (out, st)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

@@ -1087,6 +1087,53 @@ int edsx_eds_msa(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8
     });
 }
 
+// ---- edsparser-lift (path_device.hip, lift_core.hpp)
+static_assert(sizeof(LiftSite) == sizeof(edsx_lift_site) && offsetof(LiftSite, common_pos) == offsetof(edsx_lift_site, common_pos),
+              "edsx_lift_site is LiftSite");
+
+int edsx_paths_lift_sites(edsx_paths_session* s, size_t n, const uint64_t* path, const uint64_t* pos, edsx_lift_site* site,
+                          uint8_t* status)
+{
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (n && (!path || !pos || !site || !status)) throw ParamError("null argument");
+        s->p.lift(n, reinterpret_cast<const u64*>(path), reinterpret_cast<const u64*>(pos), nullptr, nullptr,
+                  reinterpret_cast<LiftSite*>(site), nullptr, status, nullptr);
+    });
+}
+
+int edsx_paths_lift_place(edsx_paths_session* s, size_t n, const uint64_t* symbol, const uint64_t* string, const uint64_t* offset,
+                          const uint64_t* dst_path, uint64_t* dst_pos, uint8_t* status)
+{
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (n && (!symbol || !string || !offset || !dst_path || !dst_pos || !status)) throw ParamError("null argument");
+        const LiftColumns sites{reinterpret_cast<const u64*>(symbol), reinterpret_cast<const u64*>(string), reinterpret_cast<const u64*>(offset)};
+        s->p.lift(n, nullptr, nullptr, &sites, reinterpret_cast<const u64*>(dst_path), nullptr, reinterpret_cast<u64*>(dst_pos),
+                  status, nullptr);
+    });
+}
+
+int edsx_paths_lift(edsx_paths_session* s, size_t n, const uint64_t* src_path, const uint64_t* src_pos, const uint64_t* dst_path,
+                    uint64_t* dst_pos, uint8_t* status, edsx_lift_site* site)
+{
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (n && (!src_path || !src_pos || !dst_path || !dst_pos || !status)) throw ParamError("null argument");
+        s->p.lift(n, reinterpret_cast<const u64*>(src_path), reinterpret_cast<const u64*>(src_pos), nullptr,
+                  reinterpret_cast<const u64*>(dst_path), reinterpret_cast<LiftSite*>(site), reinterpret_cast<u64*>(dst_pos), status, nullptr);
+    });
+}
+
+int edsx_eds_lift(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, size_t n,
+                  const uint64_t* src_path, const uint64_t* src_pos, const uint64_t* dst_path, uint64_t* dst_pos, uint8_t* status,
+                  edsx_lift_site* site)
+{
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_lift(s, n, src_path, src_pos, dst_path, dst_pos, status, site); });
+}
+
 // ---- eds2vcf (vcf_export_device.hip)
 int edsx_eds_vcf(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                  const edsx_vcf_export_opts* opts, edsx_buf* vcf, edsx_buf* ref_fasta, edsx_vcf_export_info* info)

@@ -4,6 +4,7 @@
 
 #include "eds_device.hpp"
 #include "gfa_device.hpp"
+#include "lift_core.hpp"
 
 #include <vector>
 
@@ -14,8 +15,9 @@ struct PathInfo {
     bool tokenised_on_device = false;
 };
 
-// of the last lengths() / spell() / walks() / align(): device events around the kernels, a host clock around the downloads
-// (walks: scan_ms holds both scans of a batch, copy_ms is k_path_walk; align: copy_ms is k_path_align)
+// of the last lengths() / spell() / walks() / align() / lift(): device events around the kernels, a host clock around the downloads
+// (walks: scan_ms holds both scans of a batch, copy_ms is k_path_walk; align: copy_ms is k_path_align; lift: copy_ms is
+// k_lift_find + k_lift_place, bytes_written the result bytes)
 struct PathTiming {
     double tokenise_ms = 0, choose_ms = 0, scan_ms = 0, copy_ms = 0, download_ms = 0;
     u64 bytes_written = 0;
@@ -28,6 +30,10 @@ struct PathRec { u64 rec_off, body_off, hdr_src, L, lw, body, row; };
 
 // the column layout of the session's alignment view (align): W = n_columns
 struct AlignInfo { u64 n_symbols = 0, n_columns = 0, n_zero_width_symbols = 0, widest_symbol = 0, num_paths = 0; };
+
+typedef lift::Site LiftSite;
+// sites given by the host as three columns of n entries each (the columns of a locate hit)
+struct LiftColumns { const u64* symbol; const u64* string; const u64* offset; };
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -58,6 +64,14 @@ public:
     void align(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, uint8_t gap, u64 max_bytes,
                HostBytes& out, u64* missing, hipStream_t st);
 
+    // Positions between the paths of the EDS (lift_core.hpp), n queries, duplicates allowed, any order.
+    //   src_path + src_pos: the site of character src_pos[q] of path src_path[q] (status 0, or RANGE with every field ~0)
+    //   site_in instead:    given sites, as three columns that are uploaded as they are
+    //   dst_path:           the place of each site on path dst_path[q]: dst_pos and SAME / ALIGNED / GAP / MISSING / RANGE
+    // With src and dst the sites stay on the device in between.  site_out / dst_pos may be null; status has n bytes.
+    void lift(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path, LiftSite* site_out,
+              u64* dst_pos, uint8_t* status, hipStream_t st);
+
 private:
     void check_ids(const u64* ids, size_t n) const;
     u64 table_batch(size_t n, u64 cell_bytes = 16) const;
@@ -83,6 +97,11 @@ private:
     bool align_ready_ = false;
     AlignInfo ainfo_;
     DevBuf col_;
+    // cum_common (n + 1 entries) next to col: made by the first lift() of a session, kept until it closes
+    void lift_open(hipStream_t st);
+    void lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t st);
+    bool lift_ready_ = false;
+    DevBuf cum_common_, lmap_, lcnt_, lcur_, lq_path_, lq_pos_, lq_aux_, lperm_, lsite_, lst_, lst2_, litems_;
 };
 
 } // namespace edsx

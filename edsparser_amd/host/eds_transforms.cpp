@@ -94,6 +94,28 @@ void eds_to_msa(std::istream& eds_in, std::istream& seds_in, std::ostream& out, 
     }
 }
 
+std::vector<LiftResult> lift_positions(std::istream& eds_in, std::istream& seds_in, const std::vector<LiftQuery>& queries)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    const size_t n = queries.size();
+    std::vector<uint64_t> src(n), pos(n), dst(n), out(n);
+    for (size_t q = 0; q < n; q++) { src[q] = queries[q].src_path; pos[q] = queries[q].src_pos; dst[q] = queries[q].dst_path; }
+    std::vector<uint8_t> status(n);
+    std::vector<edsx_lift_site> site(n);
+    edsx_ctx* ctx = detail::context();
+    const int rc = edsx_eds_lift(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                                 reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), n, src.data(), pos.data(), dst.data(),
+                                 out.data(), status.data(), site.data());
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    std::vector<LiftResult> res(n);
+    for (size_t q = 0; q < n; q++) {
+        res[q].dst_pos = out[q]; res[q].symbol = site[q].symbol; res[q].string = site[q].string; res[q].offset = site[q].offset;
+        res[q].column = site[q].column; res[q].common_pos = site[q].common_pos;
+        res[q].status = static_cast<LiftStatus>(status[q]);
+    }
+    return res;
+}
+
 void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
 {

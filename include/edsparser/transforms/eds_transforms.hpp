@@ -48,6 +48,21 @@ void eds_to_msa(std::istream& eds, std::istream& seds, std::ostream& out, const 
                 size_t line_width = 0, const std::vector<std::string>* names = nullptr, const std::string& prefix = "path",
                 char gap = '-', size_t max_bytes = 0, AlignInfo* info = nullptr);
 
+// edsparser-lift: positions between the paths of an EDS with sources.  Query q asks where character src_pos of path
+// src_path lies on path dst_path: its site in the EDS (symbol, string = index within the symbol, offset; the alignment
+// column of eds_to_msa; common_pos, the pattern search's coordinate, or ~0 inside a degenerate symbol) and dst_pos with
+// the status SAME (the very character), ALIGNED (another one in the same column), GAP (dst_pos is the next character to
+// the right, possibly the length of the path) or MISSING (the path has no string in the symbol).  A src_pos at or above
+// the length of the path gives RANGE and ~0 in every field; it does not fail the call (edsx_paths_lift states the rules
+// in full).  Any order, duplicates allowed.  std::invalid_argument for a path outside 1..P.
+enum class LiftStatus : unsigned char { SAME = 0, ALIGNED = 1, GAP = 2, MISSING = 3, RANGE = 4 };
+struct LiftQuery { size_t src_path = 0, src_pos = 0, dst_path = 0; };
+struct LiftResult {
+    size_t dst_pos = 0, symbol = 0, string = 0, offset = 0, column = 0, common_pos = 0;
+    LiftStatus status = LiftStatus::RANGE;
+};
+std::vector<LiftResult> lift_positions(std::istream& eds, std::istream& seds, const std::vector<LiftQuery>& queries);
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

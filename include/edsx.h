@@ -480,15 +480,53 @@ int  edsx_paths_lengths(edsx_paths_session* s, const uint64_t* ids, size_t n, ui
  * missing (may be NULL): one count per record. */
 int  edsx_paths_spell(edsx_paths_session* s, const uint64_t* ids, size_t n, const char* const* names, const char* prefix,
                       uint64_t line_width, edsx_buf* fasta, uint64_t* missing);
-/* of the last edsx_paths_lengths / edsx_paths_spell / edsx_paths_gfa_walks / edsx_paths_align (tokenise_ms: of
+/* of the last edsx_paths_lengths / edsx_paths_spell / edsx_paths_gfa_walks / edsx_paths_align / edsx_paths_lift* (tokenise_ms: of
  * edsx_paths_open; walks: scan_ms holds both scans of a batch, copy_ms the walk kernel, bytes_written the P lines; align:
- * copy_ms the alignment kernel, bytes_written the alignment) */
+ * copy_ms the alignment kernel, bytes_written the alignment; the lift calls: copy_ms the search and place kernels,
+ * bytes_written the result bytes) */
 int  edsx_paths_last_timing(const edsx_paths_session* s, edsx_paths_timing* out);
 void edsx_paths_close(edsx_paths_session* s);
 /* open + spell + close */
 int  edsx_eds_spell_paths(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
                           const uint64_t* ids, size_t n, const char* const* names, const char* prefix, uint64_t line_width,
                           edsx_buf* fasta, uint64_t* missing);
+
+/* ---- edsparser-lift: positions between the paths of an EDS with sources (path_device.hip, lift_core.hpp) ----
+ * chosen(p, i) is the string edsx_paths_spell chooses for path p in symbol i (none: "missing"); sym_pos_p(i) is the
+ * number of characters of p in front of symbol i; col[i] is the first alignment column of symbol i (edsx_paths_align).
+ *   Site of (p, x), 0 <= x < length of p: symbol i is the LARGEST with sym_pos_p(i) <= x (runs of symbols that add nothing
+ *      to p share one offset), string j = the index of chosen(p, i) within the symbol, offset o = x - sym_pos_p(i), so
+ *      that character x of p is character o of that string; column = col[i] + o; common_pos = edsx_eds_locate's
+ *      coordinate when symbol i has one string, else UINT64_MAX.
+ *   Place of (i, j, o) on path t, with start = sym_pos_t(i) and c = chosen(t, i):
+ *      MISSING  c is none                  pos = start
+ *      GAP      o >= length of c           pos = start + length of c: the next character to the right, or the length of t
+ *      SAME     c is string j              pos = start + o, the very same character
+ *      ALIGNED  otherwise                  pos = start + o, a character in the same alignment column
+ *   Lift of (a, x) to b: the place of the site of (a, x) on b; the sites stay on the device in between.
+ * Per-query errors do not fail the call: x at or above the length of the path, i at or above the number of symbols, j at
+ * or above the size of the symbol and o at or above the length of string j give status RANGE and UINT64_MAX in every
+ * output field of the query.  Queries may come in any order and repeat.  Path ids outside 1..P and a missing .seds give
+ * the statuses and texts of edsx_paths_spell.  edsx_paths_last_timing: choose_ms / scan_ms of the tables, copy_ms the
+ * search and place kernels, bytes_written the result bytes. */
+typedef struct { uint64_t symbol, string, offset, column, common_pos; } edsx_lift_site;
+#define EDSX_LIFT_SAME 0
+#define EDSX_LIFT_ALIGNED 1
+#define EDSX_LIFT_GAP 2
+#define EDSX_LIFT_MISSING 3
+#define EDSX_LIFT_RANGE 4
+/* status[q]: 0 or EDSX_LIFT_RANGE */
+int edsx_paths_lift_sites(edsx_paths_session* s, size_t n, const uint64_t* path, const uint64_t* pos, edsx_lift_site* site,
+                          uint8_t* status);
+int edsx_paths_lift_place(edsx_paths_session* s, size_t n, const uint64_t* symbol, const uint64_t* string, const uint64_t* offset,
+                          const uint64_t* dst_path, uint64_t* dst_pos, uint8_t* status);
+/* site (may be NULL): the site of every (src_path, src_pos) */
+int edsx_paths_lift(edsx_paths_session* s, size_t n, const uint64_t* src_path, const uint64_t* src_pos, const uint64_t* dst_path,
+                    uint64_t* dst_pos, uint8_t* status, edsx_lift_site* site);
+/* open + lift + close */
+int edsx_eds_lift(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, size_t n,
+                  const uint64_t* src_path, const uint64_t* src_pos, const uint64_t* dst_path, uint64_t* dst_pos, uint8_t* status,
+                  edsx_lift_site* site);
 
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
