@@ -284,6 +284,9 @@ def load_library():
     lib.edsx_paths_lift_place.argtypes = [V, ctypes.c_size_t, V, V, V, V, V, V]
     lib.edsx_paths_lift.argtypes = [V, ctypes.c_size_t, V, V, V, V, V, V]
     lib.edsx_eds_lift.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, V, V, V, V, V, V]
+    lib.edsx_paths_slice.argtypes = [V, ctypes.c_size_t, V, V, V, ctypes.c_uint64, P(_Buf), P(_Buf), V, V]
+    lib.edsx_eds_slice.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, V, V, V,
+                                   ctypes.c_uint64, P(_Buf), P(_Buf), V, V]
     _LIB = lib
     return lib
 
@@ -293,6 +296,18 @@ LOCATE_HIT = [("common_pos", "<u8"), ("symbol", "<u8"), ("string", "<u8"), ("off
 # edsx_lift_site likewise, and the statuses of a lift
 LIFT_SITE = [("symbol", "<u8"), ("string", "<u8"), ("offset", "<u8"), ("column", "<u8"), ("common_pos", "<u8")]
 LIFT_SAME, LIFT_ALIGNED, LIFT_GAP, LIFT_MISSING, LIFT_RANGE = 0, 1, 2, 3, 4
+# edsx_slice_region likewise, and the status of a region that is empty or leaves its path
+SLICE_REGION = [(f, "<u8") for f in ("symbol_first", "symbol_last", "cut_first", "cut_end", "column_first", "column_end", "strings",
+                                     "chars", "eds_off", "eds_len", "seds_off", "seds_len")]
+SLICE_RANGE = 4
+
+
+def _slice_regions(reg, st):
+    """The edsx_slice_region array as a dict of uint64 columns, plus `status`."""
+    import numpy as np
+    out = {f: np.ascontiguousarray(reg[f]) for f, _ in SLICE_REGION}
+    out["status"] = st
+    return out
 
 
 def _u64s(*cols):
@@ -678,6 +693,19 @@ class Context(_Handle):
                                             out.ctypes.data, st.ctypes.data, sites.ctypes.data if with_sites else None))
         return (out, st, sites) if with_sites else (out, st)
 
+    # ---- region slices (edsparser-slice)
+    def eds_slice(self, eds, seds, path, start, end, max_bytes=0):
+        """One-shot edsx_eds_slice: PathSession.slice on a session opened and closed for this call."""
+        import numpy as np
+        eds = bytes(eds)
+        path, start, end = _u64s(path, start, end)
+        n = len(path)
+        reg, st = np.zeros(n, dtype=SLICE_REGION), np.zeros(n, dtype=np.uint8)
+        e, q = _Buf(), _Buf()
+        self._check(self._lib.edsx_eds_slice(self._h, eds, len(eds), *_opt(seds), n, path.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                             int(max_bytes), ctypes.byref(e), ctypes.byref(q), reg.ctypes.data, st.ctypes.data))
+        return self._take(e), self._take(q), _slice_regions(reg, st)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -921,7 +949,7 @@ class PathSession(_Handle):
 
     @property
     def timing(self):
-        """Of the last lengths / spell / gfa_walks / align / lift*: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
+        """Of the last lengths / spell / gfa_walks / align / lift* / slice: tokenise_ms (of the open), choose_ms, scan_ms, copy_ms, download_ms, bytes_written."""
         t = PathsTiming()
         self._ctx._check(self._lib.edsx_paths_last_timing(self._h, ctypes.byref(t)))
         return _fields(t, _raw)
@@ -1025,6 +1053,20 @@ class PathSession(_Handle):
         self._ctx._check(self._lib.edsx_paths_lift(self._h, n, src.ctypes.data, pos.ctypes.data, dst.ctypes.data, out.ctypes.data,
                                                    st.ctypes.data, sites.ctypes.data if with_sites else None))
         return (out, st, sites) if with_sites else (out, st)
+
+    def slice(self, path, start, end, max_bytes=0):
+        """(eds bytes, seds bytes, regions): the regions [start[r], end[r]) of path path[r] - path 0: of the columns of
+        align() - as FULL-form .eds + .seds texts laid end to end (edsx_paths_slice).  regions: a dict of uint64 arrays
+        named as the fields of edsx_slice_region, plus `status` (0, or SLICE_RANGE with no bytes for a region that is empty
+        or leaves its path).  max_bytes (0: none): EdsxError when both buffers together are larger."""
+        import numpy as np
+        path, start, end = _u64s(path, start, end)
+        n = len(path)
+        reg, st = np.zeros(n, dtype=SLICE_REGION), np.zeros(n, dtype=np.uint8)
+        e, q = _Buf(), _Buf()
+        self._ctx._check(self._lib.edsx_paths_slice(self._h, n, path.ctypes.data, start.ctypes.data, end.ctypes.data, int(max_bytes),
+                                                    ctypes.byref(e), ctypes.byref(q), reg.ctypes.data, st.ctypes.data))
+        return self._ctx._take(e), self._ctx._take(q), _slice_regions(reg, st)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

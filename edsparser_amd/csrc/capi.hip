@@ -51,6 +51,7 @@ struct edsx_ctx {
     SubsetPipeline subset;                   // edsx_eds_subset
     GfaPipeline gfa;                         // edsx_eds_gfa_graph
     VcfExportPipeline vcf_export;            // edsx_eds_vcf
+    KernelTimes slice_times;                 // edsx_paths_slice, of every session of this context
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -417,6 +418,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->subset.set_timing(enabled != 0);
     ctx->gfa.set_timing(enabled != 0);
     ctx->vcf_export.set_timing(enabled != 0);
+    ctx->slice_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -424,7 +426,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     int n = ctx->msa.get_timing(names, total_ms, launches, cap);
     n += ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1132,6 +1135,36 @@ int edsx_eds_lift(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_lift(s, n, src_path, src_pos, dst_path, dst_pos, status, site); });
+}
+
+// ---- edsparser-slice (slice_device.hip, slice_core.hpp)
+static_assert(sizeof(SliceRegion) == sizeof(edsx_slice_region) && offsetof(SliceRegion, seds_len) == offsetof(edsx_slice_region, seds_len),
+              "edsx_slice_region is SliceRegion");
+static_assert(EDSX_SLICE_RANGE == slice::RANGE, "EDSX_SLICE_RANGE");
+
+int edsx_paths_slice(edsx_paths_session* s, size_t n, const uint64_t* path, const uint64_t* start, const uint64_t* end,
+                     uint64_t max_bytes, edsx_buf* eds_out, edsx_buf* seds_out, edsx_slice_region* region, uint8_t* status)
+{
+    clear(eds_out, seds_out);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!eds_out || !seds_out || (n && (!path || !start || !end || !status))) throw ParamError("null argument");
+        HostBytes e, q;
+        s->p.slice(n, reinterpret_cast<const u64*>(path), reinterpret_cast<const u64*>(start), reinterpret_cast<const u64*>(end), max_bytes,
+                   e, q, reinterpret_cast<SliceRegion*>(region), status, &s->ctx->slice_times, nullptr);
+        give(eds_out, e);
+        give(seds_out, q);
+    });
+}
+
+int edsx_eds_slice(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, size_t n,
+                   const uint64_t* path, const uint64_t* start, const uint64_t* end, uint64_t max_bytes, edsx_buf* eds_out,
+                   edsx_buf* seds_out, edsx_slice_region* region, uint8_t* status)
+{
+    clear(eds_out, seds_out);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_slice(s, n, path, start, end, max_bytes, eds_out, seds_out, region, status); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

@@ -690,6 +690,7 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     walk_ready_ = false;
     align_ready_ = false;
     lift_ready_ = false;
+    slice_ready_ = false;
     const auto t0 = std::chrono::steady_clock::now();
     eds_.load(eds, eds_n, seds, seds_n, true, st);
     eds_.drop_scratch();                                                      // the session may live long
@@ -1021,6 +1022,14 @@ void PathPipeline::lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t
 void PathPipeline::lift(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path,
                         LiftSite* site_out, u64* dst_pos, uint8_t* status, hipStream_t st)
 {
+    lift_run(n, src_path, src_pos, site_in, dst_path, site_out, dst_pos, status, nullptr, nullptr, st);
+}
+
+// dev_site / dev_status (device memory, n entries each; only with src_path and without dst_path): the sites and their
+// statuses stay on the device for the caller's kernels, and nothing is downloaded
+void PathPipeline::lift_run(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path,
+                            LiftSite* site_out, u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st)
+{
     const bool find = src_path != nullptr, put = dst_path != nullptr;
     if (find) check_ids(src_path, n);
     if (put) check_ids(dst_path, n);
@@ -1111,6 +1120,12 @@ void PathPipeline::lift(size_t n, const u64* src_path, const u64* src_pos, const
                 EDSX_HIP(hipGetLastError());
                 timing_.copy_ms += ev.ms();
             }
+        }
+        if (dev_site) {
+            EDSX_HIP(hipMemcpyAsync(dev_site + c0, lsite_.ptr, sizeof(LiftSite) * m, hipMemcpyDeviceToDevice, st));
+            EDSX_HIP(hipMemcpyAsync(dev_status + c0, lst_.ptr, m, hipMemcpyDeviceToDevice, st));
+            EDSX_HIP(hipStreamSynchronize(st));
+            continue;
         }
         const auto t0 = std::chrono::steady_clock::now();
         if (site_out) EDSX_HIP(hipMemcpyAsync(site_out + c0, lsite_.ptr, sizeof(LiftSite) * m, hipMemcpyDeviceToHost, st));

@@ -5,6 +5,7 @@
 #include "eds_device.hpp"
 #include "gfa_device.hpp"
 #include "lift_core.hpp"
+#include "slice_core.hpp"
 
 #include <vector>
 
@@ -17,7 +18,8 @@ struct PathInfo {
 
 // of the last lengths() / spell() / walks() / align() / lift(): device events around the kernels, a host clock around the downloads
 // (walks: scan_ms holds both scans of a batch, copy_ms is k_path_walk; align: copy_ms is k_path_align; lift: copy_ms is
-// k_lift_find + k_lift_place, bytes_written the result bytes)
+// k_lift_find + k_lift_place, bytes_written the result bytes; slice: scan_ms is resolve + count + scan, copy_ms the fill
+// kernels, bytes_written both texts)
 struct PathTiming {
     double tokenise_ms = 0, choose_ms = 0, scan_ms = 0, copy_ms = 0, download_ms = 0;
     u64 bytes_written = 0;
@@ -34,6 +36,22 @@ struct AlignInfo { u64 n_symbols = 0, n_columns = 0, n_zero_width_symbols = 0, w
 typedef lift::Site LiftSite;
 // sites given by the host as three columns of n entries each (the columns of a locate hit)
 struct LiftColumns { const u64* symbol; const u64* string; const u64* offset; };
+
+// edsx_slice_region (include/edsx.h)
+struct SliceRegion { u64 symbol_first, symbol_last, cut_first, cut_end, column_first, column_end, strings, chars, eds_off, eds_len, seds_off, seds_len; };
+
+// device time per kernel, accumulated while on (edsx_set_timing / edsx_get_timing), as SubsetPipeline keeps it
+class KernelTimes {
+public:
+    void set(bool on) { on_ = on; acc_.clear(); }
+    bool on() const { return on_; }
+    void add(const char* name, float ms);
+    int get(const char** names, float* ms, int* counts, int cap) const;
+private:
+    struct Acc { const char* name; float total_ms; int count; };
+    bool on_ = false;
+    std::vector<Acc> acc_;
+};
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -72,6 +90,13 @@ public:
     void lift(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path, LiftSite* site_out,
               u64* dst_pos, uint8_t* status, hipStream_t st);
 
+    // Regions of the EDS as FULL-form .eds + .seds texts laid end to end (slice_core.hpp, slice_device.hip), n
+    // regions (path, start, end), half open; path 0: columns of the alignment view.  A region that is empty or leaves its
+    // path gets status RANGE and no bytes; a path id above P is a ParamError, and so is a summed size above max_bytes (0:
+    // none), found before the texts are allocated.  region (nullable) has n entries, status n bytes.
+    void slice(size_t n, const u64* path, const u64* start, const u64* end, u64 max_bytes, HostBytes& eds_out, HostBytes& seds_out,
+               SliceRegion* region, uint8_t* status, KernelTimes* times, hipStream_t st);
+
 private:
     void check_ids(const u64* ids, size_t n) const;
     u64 table_batch(size_t n, u64 cell_bytes = 16) const;
@@ -100,8 +125,15 @@ private:
     // cum_common (n + 1 entries) next to col: made by the first lift() of a session, kept until it closes
     void lift_open(hipStream_t st);
     void lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t st);
+    void lift_run(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path, LiftSite* site_out,
+                  u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st);
     bool lift_ready_ = false;
     DevBuf cum_common_, lmap_, lcnt_, lcur_, lq_path_, lq_pos_, lq_aux_, lperm_, lsite_, lst_, lst2_, litems_;
+    // the scanned .seds bytes per string (m + 1 entries) and the symbol of every string (m): made by the first slice() of a
+    // session, kept until it closes
+    void slice_open(hipStream_t st);
+    bool slice_ready_ = false;
+    DevBuf sb_, symof_, s_in_, s_site_, s_sst_, s_reg_, s_st_, s_sum_, s_scan_, s_edst_, s_eds_, s_seds_;
 };
 
 } // namespace edsx

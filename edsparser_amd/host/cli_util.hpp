@@ -6,6 +6,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace edsparser::cli {
@@ -48,6 +49,7 @@ public:
                     value = argv[++i];
                 }
                 values_[o->long_name] = value;
+                given_.emplace_back(o->long_name, value);
             } else {
                 values_[o->long_name] = "1";
             }
@@ -66,6 +68,8 @@ public:
         auto it = values_.find(name);
         return it == values_.end() ? def : it->second;
     }
+    // every valued option as given, in command-line order (an option may repeat: get() holds its last value)
+    const std::vector<std::pair<std::string, std::string>>& given() const { return given_; }
     unsigned long get_unsigned(const std::string& name, unsigned long def) const
     {
         auto it = values_.find(name);
@@ -107,6 +111,7 @@ private:
     std::string caption_;
     std::vector<Option> opts_;
     std::map<std::string, std::string> values_;
+    std::vector<std::pair<std::string, std::string>> given_;
 };
 
 } // namespace edsparser::cli

@@ -528,6 +528,43 @@ int edsx_eds_lift(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint
                   const uint64_t* src_path, const uint64_t* src_pos, const uint64_t* dst_path, uint64_t* dst_pos, uint8_t* status,
                   edsx_lift_site* site);
 
+/* ---- edsparser-slice: regions of an EDS with sources as EDSs of their own (slice_device.hip, slice_core.hpp) ----
+ * Input: a path session and n regions (path, start, end), 0-based and half open.  path >= 1: characters [start, end) of
+ * that path.  path == 0: columns [start, end) of the alignment of edsx_paths_align, within [0, W).
+ *   Ends.  Path region: (i0, j0, o0, c0) is the site of (path, start) and (i1, j1, o1, c1) the site of (path, end - 1), by
+ *      the rule of the lift above (the LARGEST symbol with sym_pos <= x).  Column region: i0 is the largest symbol with
+ *      col[i0] <= start, o0 = start - col[i0], c0 = start; i1, o1 and c1 likewise from end - 1.  The cut offsets are o0
+ *      and o1e = o1 + 1, the column window is [c0, c1 + 1).
+ *   Symbols.  The slice holds the symbols i0 .. i1 in order, each with all its strings in order, empty ones too.  Every
+ *      symbol strictly between the ends is copied as it is, whether the anchor path adds to it or not.  EVERY string t of
+ *      symbol i0 becomes t[o0:], every string of symbol i1 becomes t[:o1e] (t[o0:o1e] when i0 == i1): the edge symbols
+ *      are cut at the alignment column, in all strings, not only in the anchor's.  A string shorter than the cut becomes
+ *      empty and stays.  Nothing is dropped, merged or reordered.
+ *   Sources.  Every string keeps its source set, one set per string, ids unchanged.
+ *   Texts.  Each region is a FULL-form text: the .eds has braces around every symbol ("{}" is one empty string, "{,}" are
+ *      two) and ends with a line feed; the .seds has one "{ids}" per string, ids ascending, a set that holds 0 written
+ *      "{0}", and ends with a line feed.  The regions lie one behind the other in eds_out and in seds_out, in request order.
+ *   It follows that row p of the alignment of a slice is columns [c0, c1 + 1) of row p of the alignment of the input, for
+ *      every path p, and that the slice spells characters [start, end) of its anchor path.
+ * region (may be NULL), per region: the symbol range (symbol_last inclusive), the cut offsets o0 and o1e, the column
+ * window, the number of strings and characters of the slice, and where its two texts lie (lengths with the line feed).
+ * Per-region errors do not fail the call: start >= end, or end above the length of the path (above W for columns), gives
+ * status EDSX_SLICE_RANGE, eds_len = seds_len = 0 and UINT64_MAX in every other field.  Regions may overlap, repeat and
+ * come in any order.  A path id above P fails with the status and text of edsx_paths_spell.  max_bytes (0: none) is held
+ * against the summed size of both buffers before they are allocated: EDSX_ERR_INVALID_PARAMETER, "Slices have <n> bytes,
+ * above the limit of <max>".  n == 0 gives two empty buffers.  edsx_paths_last_timing: scan_ms the resolve, count and scan
+ * steps (choose_ms the lift's tables), copy_ms the fill kernels, bytes_written both buffers; under edsx_set_timing the
+ * kernels come back by name from edsx_get_timing. */
+typedef struct { uint64_t symbol_first, symbol_last, cut_first, cut_end, column_first, column_end,
+                 strings, chars, eds_off, eds_len, seds_off, seds_len; } edsx_slice_region;
+#define EDSX_SLICE_RANGE 4
+int edsx_paths_slice(edsx_paths_session* s, size_t n, const uint64_t* path, const uint64_t* start, const uint64_t* end,
+                     uint64_t max_bytes, edsx_buf* eds_out, edsx_buf* seds_out, edsx_slice_region* region, uint8_t* status);
+/* open + slice + close */
+int edsx_eds_slice(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, size_t n,
+                   const uint64_t* path, const uint64_t* start, const uint64_t* end, uint64_t max_bytes, edsx_buf* eds_out,
+                   edsx_buf* seds_out, edsx_slice_region* region, uint8_t* status);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
