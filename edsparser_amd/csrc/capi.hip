@@ -22,6 +22,7 @@
 #include "multi_gpu.hpp"
 #include "path_device.hpp"
 #include "query_device.hpp"
+#include "slice_core.hpp"
 #include "subset_device.hpp"
 #include "synth.hpp"
 #include "vcf_contig.hpp"

@@ -137,6 +137,51 @@ __device__ __forceinline__ u32 mbcnt(u64 mask)
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
 }
 __device__ __forceinline__ u64 ballot64(bool p) { return __ballot(p); }
+// the sum of v over the 64 lanes, in every lane
+__device__ __forceinline__ u64 wave_sum(u64 v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the last k in [lo, hi] with a[k] <= x, given a[lo] <= x
+__device__ __forceinline__ u64 last_le(const u64* __restrict__ a, u64 lo, u64 hi, u64 x)
+{
+    while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (a[mid] <= x) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// The ids of one source set as decimal text, "a,b,c}", by the G lanes (a power of two, lane g of them) that share the set:
+// lane g takes the words g, g + G, ... of `row` (!act: no set, but the lane still takes part in the shuffles).  Per round
+// every lane counts the bytes of its word, a shuffle scan inside the group places them behind `cur`, and the lane writes
+// its ids, each followed by a comma or, where the set ends (`end`: one past the closing brace), the brace.  pol:
+//   mask(w)      the bits of word w that count          bytes(w, x)  the text bytes of the ids of x, separators included
+//   id(w, b)     the number written for bit b of word w
+template <class Policy>
+__device__ __forceinline__ void write_set_ids(const Policy& pol, const u64* __restrict__ row, bool act, u32 W, u32 G, u32 g, u64 cur, u64 end,
+                                              uint8_t* __restrict__ sout)
+{
+    for (u32 wb = 0; wb < W; wb += G) {
+        const u32 w = wb + g;
+        u64 x = (act && w < W) ? row[w] & pol.mask(w) : 0;
+        const u64 nb = pol.bytes(w < W ? w : 0, x);
+        u64 incl = nb;
+        for (u32 o = 1; o < G; o <<= 1) { const u64 t = __shfl_up(incl, o, 64); if (g >= o) incl += t; }
+        const u64 total = __shfl(incl, (int)((threadIdx.x & 63u) | (G - 1)), 64);
+        u64 p = cur + incl - nb;
+        while (x) {
+            const u32 b = (u32)__builtin_ctzll(x);
+            x &= x - 1;
+            u32 v = pol.id(w, b);
+            const u32 dg = ndigits(v);
+            for (u32 k = dg; k-- > 0;) { sout[p + k] = (uint8_t)('0' + v % 10u); v /= 10u; }
+            p += dg;
+            sout[p] = p + 1 == end ? '}' : ',';
+            p++;
+        }
+        cur += total;
+    }
+}
 
 // mix64 / hash3 (splitmix64): draw.hpp, shared with the host library
 

@@ -641,11 +641,6 @@ DeviceEds::Pool DeviceEds::consume()
 // acc: [0] degenerate symbols [1] sum(size - 1) over them [2] characters of the non-degenerate symbols [3] their number
 //      [4] min / [5] max of their lengths [6] "not an l-EDS" [7] empty strings [8] all characters [9] sum of the set
 //      sizes [10] largest set; orbits[W]: OR of all path sets
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ void __launch_bounds__(256) k_eds_stats(SymView s, u64 n, const u32* __restrict__ elen, u64 m, const u64* __restrict__ bits,
                                                    u32 W, u64 l, u64* __restrict__ acc, u64* __restrict__ orbits)
 {
@@ -681,8 +676,8 @@ __global__ void __launch_bounds__(256) k_eds_stats(SymView s, u64 n, const u32* 
             if ((threadIdx.x & 63) == 0 && o) atomicOr(&orbits[w], o);
         }
     }
-    ndeg = wave_sum64(ndeg); change = wave_sum64(change); common = wave_sum64(common); nctx = wave_sum64(nctx);
-    empty = wave_sum64(empty); chars = wave_sum64(chars); tot = wave_sum64(tot);
+    ndeg = wave_sum(ndeg); change = wave_sum(change); common = wave_sum(common); nctx = wave_sum(nctx);
+    empty = wave_sum(empty); chars = wave_sum(chars); tot = wave_sum(tot);
     for (int sh = 32; sh > 0; sh >>= 1) {
         const u64 a = __shfl_xor(mn, sh, 64), b = __shfl_xor(mx, sh, 64), c = __shfl_xor(big, sh, 64), d = __shfl_xor(bad, sh, 64);
         mn = a < mn ? a : mn; mx = b > mx ? b : mx; big = c > big ? c : big; bad |= d;

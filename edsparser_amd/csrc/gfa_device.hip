@@ -22,7 +22,6 @@
 //   k_gfa_links     at most two lines per chunk (a line has 15 bytes or more)
 #include "gfa_device.hpp"
 
-#include <deque>
 #include <string>
 
 namespace edsx {
@@ -118,9 +117,7 @@ __global__ void __launch_bounds__(GT) k_gfa_links(gfa::LinkTab t, u64 sec0, u64 
         const u64 A0 = max(sec0, tile * GFA_TILE), A1 = min(sec1, (tile + 1) * GFA_TILE);
         if (threadIdx.x == 0 || threadIdx.x == 64) {                 // the last i with loff[i] <= the tile's first / last byte
             const u64 o = threadIdx.x == 0 ? A0 - sec0 : A1 - 1 - sec0;
-            u64 lo = 0, hi = t.n - 1;
-            while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (t.loff[mid] <= o) lo = mid; else hi = mid - 1; }
-            si[threadIdx.x >> 6] = lo;
+            si[threadIdx.x >> 6] = last_le(t.loff, 0, t.n - 1, o);
         }
         __syncthreads();
         const u64 iA = si[0], iB = si[1];
@@ -150,41 +147,11 @@ void segment_ranks(const EdsView& v, u64* seg_rank, const u64* d_m1, u64* d_tota
     exclusive_scan_u64(seg_rank, seg_rank, d_m1, d_total, tmp, st);
 }
 
-struct GfaPipeline::Timed {
-    const char* name;
-    EventPair ev;
-    explicit Timed(const char* n) : name(n) {}
-};
-
-void GfaPipeline::add_time(const char* name, float ms)
-{
-    for (auto& a : acc_) if (std::string(a.name) == name) { a.total_ms += ms; a.count++; return; }
-    acc_.push_back({name, ms, 1});
-}
-
-int GfaPipeline::get_timing(const char** names, float* ms, int* counts, int cap) const
-{
-    int n = 0;
-    for (const auto& a : acc_) {
-        if (n >= cap) break;
-        names[n] = a.name; ms[n] = a.total_ms; counts[n] = a.count; n++;
-    }
-    return n;
-}
-
 void GfaPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, u64 max_links,
                       HostBytes& out, GfaInfo& info, hipStream_t st)
 {
     info = GfaInfo{};
-    std::deque<Timed> timed;
-    auto timed_run = [&](const char* name, auto&& launch) {
-        if (!timing_) { launch(); return; }
-        timed.emplace_back(name);
-        EDSX_HIP(hipEventRecord(timed.back().ev.a, st));
-        launch();
-        EDSX_HIP(hipEventRecord(timed.back().ev.b, st));
-    };
-    auto harvest = [&] { for (auto& t : timed) add_time(t.name, t.ev.ms()); timed.clear(); };
+    TimedRuns timed(st, &times_);
 
     de.load(eds, eds_n, seds, seds_n, seds != nullptr, st);
     const u64 n = de.n(), m = de.m(), N = de.n_chars();
@@ -204,17 +171,17 @@ void GfaPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uin
         u64 *ctl = ctl_.as<u64>(), *tmp = scan_tmp_.as<u64>(), *seg_rank = seg_rank_.as<u64>(), *C = cscan_.as<u64>(),
             *closed = closed_.as<u64>(), *vend = vend_.as<u64>(), *lcount = lcount_.as<u64>(), *loff = loff_.as<u64>();
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
-        timed_run("scan_segments", [&] { segment_ranks(v, seg_rank, ctl + CT_M1, ctl + CT_SEGS, tmp, st); });
-        timed_run("k_gfa_closed", [&] {
+        timed.run("scan_segments", [&] { segment_ranks(v, seg_rank, ctl + CT_M1, ctl + CT_SEGS, tmp, st); });
+        timed.run("k_gfa_closed", [&] {
             hipLaunchKernelGGL(k_gfa_closed, dim3(grid_for(n + 1, 8192)), dim3(GT), 0, st, v.sym.size, v.sym.ent_off, n, seg_rank, C);
         });
-        timed_run("scan_closed", [&] { exclusive_scan_u64(C, C, ctl + CT_N1, ctl + CT_CLOSED, tmp, st); });
-        timed_run("k_gfa_reach", [&] {
+        timed.run("scan_closed", [&] { exclusive_scan_u64(C, C, ctl + CT_N1, ctl + CT_CLOSED, tmp, st); });
+        timed.run("k_gfa_reach", [&] {
             hipLaunchKernelGGL(k_gfa_compact, dim3(grid_for(n, 8192)), dim3(GT), 0, st, C, n, closed);
             hipLaunchKernelGGL(k_gfa_reach, dim3(grid_for(n + 1, 8192)), dim3(GT), 0, st, v.sym.size, v.sym.ent_off, n, seg_rank, C, closed,
                                vend, lcount, loff);
         });
-        timed_run("scan_links", [&] {
+        timed.run("scan_links", [&] {
             ScanSet<2> ss{{lcount, loff}, {lcount, loff}, {ctl + CT_LINKS, ctl + CT_LBYTES}};
             exclusive_scan_multi<2>(ss, ctl + CT_N1, tmp, st);
         });
@@ -228,7 +195,7 @@ void GfaPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uin
     info.n_links = links; info.segment_bytes = sbytes; info.link_bytes = lbytes;
     const u64 cap = max_links ? max_links : 1ull << 32;
     if (links > cap) {
-        harvest();
+        timed.harvest();
         throw ParamError("Graph has " + std::to_string(links) + " links, above the limit of " + std::to_string(cap));
     }
 
@@ -238,19 +205,19 @@ void GfaPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uin
     uint8_t* o = out_.as<uint8_t>();
     EDSX_HIP(hipMemcpyAsync(o, header, gfa::HEADER_BYTES, hipMemcpyHostToDevice, st));
     if (sbytes)
-        timed_run("k_gfa_segments", [&] {
+        timed.run("k_gfa_segments", [&] {
             const gfa::SegTab t{seg_rank_.as<u64>(), v.str_off, v.elen, v.chars, m};
             hipLaunchKernelGGL(k_gfa_segments, dim3(tile_grid(gfa::HEADER_BYTES, sbytes)), dim3(GT), 0, st, t, (u64)gfa::HEADER_BYTES, sbytes, o);
         });
     if (lbytes)
-        timed_run("k_gfa_links", [&] {
+        timed.run("k_gfa_links", [&] {
             const gfa::LinkTab t{v.sym.size, v.sym.ent_off, seg_rank_.as<u64>(), vend_.as<u64>(), loff_.as<u64>(), n};
             hipLaunchKernelGGL(k_gfa_links, dim3(tile_grid(gfa::HEADER_BYTES + sbytes, lbytes)), dim3(GT), 0, st, t,
                                gfa::HEADER_BYTES + sbytes, lbytes, o);
         });
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    harvest();
+    timed.harvest();
     out.take(total);
     PinnedDownload::copy(out.data, o, total, st);
 }

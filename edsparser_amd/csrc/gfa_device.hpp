@@ -3,6 +3,7 @@
 #pragma once
 
 #include "eds_device.hpp"
+#include "kernel_times.hpp"
 #include "gfa_text.hpp"
 
 #include <vector>
@@ -31,16 +32,11 @@ public:
              GfaInfo& info, hipStream_t st);
 
     // device time per kernel, accumulated while on (edsx_set_timing / edsx_get_timing)
-    void set_timing(bool on) { timing_ = on; acc_.clear(); }
-    int get_timing(const char** names, float* ms, int* counts, int cap) const;
+    void set_timing(bool on) { times_.set(on); }
+    int get_timing(const char** names, float* ms, int* counts, int cap) const { return times_.get(names, ms, counts, cap); }
 
 private:
-    struct Acc { const char* name; float total_ms; int count; };
-    struct Timed;
-    void add_time(const char* name, float ms);
-
-    bool timing_ = false;
-    std::vector<Acc> acc_;
+    KernelTimes times_;
     DevBuf ctl_, scan_tmp_;
     DevBuf seg_rank_;                                            // per string (m + 1)
     DevBuf cscan_, closed_, vend_, lcount_, loff_;               // per symbol (n + 1)

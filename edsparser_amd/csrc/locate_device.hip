@@ -24,6 +24,7 @@
 // hit's number of choices; a scan of those is choice_off, and k_locate<M_CHOICES>, the same kernel, writes the choices.
 // No atomics on the result path; the counters use LDS atomics and the flags one atomicOr per flagged start.
 #include "locate_device.hpp"
+#include "kernel_times.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -286,14 +287,13 @@ void LocatePipeline::run(QueryPipeline& qp, DeviceEds& de, const uint8_t* eds, s
     str_sym_.ensure(8 * m);
     ctl_.ensure(8 * 4);
     u64* ctl = ctl_.as<u64>();                                  // scan lengths: [0] counters  [1] patterns  [2] hits
-    EventPair ev;
-    EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_loc_str_sym, dim3(grid_for(ns, 4096)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, ns,
-                       str_sym_.as<u64>());
-    EDSX_HIP(hipEventRecord(ev.b, st));
+    TimedRuns timed(st, nullptr);
+    timed.run("k_loc_str_sym", [&] {
+        hipLaunchKernelGGL(k_loc_str_sym, dim3(grid_for(ns, 4096)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, ns, str_sym_.as<u64>());
+    }, &info.tables_ms);
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    info.tables_ms += ev.ms();
+    timed.harvest();
 
     // patterns per launch: whole chunks, within the counter budget
     const u64 group = std::max<u64>(LCHUNK, COUNT_ENTRIES / ntiles / LCHUNK * LCHUNK);
@@ -327,20 +327,20 @@ void LocatePipeline::run(QueryPipeline& qp, DeviceEds& de, const uint8_t* eds, s
         // about 4096 blocks in flight, whatever the number of chunks; a block strides over the tiles
         const u64 chunks = (np + LCHUNK - 1) / LCHUNK;
         const dim3 grid((unsigned)std::min<u64>(ntiles, std::max<u64>(256, 4096 / chunks)), (unsigned)chunks);
-        EDSX_HIP(hipEventRecord(ev.a, st));
-        hipLaunchKernelGGL(k_locate<M_COUNT>, grid, dim3(LNT), 0, st, a);
-        exclusive_scan_u64(a.counts, a.counts, ctl, a.counts + len, scan_tmp_.as<u64>(), st);
-        hipLaunchKernelGGL(k_loc_kept, dim3(grid_for(np, 4096)), dim3(256), 0, st, a.counts, ntiles, np, max_hits, totals_.as<u64>(),
-                           kept_.as<u64>(), a.flags);
-        exclusive_scan_u64(kept_.as<u64>(), hoff_.as<u64>(), ctl + 1, hoff_.as<u64>() + np, scan_tmp_.as<u64>(), st);
-        EDSX_HIP(hipEventRecord(ev.b, st));
+        timed.run("count", [&] {
+            hipLaunchKernelGGL(k_locate<M_COUNT>, grid, dim3(LNT), 0, st, a);
+            exclusive_scan_u64(a.counts, a.counts, ctl, a.counts + len, scan_tmp_.as<u64>(), st);
+            hipLaunchKernelGGL(k_loc_kept, dim3(grid_for(np, 4096)), dim3(256), 0, st, a.counts, ntiles, np, max_hits, totals_.as<u64>(),
+                               kept_.as<u64>(), a.flags);
+            exclusive_scan_u64(kept_.as<u64>(), hoff_.as<u64>(), ctl + 1, hoff_.as<u64>() + np, scan_tmp_.as<u64>(), st);
+        }, &info.kernel_ms);
         hoff.resize(np + 1); flg.resize(np);
         EDSX_HIP(hipMemcpyAsync(hoff.data(), hoff_.ptr, 8 * (np + 1), hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipMemcpyAsync(out.totals.data() + g0, totals_.ptr, 8 * np, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipMemcpyAsync(flg.data(), flags_.ptr, 4 * np, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        info.kernel_ms += ev.ms();
+        timed.harvest();
         const u64 H = hoff[np], h0 = out.hits.size();
         for (u64 q = 0; q < np; q++) { out.flags[g0 + q] = (uint8_t)flg[q]; out.hit_off[g0 + q + 1] = h0 + hoff[q + 1]; }
         if (H == 0) continue;
@@ -349,24 +349,22 @@ void LocatePipeline::run(QueryPipeline& qp, DeviceEds& de, const uint8_t* eds, s
         scan_tmp_.ensure(8 * (std::max(len, H) / SCAN_TILE + 4));
         EDSX_HIP(hipMemcpyAsync(ctl + 2, &H, 8, hipMemcpyHostToDevice, st));
         a.hits = hits_.as<LocateHit>(); a.hit_k = hit_k_.as<u64>(); a.coff = coff_.as<u64>();
-        EDSX_HIP(hipEventRecord(ev.a, st));
-        hipLaunchKernelGGL(k_locate<M_HITS>, grid, dim3(LNT), 0, st, a);
-        exclusive_scan_u64(a.hit_k, coff_.as<u64>(), ctl + 2, coff_.as<u64>() + H, scan_tmp_.as<u64>(), st);
-        EDSX_HIP(hipEventRecord(ev.b, st));
+        timed.run("hits", [&] {
+            hipLaunchKernelGGL(k_locate<M_HITS>, grid, dim3(LNT), 0, st, a);
+            exclusive_scan_u64(a.hit_k, coff_.as<u64>(), ctl + 2, coff_.as<u64>() + H, scan_tmp_.as<u64>(), st);
+        }, &info.kernel_ms);
         u64 K = 0;
         EDSX_HIP(hipMemcpyAsync(&K, coff_.as<u64>() + H, 8, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        info.kernel_ms += ev.ms();
+        timed.harvest();
         if (K) {
             choices_.ensure(4 * K);
             a.choices = choices_.as<int32_t>();
-            EDSX_HIP(hipEventRecord(ev.a, st));
-            hipLaunchKernelGGL(k_locate<M_CHOICES>, grid, dim3(LNT), 0, st, a);
-            EDSX_HIP(hipEventRecord(ev.b, st));
+            timed.run("choices", [&] { hipLaunchKernelGGL(k_locate<M_CHOICES>, grid, dim3(LNT), 0, st, a); }, &info.kernel_ms);
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
-            info.kernel_ms += ev.ms();
+            timed.harvest();
         }
         const auto t0 = std::chrono::steady_clock::now();
         const u64 k0 = out.choices.size();

@@ -40,7 +40,12 @@
 //              k_path_align    the shape of k_path_copy over columns instead of characters: col does not depend on the
 //                              path, so the symbol range of a step needs no table row; 2000 symbols per step in LDS,
 //                              those behind them from global memory; gap runs are stores without a load
+//
+// spell, align and walks write records - a header text and a body - through one driver, emit_records: the arithmetic of
+// the records and of their batches is path_records.hpp; each of the three brings its tables and its body kernel.  The
+// coordinate lift and the region slice of the session: lift_device.hip, slice_device.hip.
 #include "path_device.hpp"
+#include "gfa_device.hpp"
 
 #include <chrono>
 #include <cstdlib>
@@ -527,138 +532,6 @@ __global__ void __launch_bounds__(CP_THREADS) k_path_walk(WalkArgs a)
     }
 }
 
-// ---- coordinate lift: point queries over the same tables (lift_core.hpp) ----------------------------------
-constexpr u32 LF_TOP = 2048;         // sym_pos of evenly spaced symbols kept in LDS per work item (16 KiB)
-constexpr u32 LF_ITEM = 2048;        // queries of one table row per work item
-constexpr u32 LF_MIN = 256;          // a work item with fewer queries does not fill the LDS table: global search only
-
-constexpr u32 LG_ROWS = 4096;        // rows whose counters a workgroup keeps in LDS (16 KiB)
-constexpr u32 LG_PER = 16;           // queries per lane and tile
-
-// queries to table rows, in two passes over cur (one entry per distinct path of the call, D of them): perm == null counts
-// the queries of every row; after the scan, with cur[d] the first slot of row d, perm != null hands every query a slot of
-// its row.  A workgroup takes tiles of 4096 queries: it counts the rows of a tile in LDS, asks for the slots of each row
-// with one global atomic, and the queries take theirs by the rank the LDS atomic gave them - a few rows with millions of
-// queries would otherwise queue up on a few addresses.  More than LG_ROWS rows: one global atomic per query, spread over
-// as many addresses.  The order inside a row is whatever the atomics give: every query keeps its own index, so no result
-// depends on it.  Slots are below 2^28 (the chunk size of lift()).
-__global__ void __launch_bounds__(256) k_lift_group(const u64* __restrict__ path, u64 nq, const u32* __restrict__ rowmap, u64 D,
-                                                    u64* __restrict__ cur, u32* __restrict__ perm)
-{
-    __shared__ u32 cnt[LG_ROWS];
-    const u64 tile = 256ull * LG_PER;
-    const bool local = D <= LG_ROWS;                                      // the same for every workgroup
-    for (u64 t0 = blockIdx.x * tile; t0 < nq; t0 += (u64)gridDim.x * tile) {
-        if (!local) {
-            for (u32 j = 0; j < LG_PER; j++) {
-                const u64 q = t0 + (u64)j * 256 + threadIdx.x;
-                if (q >= nq) break;
-                const u64 slot = atomicAdd((unsigned long long*)&cur[rowmap[path[q]]], 1ull);
-                if (perm) perm[slot] = (u32)q;
-            }
-            continue;
-        }
-        for (u32 r = threadIdx.x; r < (u32)D; r += 256) cnt[r] = 0;
-        __syncthreads();
-        u32 row[LG_PER], idx[LG_PER];
-#pragma unroll
-        for (u32 j = 0; j < LG_PER; j++) {
-            const u64 q = t0 + (u64)j * 256 + threadIdx.x;
-            row[j] = q < nq ? rowmap[path[q]] : ~0u;
-        }
-#pragma unroll
-        for (u32 j = 0; j < LG_PER; j++) idx[j] = row[j] != ~0u ? atomicAdd(&cnt[row[j]], 1u) : 0u;
-        __syncthreads();
-        for (u32 r = threadIdx.x; r < (u32)D; r += 256) {                 // the tile's count of row r becomes its first slot
-            const u32 c = cnt[r];
-            if (c) cnt[r] = (u32)atomicAdd((unsigned long long*)&cur[r], (unsigned long long)c);
-        }
-        __syncthreads();
-        if (perm) {
-#pragma unroll
-            for (u32 j = 0; j < LG_PER; j++)
-                if (row[j] != ~0u) perm[cnt[row[j]] + idx[j]] = (u32)(t0 + (u64)j * 256 + threadIdx.x);
-        }
-        __syncthreads();                                                  // the next tile clears cnt
-    }
-}
-
-struct LiftItem { u64 row, q0, q1; };        // slots [q0, q1) of perm hold queries of this row of the current tables
-
-// One workgroup per item.  It keeps sym_pos of every stride-th symbol of its row in LDS; a lane finds the stretch of
-// its query there and finishes with at most log2(stride) dependent steps in global memory.
-__global__ void __launch_bounds__(CP_THREADS) k_lift_find(lift::LiftTab t, const LiftItem* __restrict__ items, u64 nitems,
-                                                          const u32* __restrict__ perm, const u64* __restrict__ qpos,
-                                                          lift::Site* __restrict__ site, uint8_t* __restrict__ status)
-{
-    __shared__ u64 top[LF_TOP];
-    const u64 stride = (t.n + LF_TOP - 1) / LF_TOP;
-    for (u64 it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const LiftItem item = items[it];
-        const u64 kb = item.row * t.nc;
-        const bool sampled = item.q1 - item.q0 >= LF_MIN && t.n > LF_TOP;      // the same for the whole workgroup
-        __syncthreads();                                                       // the last item's readers of top are through
-        if (sampled) {
-            for (u32 j = threadIdx.x; j < LF_TOP; j += CP_THREADS) {
-                const u64 i = (u64)j * stride;
-                top[j] = i < t.n ? lift::sym_pos(t, kb, i) : NONE;
-            }
-            __syncthreads();
-        }
-        const u64 len = lift::sym_pos(t, kb, t.n);
-        for (u64 k = item.q0 + threadIdx.x; k < item.q1; k += CP_THREADS) {
-            const u64 q = perm[k], x = qpos[q];
-            lift::Site s;
-            uint8_t stt = lift::RANGE;
-            if (x >= len) lift::no_site(s);
-            else {
-                u64 lo = 0, hi = t.n;
-                if (sampled) {
-                    u32 a = 0, b = LF_TOP;                                     // top[0] = 0 <= x
-                    while (b - a > 1) { const u32 mid = (a + b) >> 1; if (top[mid] <= x) a = mid; else b = mid; }
-                    lo = (u64)a * stride;
-                    hi = min(lo + stride, t.n);
-                }
-                lift::site_at(t, kb, lift::search(t, kb, lo, hi, x), x, s);
-                stt = 0;
-            }
-            site[q] = s;
-            status[q] = stt;
-        }
-    }
-}
-
-// one lane per query of slots [k0, k1): the tables hold the rows of the distinct paths d0 ..; no search
-__global__ void __launch_bounds__(256) k_lift_place(lift::LiftTab t, const u32* __restrict__ perm, u64 k0, u64 k1,
-                                                    const u64* __restrict__ dpath, const u32* __restrict__ rowmap, u64 d0,
-                                                    const lift::Site* __restrict__ site, const uint8_t* __restrict__ st_in,
-                                                    u64* __restrict__ pos, uint8_t* __restrict__ st_out)
-{
-    for (u64 k = k0 + blockIdx.x * (u64)blockDim.x + threadIdx.x; k < k1; k += (u64)gridDim.x * blockDim.x) {
-        const u64 q = perm[k], kb = ((u64)rowmap[dpath[q]] - d0) * t.nc;
-        u64 p = NONE;
-        uint8_t stt = lift::RANGE;
-        if (st_in[q] != lift::RANGE) stt = lift::place(t, kb, site[q].symbol, site[q].string, site[q].offset, p);
-        pos[q] = p;
-        st_out[q] = stt;
-    }
-}
-
-// the (symbol, string, offset) columns of a lift_place call as sites (the other two fields are not read)
-__global__ void k_lift_pack(const u64* __restrict__ symbol, const u64* __restrict__ string, const u64* __restrict__ offset, u64 nq,
-                            lift::Site* __restrict__ site)
-{
-    for (u64 q = blockIdx.x * (u64)blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x)
-        site[q] = lift::Site{symbol[q], string[q], offset[q], 0, 0};
-}
-
-// common characters of symbol i into cc[i] (scanned in place afterwards; cc[n] = 0 becomes the total)
-__global__ void k_lift_common(const u64* __restrict__ size, const u64* __restrict__ len1, u64 n, u64* __restrict__ cc)
-{
-    for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i <= n; i += (u64)gridDim.x * blockDim.x)
-        cc[i] = i < n && size[i] == 1 ? len1[i] : 0;
-}
-
 u64 free_hbm()
 {
     size_t free_b = 0, total_b = 0;
@@ -666,19 +539,8 @@ u64 free_hbm()
     return free_b;
 }
 
-// the header lines ">name\n" of n records laid end to end in blob (names[k], else prefix - null: "path" - + id); -> where each begins
-std::vector<u64> fasta_headers(const u64* ids, size_t n, const char* const* names, const char* prefix, std::string& blob)
-{
-    std::vector<u64> hoff(n + 1, 0);
-    const std::string pre = prefix ? prefix : "path";
-    for (size_t k = 0; k < n; k++) {
-        blob += '>';
-        if (names) blob += names[k]; else blob += pre + std::to_string(ids[k]);
-        blob += '\n';
-        hoff[k + 1] = blob.size();
-    }
-    return hoff;
-}
+// the grid of a body kernel: a workgroup per (tile, record), capped
+unsigned body_grid(u64 nrec, u64 max_tiles) { return (unsigned)std::min<u64>(max_tiles * nrec, 1u << 20); }
 
 } // namespace
 
@@ -687,10 +549,7 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     if (!seds) throw ParamError("Path spelling needs sources (.seds)");
     info_ = PathInfo{};
     timing_ = PathTiming{};
-    walk_ready_ = false;
-    align_ready_ = false;
-    lift_ready_ = false;
-    slice_ready_ = false;
+    walk_.ready = align_.ready = lift_.ready = slice_.ready = false;
     const auto t0 = std::chrono::steady_clock::now();
     eds_.load(eds, eds_n, seds, seds_n, true, st);
     eds_.drop_scratch();                                                      // the session may live long
@@ -741,18 +600,25 @@ void PathPipeline::check_ids(const u64* ids, size_t n) const
             throw ParamError("Path id " + std::to_string(ids[k]) + " out of range (1.." + std::to_string(info_.num_paths) + ")");
 }
 
-// EDSX_PATHS_BUDGET (bytes): stands in for the free HBM the batch sizes are taken from (the tests force several batches)
-u64 PathPipeline::budget_override()
+void PathPipeline::begin_call()
+{
+    const double tok = timing_.tokenise_ms;
+    timing_ = PathTiming{};
+    timing_.tokenise_ms = tok;
+}
+
+// the bytes a batch may take: EDSX_PATHS_BUDGET when set (the tests force several batches), else that part of the free HBM
+u64 PathPipeline::budget(u64 part)
 {
     const char* e = getenv("EDSX_PATHS_BUDGET");
-    return e ? std::strtoull(e, nullptr, 10) : 0;
+    const u64 ov = e ? std::strtoull(e, nullptr, 10) : 0;
+    return ov ? ov : free_hbm() / part;
 }
 
 // paths per choice table: 16 bytes per (path, choice symbol) within a quarter of the free HBM (24 with the token bytes)
 u64 PathPipeline::table_batch(size_t n, u64 cell_bytes) const
 {
-    const u64 ov = budget_override(), budget = ov ? ov : free_hbm() / 4;
-    return std::max<u64>(1, std::min<u64>(n, budget / (cell_bytes * nc_ + 64)));
+    return std::max<u64>(1, std::min<u64>(n, budget(4) / (cell_bytes * nc_ + 64)));
 }
 
 void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st)
@@ -761,7 +627,7 @@ void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vec
     ids_.ensure(8 * K); miss_.ensure(8 * K); tot_.ensure(8 * K);
     EDSX_HIP(hipMemcpyAsync(ids_.ptr, ids, 8 * K, hipMemcpyHostToDevice, st));
     EDSX_HIP(hipMemsetAsync(miss_.ptr, 0, 8 * K, st));
-    EventPair ec, es;
+    TimedRuns timed(st, nullptr);
     const u64 cells = K * nc_;
     if (nc_) {
         csid_.ensure(8 * cells);
@@ -769,29 +635,27 @@ void PathPipeline::tables(const u64* ids, u64 K, std::vector<u64>& len, std::vec
         scan_tmp_.ensure(8 * (cells / SCAN_TILE + 4));
         ctl_.ensure(8 * 8);
         EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &cells, 8, hipMemcpyHostToDevice, st));
-        EDSX_HIP(hipEventRecord(ec.a, st));
         const EdsView v = eds_.view();
-        hipLaunchKernelGGL(k_path_choose, dim3(grid_for(cells, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, v.bits,
-                           v.W, cidx_.as<u64>(), nc_, ids_.as<u64>(), K, csid_.as<u64>(), clen_.as<u64>(), miss_.as<u64>());
-        EDSX_HIP(hipEventRecord(ec.b, st));
-        EDSX_HIP(hipEventRecord(es.a, st));
-        exclusive_scan_u64(clen_.as<u64>(), clen_.as<u64>(), ctl_.as<u64>(), clen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
-        EDSX_HIP(hipEventRecord(es.b, st));
+        timed.run("k_path_choose", [&] {
+            hipLaunchKernelGGL(k_path_choose, dim3(grid_for(cells, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, v.bits,
+                               v.W, cidx_.as<u64>(), nc_, ids_.as<u64>(), K, csid_.as<u64>(), clen_.as<u64>(), miss_.as<u64>());
+        }, &timing_.choose_ms);
+        timed.run("scan_cells", [&] {
+            exclusive_scan_u64(clen_.as<u64>(), clen_.as<u64>(), ctl_.as<u64>(), clen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
+        }, &timing_.scan_ms);
     }
     hipLaunchKernelGGL(k_path_totals, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, clen_.as<u64>(), nc_, F_, K, tot_.as<u64>());
     EDSX_HIP(hipMemcpyAsync(len.data(), tot_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipMemcpyAsync(miss.data(), miss_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    if (nc_) { timing_.choose_ms += ec.ms(); timing_.scan_ms += es.ms(); }
+    timed.harvest();
 }
 
 void PathPipeline::lengths(const u64* ids, size_t n, u64* length, u64* missing, hipStream_t st)
 {
     check_ids(ids, n);
-    const double tok = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tok;
+    begin_call();
     if (n == 0) return;
     const u64 KT = table_batch(n);
     std::vector<u64> len, miss;
@@ -803,103 +667,96 @@ void PathPipeline::lengths(const u64* ids, size_t n, u64* length, u64* missing, 
     }
 }
 
-void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, HostBytes& out,
-                         u64* missing, hipStream_t st)
+template <class Tables, class Body>
+void PathPipeline::emit_records(records::Rule rule, size_t n, const records::Headers& hdr, u64 line_width, u64 cell_bytes,
+                                HostBytes& out, u64* missing, Tables&& make_tables, Body&& launch_body, hipStream_t st)
 {
-    check_ids(ids, n);
-    const double tok = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tok;
-    out.take(0);
-    if (n == 0) return;
-    std::string blob;
-    const std::vector<u64> hoff = fasta_headers(ids, n, names, prefix, blob);
-    // lengths of all requested paths; one table batch: its tables stay for the copy
-    const u64 KT = table_batch(n);
+    // lengths and missing counts of all requested paths; one table batch: its tables stay for the bodies
+    const u64 KT = table_batch(n, cell_bytes);
     const bool single = KT >= n;
     std::vector<u64> len(n), miss(n), bl, bm;
     for (size_t i0 = 0; i0 < n; i0 += KT) {
         const u64 K = std::min<u64>(KT, n - i0);
-        tables(ids + i0, K, bl, bm, st);
+        make_tables(i0, K, bl, bm);
         std::memcpy(len.data() + i0, bl.data(), 8 * K);
         std::memcpy(miss.data() + i0, bm.data(), 8 * K);
     }
     if (missing) std::memcpy(missing, miss.data(), 8 * n);
-    std::vector<PathRec> rec(n);
-    std::vector<u64> host_off(n + 1, 0);                        // record starts in the caller's buffer
-    for (size_t k = 0; k < n; k++) {
-        PathRec& r = rec[k];
-        r.L = len[k];
-        r.lw = (line_width == 0 || line_width > r.L) ? std::max<u64>(r.L, 1) : line_width;
-        r.body = r.L ? r.L + (r.L + r.lw - 1) / r.lw : 0;
-        r.hdr_src = hoff[k];
-        r.row = k % KT;
-        host_off[k + 1] = host_off[k] + (hoff[k + 1] - hoff[k]) + r.body;
-    }
-    const u64 total = host_off[n];
+    const records::Layout lay = records::layout(rule, len.data(), n, hdr.off.data(), line_width, KT);
+    const u64 total = lay.start[n];
     out.take(total);
     timing_.bytes_written = total;
-    hdr_.ensure(blob.size());
-    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
+    if (total == 0) return;
+    hdr_.ensure(hdr.blob.size());
+    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, hdr.blob.data(), hdr.blob.size(), hipMemcpyHostToDevice, st));
+    const u64 out_budget = budget(2);
+    std::vector<PathRec> batch;
     for (size_t i0 = 0; i0 < n; i0 += KT) {
         const size_t i1 = std::min<size_t>(n, i0 + KT);
-        if (!single) tables(ids + i0, i1 - i0, bl, bm, st);
-        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many records as the budget holds
-            size_t r1 = r0 + 1;
-            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
-            const u64 bytes = host_off[r1] - host_off[r0], nrec = r1 - r0;
-            u64 max_body = 0;
-            for (size_t k = r0; k < r1; k++) {
-                rec[k].rec_off = host_off[k] - host_off[r0];
-                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
-                max_body = std::max(max_body, rec[k].body);
-            }
+        if (!single) make_tables(i0, i1 - i0, bl, bm);
+        for (size_t r0 = i0, r1; r0 < i1; r0 = r1) {
+            r1 = records::batch_end(lay.start, r0, i1, out_budget);
+            const u64 bytes = lay.start[r1] - lay.start[r0], max_body = records::batch_records(lay, hdr.off.data(), r0, r1, batch);
+            if (batch.empty()) continue;
+            const u64 nrec = batch.size(), max_tiles = (max_body + CP_TILE - 1) / CP_TILE;
             out_.ensure(bytes + 16);                             // 16 bytes of slack behind the text, as every output buffer here
             rec_.ensure(sizeof(PathRec) * nrec);
-            EDSX_HIP(hipMemcpyAsync(rec_.ptr, rec.data() + r0, sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
-            const EdsView v = eds_.view();
-            CopyArgs a{v.sym.ent_off, v.str_off, v.chars, cum_fixed_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, nc_ ? clen_.as<u64>() : nullptr, n_, nc_,
-                       rec_.as<PathRec>(), nrec, (max_body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>()};
-            EventPair ev;
-            EDSX_HIP(hipEventRecord(ev.a, st));
-            hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
-            const u64 work = a.max_tiles * nrec;
-            if (work) hipLaunchKernelGGL(k_path_copy, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
-            EDSX_HIP(hipEventRecord(ev.b, st));
+            EDSX_HIP(hipMemcpyAsync(rec_.ptr, batch.data(), sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
+            TimedRuns timed(st, nullptr);
+            timed.run("records", [&] {
+                hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), out_.as<uint8_t>());
+                if (max_tiles) launch_body(rec_.as<PathRec>(), nrec, max_tiles, out_.as<uint8_t>());
+            }, &timing_.copy_ms);
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
-            timing_.copy_ms += ev.ms();
+            timed.harvest();
             const auto t0 = std::chrono::steady_clock::now();
-            PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
+            PinnedDownload::copy(out.data + lay.start[r0], out_.ptr, bytes, st);
             timing_.download_ms += since_ms(t0);
-            r0 = r1;
         }
     }
 }
 
+void PathPipeline::spell(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, HostBytes& out,
+                         u64* missing, hipStream_t st)
+{
+    check_ids(ids, n);
+    begin_call();
+    out.take(0);
+    if (n == 0) return;
+    const EdsView v = eds_.view();
+    emit_records(records::FASTA, n, records::fasta_headers(ids, n, names, prefix), line_width, 16, out, missing,
+        [&](size_t i0, u64 K, std::vector<u64>& len, std::vector<u64>& miss) { tables(ids + i0, K, len, miss, st); },
+        [&](const PathRec* rec, u64 nrec, u64 max_tiles, uint8_t* dst) {
+            const CopyArgs a{v.sym.ent_off, v.str_off, v.chars, cum_fixed_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr,
+                             nc_ ? clen_.as<u64>() : nullptr, n_, nc_, rec, nrec, max_tiles, dst};
+            hipLaunchKernelGGL(k_path_copy, dim3(body_grid(nrec, max_tiles)), dim3(CP_THREADS), 0, st, a);
+        }, st);
+}
+
 void PathPipeline::align_open(hipStream_t st)
 {
-    if (align_ready_) return;
-    ainfo_ = AlignInfo{};
-    ainfo_.n_symbols = n_; ainfo_.num_paths = info_.num_paths;
+    if (align_.ready) return;
+    AlignInfo& ai = align_.info;
+    ai = AlignInfo{};
+    ai.n_symbols = n_; ai.num_paths = info_.num_paths;
     if (n_) {
         const EdsView v = eds_.view();
-        col_.ensure(8 * (n_ + 1));
+        align_.col.ensure(8 * (n_ + 1));
         ctl_.ensure(8 * 8);
         scan_tmp_.ensure(8 * (n_ / SCAN_TILE + 4));
         u64 h[4] = {n_ + 1, 0, 0, 0};                            // count; W; symbols of width 0; the widest
-        u64* ctl = ctl_.as<u64>();
+        u64 *ctl = ctl_.as<u64>(), *col = align_.col.as<u64>();
         EDSX_HIP(hipMemcpyAsync(ctl, h, sizeof(h), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_align_width, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, n_,
-                           col_.as<u64>(), ctl + 2);
-        exclusive_scan_u64(col_.as<u64>(), col_.as<u64>(), ctl, ctl + 1, scan_tmp_.as<u64>(), st);
+        hipLaunchKernelGGL(k_align_width, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.size, v.sym.ent_off, v.str_off, n_, col,
+                           ctl + 2);
+        exclusive_scan_u64(col, col, ctl, ctl + 1, scan_tmp_.as<u64>(), st);
         EDSX_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        ainfo_.n_columns = h[1]; ainfo_.n_zero_width_symbols = h[2]; ainfo_.widest_symbol = h[3];
+        ai.n_columns = h[1]; ai.n_zero_width_symbols = h[2]; ai.widest_symbol = h[3];
     }
-    align_ready_ = true;
+    align_.ready = true;
 }
 
 void PathPipeline::align(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, uint8_t gap,
@@ -907,259 +764,57 @@ void PathPipeline::align(const u64* ids, size_t n, const char* const* names, con
 {
     check_ids(ids, n);
     if (std::strchr(">\n\r {},", gap)) throw ParamError("Gap character is not usable in an alignment");   // (and 0)
-    const double tok = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tok;
+    begin_call();
     out.take(0);
     if (n == 0) return;
     align_open(st);
-    // header texts, and the size of the whole: every row has W columns, so the counts give it
-    const u64 W = ainfo_.n_columns;
-    const u64 lw = (line_width == 0 || line_width > W) ? std::max<u64>(W, 1) : line_width;
-    const u64 body = W ? W + (W + lw - 1) / lw : 0;
-    std::string blob;
-    const std::vector<u64> hoff = fasta_headers(ids, n, names, prefix, blob);
-    const unsigned __int128 total128 = (unsigned __int128)body * n + blob.size();
+    // header texts, and the size of the whole: every row has W columns, so the counts give it before any table is made
+    const u64 W = align_.info.n_columns;
+    const records::Headers hdr = records::fasta_headers(ids, n, names, prefix);
+    u64 lw, body;
+    records::body_of(records::FASTA, W, line_width, lw, body);
+    const unsigned __int128 total128 = (unsigned __int128)body * n + hdr.blob.size();
     if ((max_bytes && total128 > max_bytes) || total128 > ~0ull) {
         const std::string cap = std::to_string(max_bytes ? max_bytes : ~0ull);
         const std::string have = total128 > ~0ull ? "more than " + std::to_string(~0ull) : std::to_string((u64)total128);
         throw ParamError("Alignment has " + have + " bytes, above the limit of " + cap);
     }
-    const u64 total = (u64)total128;
-    // the missing counts of all requested paths; one table batch: its table stays for the rows
-    const u64 KT = table_batch(n);
-    const bool single = KT >= n;
-    std::vector<u64> miss(n), bl, bm;
-    for (size_t i0 = 0; i0 < n; i0 += KT) {
-        const u64 K = std::min<u64>(KT, n - i0);
-        tables(ids + i0, K, bl, bm, st);
-        std::memcpy(miss.data() + i0, bm.data(), 8 * K);
-    }
-    if (missing) std::memcpy(missing, miss.data(), 8 * n);
-    std::vector<PathRec> rec(n);
-    std::vector<u64> host_off(n + 1, 0);                        // record starts in the caller's buffer
-    for (size_t k = 0; k < n; k++) {
-        PathRec& r = rec[k];
-        r.L = W; r.lw = lw; r.body = body;
-        r.hdr_src = hoff[k];
-        r.row = k % KT;
-        host_off[k + 1] = host_off[k] + (hoff[k + 1] - hoff[k]) + body;
-    }
-    out.take(total);
-    timing_.bytes_written = total;
-    hdr_.ensure(blob.size());
-    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
-    for (size_t i0 = 0; i0 < n; i0 += KT) {
-        const size_t i1 = std::min<size_t>(n, i0 + KT);
-        if (!single) tables(ids + i0, i1 - i0, bl, bm, st);
-        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many records as the budget holds
-            size_t r1 = r0 + 1;
-            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
-            const u64 bytes = host_off[r1] - host_off[r0], nrec = r1 - r0;
-            for (size_t k = r0; k < r1; k++) {
-                rec[k].rec_off = host_off[k] - host_off[r0];
-                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
-            }
-            out_.ensure(bytes + 16);                             // 16 bytes of slack behind the text, as every output buffer here
-            rec_.ensure(sizeof(PathRec) * nrec);
-            EDSX_HIP(hipMemcpyAsync(rec_.ptr, rec.data() + r0, sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
-            const EdsView v = eds_.view();
-            AlignArgs a{v.sym.ent_off, v.str_off, v.chars, col_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, n_, nc_,
-                        rec_.as<PathRec>(), nrec, (body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>(), gap};
-            EventPair ev;
-            EDSX_HIP(hipEventRecord(ev.a, st));
-            hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
-            const u64 work = a.max_tiles * nrec;
-            if (work) hipLaunchKernelGGL(k_path_align, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
-            EDSX_HIP(hipEventRecord(ev.b, st));
-            EDSX_HIP(hipStreamSynchronize(st));
-            EDSX_HIP(hipGetLastError());
-            timing_.copy_ms += ev.ms();
-            const auto t0 = std::chrono::steady_clock::now();
-            PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
-            timing_.download_ms += since_ms(t0);
-            r0 = r1;
-        }
-    }
-}
-
-void PathPipeline::lift_open(hipStream_t st)
-{
-    align_open(st);                                              // col
-    if (lift_ready_ || n_ == 0) return;
     const EdsView v = eds_.view();
-    cum_common_.ensure(8 * (n_ + 1));
-    ctl_.ensure(8 * 8);
-    scan_tmp_.ensure(8 * (n_ / SCAN_TILE + 4));
-    const u64 cnt = n_ + 1;
-    u64* ctl = ctl_.as<u64>();
-    EDSX_HIP(hipMemcpyAsync(ctl, &cnt, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_lift_common, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.size, v.sym.len1, n_, cum_common_.as<u64>());
-    exclusive_scan_u64(cum_common_.as<u64>(), cum_common_.as<u64>(), ctl, ctl + 1, scan_tmp_.as<u64>(), st);
-    EDSX_HIP(hipStreamSynchronize(st));
-    EDSX_HIP(hipGetLastError());
-    lift_ready_ = true;
-}
-
-// queries [0, m) of lq_path_ to the rows of the D distinct paths: lperm_ holds them row by row, start (D + 1) where each row begins
-void PathPipeline::lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t st)
-{
-    u64 *cnt = lcnt_.as<u64>(), *cur = lcur_.as<u64>();
-    EDSX_HIP(hipMemsetAsync(cnt, 0, 8 * (D + 1), st));
-    EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &D, 8, hipMemcpyHostToDevice, st));
-    const unsigned grid = (unsigned)std::min<u64>((m + 256 * LG_PER - 1) / (256 * LG_PER), 4096);
-    hipLaunchKernelGGL(k_lift_group, dim3(grid), dim3(256), 0, st, lq_path_.as<u64>(), m, lmap_.as<u32>(), D, cnt, (u32*)nullptr);
-    exclusive_scan_u64(cnt, cnt, ctl_.as<u64>(), cnt + D, scan_tmp_.as<u64>(), st);
-    EDSX_HIP(hipMemcpyAsync(cur, cnt, 8 * D, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_lift_group, dim3(grid), dim3(256), 0, st, lq_path_.as<u64>(), m, lmap_.as<u32>(), D, cur, lperm_.as<u32>());
-    start.assign(D + 1, 0);
-    EDSX_HIP(hipMemcpyAsync(start.data(), cnt, 8 * (D + 1), hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipStreamSynchronize(st));
-    EDSX_HIP(hipGetLastError());
-}
-
-void PathPipeline::lift(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path,
-                        LiftSite* site_out, u64* dst_pos, uint8_t* status, hipStream_t st)
-{
-    lift_run(n, src_path, src_pos, site_in, dst_path, site_out, dst_pos, status, nullptr, nullptr, st);
-}
-
-// dev_site / dev_status (device memory, n entries each; only with src_path and without dst_path): the sites and their
-// statuses stay on the device for the caller's kernels, and nothing is downloaded
-void PathPipeline::lift_run(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path,
-                            LiftSite* site_out, u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st)
-{
-    const bool find = src_path != nullptr, put = dst_path != nullptr;
-    if (find) check_ids(src_path, n);
-    if (put) check_ids(dst_path, n);
-    const double tok = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tok;
-    if (n == 0) return;
-    lift_open(st);
-    // the distinct paths of the call, ascending: one table row each
-    const u64 P = info_.num_paths;
-    std::vector<u32> rowmap(P + 1, 0);
-    for (size_t q = 0; q < n; q++) {
-        if (find) rowmap[src_path[q]] = 1;
-        if (put) rowmap[dst_path[q]] = 1;
-    }
-    std::vector<u64> ids;
-    for (u64 p = 1; p <= P; p++) if (rowmap[p]) { rowmap[p] = (u32)ids.size(); ids.push_back(p); }
-    const u64 D = ids.size();
-    lmap_.ensure(4 * (P + 1));
-    EDSX_HIP(hipMemcpyAsync(lmap_.ptr, rowmap.data(), 4 * (P + 1), hipMemcpyHostToDevice, st));
-    const u64 KT = table_batch(D);
-    const bool single = KT >= D;
-    std::vector<u64> bl, bm, start;
-    if (single) tables(ids.data(), D, bl, bm, st);               // one table batch: made once for every chunk and both steps
-    // queries per chunk: 88 bytes each within a quarter of the free HBM, never fewer than 65 536
-    const u64 ov = budget_override(), budget = ov ? ov : free_hbm() / 4;
-    const u64 QC = std::min<u64>(std::max<u64>(budget / 88, 1u << 16), 1u << 28);
-    lcnt_.ensure(8 * (D + 1)); lcur_.ensure(8 * (D + 1));
-    ctl_.ensure(8 * 8);
-    scan_tmp_.ensure(8 * (D / SCAN_TILE + 4));
-    const EdsView v = eds_.view();
-    auto tab = [&] {
-        return lift::LiftTab{v.sym.size, v.sym.ent_off, v.str_off, cum_fixed_.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr,
-                             nc_ ? clen_.as<u64>() : nullptr, col_.as<u64>(), cum_common_.as<u64>(), n_, nc_};
-    };
-    std::vector<LiftItem> items;
-    for (size_t c0 = 0; c0 < n; c0 += QC) {
-        const u64 m = std::min<u64>(QC, n - c0);
-        lq_path_.ensure(8 * m); lq_pos_.ensure(8 * m); lperm_.ensure(4 * m); lsite_.ensure(sizeof(LiftSite) * m);
-        lst_.ensure(m); lst2_.ensure(m);
-        if (find) {
-            EDSX_HIP(hipMemcpyAsync(lq_path_.ptr, src_path + c0, 8 * m, hipMemcpyHostToDevice, st));
-            EDSX_HIP(hipMemcpyAsync(lq_pos_.ptr, src_pos + c0, 8 * m, hipMemcpyHostToDevice, st));
-            lift_group(m, D, start, st);
-            for (u64 d0 = 0; d0 < D; d0 += KT) {
-                const u64 d1 = std::min<u64>(D, d0 + KT);
-                if (start[d1] == start[d0]) continue;
-                if (!single) tables(ids.data() + d0, d1 - d0, bl, bm, st);
-                items.clear();
-                for (u64 d = d0; d < d1; d++)
-                    for (u64 q0 = start[d]; q0 < start[d + 1]; q0 += LF_ITEM)
-                        items.push_back(LiftItem{d - d0, q0, std::min<u64>(start[d + 1], q0 + LF_ITEM)});
-                litems_.ensure(sizeof(LiftItem) * items.size());
-                EDSX_HIP(hipMemcpyAsync(litems_.ptr, items.data(), sizeof(LiftItem) * items.size(), hipMemcpyHostToDevice, st));
-                EventPair ev;
-                EDSX_HIP(hipEventRecord(ev.a, st));
-                hipLaunchKernelGGL(k_lift_find, dim3((unsigned)std::min<u64>(items.size(), 1u << 20)), dim3(CP_THREADS), 0, st, tab(),
-                                   litems_.as<LiftItem>(), (u64)items.size(), lperm_.as<u32>(), lq_pos_.as<u64>(), lsite_.as<LiftSite>(),
-                                   lst_.as<uint8_t>());
-                EDSX_HIP(hipEventRecord(ev.b, st));
-                EDSX_HIP(hipStreamSynchronize(st));
-                EDSX_HIP(hipGetLastError());
-                timing_.copy_ms += ev.ms();
-            }
-        } else {
-            lq_aux_.ensure(8 * m);                               // the three columns as they are; packed on the device
-            EDSX_HIP(hipMemcpyAsync(lq_path_.ptr, site_in->symbol + c0, 8 * m, hipMemcpyHostToDevice, st));
-            EDSX_HIP(hipMemcpyAsync(lq_pos_.ptr, site_in->string + c0, 8 * m, hipMemcpyHostToDevice, st));
-            EDSX_HIP(hipMemcpyAsync(lq_aux_.ptr, site_in->offset + c0, 8 * m, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_lift_pack, dim3(grid_for(m, 8192)), dim3(256), 0, st, lq_path_.as<u64>(), lq_pos_.as<u64>(),
-                               lq_aux_.as<u64>(), m, lsite_.as<LiftSite>());
-            EDSX_HIP(hipMemsetAsync(lst_.ptr, 0, m, st));
-        }
-        if (put) {                                               // the sites stay where k_lift_find wrote them
-            EDSX_HIP(hipMemcpyAsync(lq_path_.ptr, dst_path + c0, 8 * m, hipMemcpyHostToDevice, st));
-            lift_group(m, D, start, st);
-            for (u64 d0 = 0; d0 < D; d0 += KT) {
-                const u64 d1 = std::min<u64>(D, d0 + KT);
-                if (start[d1] == start[d0]) continue;
-                if (!single) tables(ids.data() + d0, d1 - d0, bl, bm, st);
-                EventPair ev;
-                EDSX_HIP(hipEventRecord(ev.a, st));
-                hipLaunchKernelGGL(k_lift_place, dim3(grid_for(start[d1] - start[d0], 8192)), dim3(256), 0, st, tab(), lperm_.as<u32>(),
-                                   start[d0], start[d1], lq_path_.as<u64>(), lmap_.as<u32>(), d0, lsite_.as<LiftSite>(), lst_.as<uint8_t>(),
-                                   lq_pos_.as<u64>(), lst2_.as<uint8_t>());
-                EDSX_HIP(hipEventRecord(ev.b, st));
-                EDSX_HIP(hipStreamSynchronize(st));
-                EDSX_HIP(hipGetLastError());
-                timing_.copy_ms += ev.ms();
-            }
-        }
-        if (dev_site) {
-            EDSX_HIP(hipMemcpyAsync(dev_site + c0, lsite_.ptr, sizeof(LiftSite) * m, hipMemcpyDeviceToDevice, st));
-            EDSX_HIP(hipMemcpyAsync(dev_status + c0, lst_.ptr, m, hipMemcpyDeviceToDevice, st));
-            EDSX_HIP(hipStreamSynchronize(st));
-            continue;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        if (site_out) EDSX_HIP(hipMemcpyAsync(site_out + c0, lsite_.ptr, sizeof(LiftSite) * m, hipMemcpyDeviceToHost, st));
-        if (dst_pos) EDSX_HIP(hipMemcpyAsync(dst_pos + c0, lq_pos_.ptr, 8 * m, hipMemcpyDeviceToHost, st));
-        EDSX_HIP(hipMemcpyAsync(status + c0, put ? lst2_.ptr : lst_.ptr, m, hipMemcpyDeviceToHost, st));
-        EDSX_HIP(hipStreamSynchronize(st));
-        timing_.download_ms += since_ms(t0);
-        timing_.bytes_written += m * ((site_out ? sizeof(LiftSite) : 0) + (dst_pos ? 8 : 0) + 1);
-    }
+    emit_records(records::FASTA, n, hdr, line_width, 16, out, missing,
+        [&](size_t i0, u64 K, std::vector<u64>& len, std::vector<u64>& miss) {   // the chosen strings and the missing counts
+            tables(ids + i0, K, len, miss, st);
+            len.assign(K, W);
+        },
+        [&](const PathRec* rec, u64 nrec, u64 max_tiles, uint8_t* dst) {
+            const AlignArgs a{v.sym.ent_off, v.str_off, v.chars, align_.col.as<u64>(), rank_.as<u64>(), nc_ ? csid_.as<u64>() : nullptr, n_, nc_,
+                              rec, nrec, max_tiles, dst, gap};
+            hipLaunchKernelGGL(k_path_align, dim3(body_grid(nrec, max_tiles)), dim3(CP_THREADS), 0, st, a);
+        }, st);
 }
 
 void PathPipeline::walk_open(hipStream_t st)
 {
-    if (walk_ready_ || n_ == 0) return;
+    if (walk_.ready || n_ == 0) return;
     const EdsView v = eds_.view();
-    seg_rank_.ensure(8 * (v.m + 1));
-    cum_tok_.ensure(8 * (n_ + 1));
-    cnt_.ensure(8 * (n_ + 1));
+    walk_.seg_rank.ensure(8 * (v.m + 1));
+    walk_.cum_tok.ensure(8 * (n_ + 1));
+    walk_.cnt.ensure(8 * (n_ + 1));
     ctl_.ensure(8 * 8);
     scan_tmp_.ensure(8 * 2 * (v.m / SCAN_TILE + n_ / SCAN_TILE + 8));
     u64 h[6] = {v.m + 1, n_ + 1, 0, 0, 0, 0};
     u64* ctl = ctl_.as<u64>();
     EDSX_HIP(hipMemcpyAsync(ctl, h, sizeof(h), hipMemcpyHostToDevice, st));
-    segment_ranks(v, seg_rank_.as<u64>(), ctl, ctl + 2, scan_tmp_.as<u64>(), st);
-    u64 *ct = cum_tok_.as<u64>(), *cn = cnt_.as<u64>();
-    hipLaunchKernelGGL(k_path_tokfixed, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.ent_off, v.elen, seg_rank_.as<u64>(),
+    segment_ranks(v, walk_.seg_rank.as<u64>(), ctl, ctl + 2, scan_tmp_.as<u64>(), st);
+    u64 *ct = walk_.cum_tok.as<u64>(), *cn = walk_.cnt.as<u64>();
+    hipLaunchKernelGGL(k_path_tokfixed, dim3(grid_for(n_ + 1, 8192)), dim3(256), 0, st, v.sym.ent_off, v.elen, walk_.seg_rank.as<u64>(),
                        rank_.as<u64>(), n_, ct, cn);
     ScanSet<2> ss{{ct, cn}, {ct, cn}, {ctl + 3, ctl + 4}};
     exclusive_scan_multi<2>(ss, ctl + 1, scan_tmp_.as<u64>(), st);
     EDSX_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    Ftok_ = h[3]; Fcnt_ = h[4];
-    walk_ready_ = true;
+    walk_.Ftok = h[3]; walk_.Fcnt = h[4];
+    walk_.ready = true;
 }
 
 void PathPipeline::walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std::vector<u64>& miss, std::vector<u64>& cnt, hipStream_t st)
@@ -1168,121 +823,54 @@ void PathPipeline::walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std
     tables(ids, K, len, miss, st);                               // csid_, the missing counts (and the lengths, not used here)
     tok.assign(K, 0); cnt.assign(K, 0);
     const u64 cells = K * nc_;
-    cnt_.ensure(8 * std::max<u64>(K, n_ + 1));
-    u64* cn = cnt_.as<u64>();
+    walk_.cnt.ensure(8 * std::max<u64>(K, n_ + 1));
+    u64* cn = walk_.cnt.as<u64>();
     EDSX_HIP(hipMemsetAsync(cn, 0, 8 * K, st));
-    EventPair es;
+    TimedRuns timed(st, nullptr);
     if (nc_) {
-        tlen_.ensure(8 * (cells + 1));
+        walk_.tlen.ensure(8 * (cells + 1));
+        u64* tlen = walk_.tlen.as<u64>();
         EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &cells, 8, hipMemcpyHostToDevice, st));
         const EdsView v = eds_.view();
-        EDSX_HIP(hipEventRecord(es.a, st));
-        hipLaunchKernelGGL(k_path_tok, dim3(grid_for(cells, 8192)), dim3(256), 0, st, csid_.as<u64>(), nc_, K, v.elen, seg_rank_.as<u64>(),
-                           tlen_.as<u64>(), cn);
-        exclusive_scan_u64(tlen_.as<u64>(), tlen_.as<u64>(), ctl_.as<u64>(), tlen_.as<u64>() + cells, scan_tmp_.as<u64>(), st);
-        EDSX_HIP(hipEventRecord(es.b, st));
+        timed.run("k_path_tok", [&] {
+            hipLaunchKernelGGL(k_path_tok, dim3(grid_for(cells, 8192)), dim3(256), 0, st, csid_.as<u64>(), nc_, K, v.elen,
+                               walk_.seg_rank.as<u64>(), tlen, cn);
+            exclusive_scan_u64(tlen, tlen, ctl_.as<u64>(), tlen + cells, scan_tmp_.as<u64>(), st);
+        }, &timing_.scan_ms);
     }
-    hipLaunchKernelGGL(k_path_toktotals, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, tlen_.as<u64>(), nc_, Ftok_, K, tot_.as<u64>());
+    hipLaunchKernelGGL(k_path_toktotals, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, walk_.tlen.as<u64>(), nc_, walk_.Ftok, K, tot_.as<u64>());
     EDSX_HIP(hipMemcpyAsync(tok.data(), tot_.ptr, 8 * K, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipMemcpyAsync(cnt.data(), cn, 8 * K, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    for (u64 k = 0; k < K; k++) cnt[k] += Fcnt_;
-    if (nc_) timing_.scan_ms += es.ms();
+    timed.harvest();
+    for (u64 k = 0; k < K; k++) cnt[k] += walk_.Fcnt;
 }
 
 void PathPipeline::walks(const u64* ids, size_t n, const char* const* names, const char* prefix, HostBytes& out, u64* missing,
                          u64* steps, hipStream_t st)
 {
     check_ids(ids, n);
-    const double tk = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tk;
+    begin_call();
     out.take(0);
     if (n == 0) return;
-    // the texts in front of the walks: "P\t<name>\t"
-    std::string blob;
-    std::vector<u64> hoff(n + 1, 0);
-    const std::string pre = prefix ? prefix : "path";
-    for (size_t k = 0; k < n; k++) {
-        const std::string name = names ? std::string(names[k]) : pre + std::to_string(ids[k]);
-        if (name.empty() || name.find_first_of("\t\n ") != std::string::npos)
-            throw ParamError("Path name " + std::to_string(k) + " is not a GFA name");
-        blob += "P\t" + name + "\t";
-        hoff[k + 1] = blob.size();
-    }
+    size_t bad = n;
+    const records::Headers hdr = records::walk_headers(ids, n, names, prefix, bad);   // the texts in front of the walks: "P\t<name>\t"
+    if (bad < n) throw ParamError("Path name " + std::to_string(bad) + " is not a GFA name");
     walk_open(st);
-    const u64 KT = table_batch(n, 24);
-    const bool single = KT >= n;
-    std::vector<u64> tok(n), miss(n), cnt(n), bt, bm, bc;
-    for (size_t i0 = 0; i0 < n; i0 += KT) {
-        const u64 K = std::min<u64>(KT, n - i0);
-        walk_tables(ids + i0, K, bt, bm, bc, st);
-        std::memcpy(tok.data() + i0, bt.data(), 8 * K);
-        std::memcpy(miss.data() + i0, bm.data(), 8 * K);
-        std::memcpy(cnt.data() + i0, bc.data(), 8 * K);
-    }
-    if (missing) std::memcpy(missing, miss.data(), 8 * n);
-    if (steps) std::memcpy(steps, cnt.data(), 8 * n);
-    std::vector<PathRec> rec(n);
-    std::vector<u64> host_off(n + 1, 0);                        // line starts in the caller's buffer; a path without a step has none
-    for (size_t k = 0; k < n; k++) {
-        PathRec& r = rec[k];
-        r.L = tok[k]; r.lw = 0;
-        r.body = r.L ? r.L + 2 : 0;
-        r.hdr_src = hoff[k];
-        r.row = k % KT;
-        host_off[k + 1] = host_off[k] + (r.L ? (hoff[k + 1] - hoff[k]) + r.body : 0);
-    }
-    const u64 total = host_off[n];
-    out.take(total);
-    timing_.bytes_written = total;
-    if (total == 0) return;
-    hdr_.ensure(blob.size());
-    EDSX_HIP(hipMemcpyAsync(hdr_.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const u64 ov = budget_override(), out_budget = ov ? ov : free_hbm() / 2;
-    std::vector<PathRec> batch;
-    for (size_t i0 = 0; i0 < n; i0 += KT) {
-        const size_t i1 = std::min<size_t>(n, i0 + KT);
-        if (!single) walk_tables(ids + i0, i1 - i0, bt, bm, bc, st);
-        for (size_t r0 = i0; r0 < i1;) {                         // output batches: as many lines as the budget holds
-            size_t r1 = r0 + 1;
-            while (r1 < i1 && host_off[r1 + 1] - host_off[r0] <= out_budget) r1++;
-            const u64 bytes = host_off[r1] - host_off[r0];
-            batch.clear();
-            u64 max_body = 0;
-            for (size_t k = r0; k < r1; k++) {
-                if (!rec[k].L) continue;
-                rec[k].rec_off = host_off[k] - host_off[r0];
-                rec[k].body_off = rec[k].rec_off + (hoff[k + 1] - hoff[k]);
-                max_body = std::max(max_body, rec[k].body);
-                batch.push_back(rec[k]);
-            }
-            if (!batch.empty()) {
-                const u64 nrec = batch.size();
-                out_.ensure(bytes + 16);                         // 16 bytes of slack behind the text, as every output buffer here
-                rec_.ensure(sizeof(PathRec) * nrec);
-                EDSX_HIP(hipMemcpyAsync(rec_.ptr, batch.data(), sizeof(PathRec) * nrec, hipMemcpyHostToDevice, st));
-                const EdsView v = eds_.view();
-                WalkArgs a{gfa::WalkTab{v.sym.ent_off, seg_rank_.as<u64>(), cum_tok_.as<u64>(), rank_.as<u64>(),
-                                        nc_ ? csid_.as<u64>() : nullptr, nc_ ? tlen_.as<u64>() : nullptr, n_, nc_},
-                           rec_.as<PathRec>(), nrec, (max_body + CP_TILE - 1) / CP_TILE, out_.as<uint8_t>()};
-                EventPair ev;
-                EDSX_HIP(hipEventRecord(ev.a, st));
-                hipLaunchKernelGGL(k_path_headers, dim3((unsigned)nrec), dim3(64), 0, st, hdr_.as<uint8_t>(), rec_.as<PathRec>(), a.out);
-                const u64 work = a.max_tiles * nrec;
-                hipLaunchKernelGGL(k_path_walk, dim3((unsigned)std::min<u64>(work, 1u << 20)), dim3(CP_THREADS), 0, st, a);
-                EDSX_HIP(hipEventRecord(ev.b, st));
-                EDSX_HIP(hipStreamSynchronize(st));
-                EDSX_HIP(hipGetLastError());
-                timing_.copy_ms += ev.ms();
-                const auto t0 = std::chrono::steady_clock::now();
-                PinnedDownload::copy(out.data + host_off[r0], out_.ptr, bytes, st);
-                timing_.download_ms += since_ms(t0);
-            }
-            r0 = r1;
-        }
-    }
+    const EdsView v = eds_.view();
+    std::vector<u64> cnt;
+    emit_records(records::WALK, n, hdr, 0, 24, out, missing,
+        [&](size_t i0, u64 K, std::vector<u64>& tok, std::vector<u64>& miss) {
+            walk_tables(ids + i0, K, tok, miss, cnt, st);
+            if (steps) std::memcpy(steps + i0, cnt.data(), 8 * K);
+        },
+        [&](const PathRec* rec, u64 nrec, u64 max_tiles, uint8_t* dst) {
+            const WalkArgs a{gfa::WalkTab{v.sym.ent_off, walk_.seg_rank.as<u64>(), walk_.cum_tok.as<u64>(), rank_.as<u64>(),
+                                          nc_ ? csid_.as<u64>() : nullptr, nc_ ? walk_.tlen.as<u64>() : nullptr, n_, nc_},
+                             rec, nrec, max_tiles, dst};
+            hipLaunchKernelGGL(k_path_walk, dim3(body_grid(nrec, max_tiles)), dim3(CP_THREADS), 0, st, a);
+        }, st);
 }
 
 } // namespace edsx

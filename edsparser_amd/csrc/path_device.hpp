@@ -1,11 +1,12 @@
 // path_device.hpp — host driver of the path spelling kernels (see path_device.hip): the sequence of every path of an
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
+// The session's coordinate lift and region slice: lift_device.hip, slice_device.hip (where an operation goes).
 #pragma once
 
 #include "eds_device.hpp"
-#include "gfa_device.hpp"
+#include "kernel_times.hpp"
 #include "lift_core.hpp"
-#include "slice_core.hpp"
+#include "path_records.hpp"
 
 #include <vector>
 
@@ -25,11 +26,6 @@ struct PathTiming {
     u64 bytes_written = 0;
 };
 
-// one requested path of an output batch: where its record and its body start in the batch's buffer, where its header
-// text lies in the header blob, its length, the line width in force (>= 1), the body bytes (characters + newlines) and
-// its row of the choice tables
-struct PathRec { u64 rec_off, body_off, hdr_src, L, lw, body, row; };
-
 // the column layout of the session's alignment view (align): W = n_columns
 struct AlignInfo { u64 n_symbols = 0, n_columns = 0, n_zero_width_symbols = 0, widest_symbol = 0, num_paths = 0; };
 
@@ -39,19 +35,6 @@ struct LiftColumns { const u64* symbol; const u64* string; const u64* offset; };
 
 // edsx_slice_region (include/edsx.h)
 struct SliceRegion { u64 symbol_first, symbol_last, cut_first, cut_end, column_first, column_end, strings, chars, eds_off, eds_len, seds_off, seds_len; };
-
-// device time per kernel, accumulated while on (edsx_set_timing / edsx_get_timing), as SubsetPipeline keeps it
-class KernelTimes {
-public:
-    void set(bool on) { on_ = on; acc_.clear(); }
-    bool on() const { return on_; }
-    void add(const char* name, float ms);
-    int get(const char** names, float* ms, int* counts, int cap) const;
-private:
-    struct Acc { const char* name; float total_ms; int count; };
-    bool on_ = false;
-    std::vector<Acc> acc_;
-};
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -78,7 +61,7 @@ public:
     // holds the chosen string of the path left-justified and filled up with `gap`; every row has W = sum w[i] characters,
     // whatever paths are asked for.  FASTA as spell() writes it.  max_bytes (0: none): ParamError, from the counts and
     // before any table or text is made, when the text is larger.
-    const AlignInfo& align_info(hipStream_t st) { align_open(st); return ainfo_; }
+    const AlignInfo& align_info(hipStream_t st) { align_open(st); return align_.info; }
     void align(const u64* ids, size_t n, const char* const* names, const char* prefix, u64 line_width, uint8_t gap, u64 max_bytes,
                HostBytes& out, u64* missing, hipStream_t st);
 
@@ -98,42 +81,56 @@ public:
                SliceRegion* region, uint8_t* status, KernelTimes* times, hipStream_t st);
 
 private:
+    // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
+    // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
+    // the number of such symbols; per table batch the token bytes of the choice cells, scanned (tlen), and the steps per row
+    struct WalkState { bool ready = false; u64 Ftok = 0, Fcnt = 0; DevBuf seg_rank, cum_tok, tlen, cnt; };
+    // align: col, the exclusive scan of the symbol widths (n + 1 entries)
+    struct AlignState { bool ready = false; AlignInfo info; DevBuf col; };
+    // lift: cum_common next to col (n + 1); the row of every path of the call (map), the queries of a chunk (q_*), grouped
+    // by row (cnt, cur, perm, items), their sites and the statuses of both steps
+    struct LiftState { bool ready = false; DevBuf cum_common, map, cnt, cur, q_path, q_pos, q_aux, perm, site, st, st2, items; };
+    // slice: the scanned .seds bytes per string (sb, m + 1) and the symbol of every string (symof, m); per call the regions
+    // as given (in), the sites of their ends, the regions resolved (reg, st), A per region (sum), the five scanned counts
+    // (scan), the destinations of the edge strings (edst) and both texts
+    struct SliceState { bool ready = false; DevBuf sb, symof, in, site, sst, reg, st, sum, scan, edst, eds, seds; };
+
+    // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
+    void begin_call();                                            // a fresh PathTiming that keeps tokenise_ms
     u64 table_batch(size_t n, u64 cell_bytes = 16) const;
-    // seg_rank and the token bytes of the fixed symbols: made by the first walks() of a session, kept until it closes
+    static u64 budget(u64 part);                                  // bytes a batch may take: 1 / part of the free HBM
+    // choose + scan for ids[0..K): device tables for the copy kernel, host lengths and missing counts
+    void tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st);
+    // The records of spell / align / walks (path_records.hpp) into `out`, batch by batch within the budgets.
+    //   make_tables(i0, K, len, miss)             the tables of ids [i0, i0 + K) and the lengths that size their records
+    //   launch_body(rec, nrec, max_tiles, dst)    the body kernel over the nrec records of an output batch
+    template <class Tables, class Body>
+    void emit_records(records::Rule rule, size_t n, const records::Headers& hdr, u64 line_width, u64 cell_bytes, HostBytes& out,
+                      u64* missing, Tables&& make_tables, Body&& launch_body, hipStream_t st);
+    // ---- walks: made by the first walks() of a session
     void walk_open(hipStream_t st);
     // tables(), then the token bytes of every (path, choice symbol) and their scan; tok / cnt: token bytes and ids per path
     void walk_tables(const u64* ids, u64 K, std::vector<u64>& tok, std::vector<u64>& miss, std::vector<u64>& cnt, hipStream_t st);
-    // col (the exclusive scan of the symbol widths, n + 1 entries): made by the first align() or align_info() of a
-    // session, kept until it closes
+    // ---- align: made by the first align() or align_info() of a session
     void align_open(hipStream_t st);
-    static u64 budget_override();
-    // choose + scan for ids[0..K): device tables for the copy kernel, host lengths and missing counts
-    void tables(const u64* ids, u64 K, std::vector<u64>& len, std::vector<u64>& miss, hipStream_t st);
+    // ---- lift (lift_device.hip): made by the first lift() of a session
+    void lift_open(hipStream_t st);
+    void lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t st);
+    void lift_run(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path, LiftSite* site_out,
+                  u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st);
+    // ---- slice (slice_device.hip): made by the first slice() of a session
+    void slice_open(hipStream_t st);
 
     DeviceEds eds_;
     PathInfo info_;
     PathTiming timing_;
     u64 n_ = 0, nc_ = 0, F_ = 0;
-    DevBuf cum_fixed_, rank_, cidx_, ctl_, scan_tmp_, ids_, csid_, clen_, tot_, miss_, rec_, hdr_, hoff_, out_;
-    bool walk_ready_ = false;
-    u64 Ftok_ = 0, Fcnt_ = 0;                                    // token bytes / ids of the fixed symbols
-    DevBuf seg_rank_, cum_tok_, tlen_, cnt_;
-    bool align_ready_ = false;
-    AlignInfo ainfo_;
-    DevBuf col_;
-    // cum_common (n + 1 entries) next to col: made by the first lift() of a session, kept until it closes
-    void lift_open(hipStream_t st);
-    void lift_group(u64 m, u64 D, std::vector<u64>& start, hipStream_t st);
-    void lift_run(size_t n, const u64* src_path, const u64* src_pos, const LiftColumns* site_in, const u64* dst_path, LiftSite* site_out,
-                  u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st);
-    bool lift_ready_ = false;
-    DevBuf cum_common_, lmap_, lcnt_, lcur_, lq_path_, lq_pos_, lq_aux_, lperm_, lsite_, lst_, lst2_, litems_;
-    // the scanned .seds bytes per string (m + 1 entries) and the symbol of every string (m): made by the first slice() of a
-    // session, kept until it closes
-    void slice_open(hipStream_t st);
-    bool slice_ready_ = false;
-    DevBuf sb_, symof_, s_in_, s_site_, s_sst_, s_reg_, s_st_, s_sum_, s_scan_, s_edst_, s_eds_, s_seds_;
+    DevBuf cum_fixed_, rank_, cidx_, ctl_, scan_tmp_, ids_, csid_, clen_, tot_, miss_, rec_, hdr_, out_;
+    WalkState walk_;
+    AlignState align_;
+    LiftState lift_;
+    SliceState slice_;
 };
 
 } // namespace edsx

@@ -11,6 +11,7 @@
 // The draws are edsx::pattern_draw (draw.hpp), shared with EDS::generate_patterns(os, count, length, seed): for the same
 // seed both write the same bytes.
 #include "query_device.hpp"
+#include "kernel_times.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -209,18 +210,18 @@ u64 QueryPipeline::tables(DeviceEds& de, const uint8_t* eds, size_t eds_n, const
     u64 hn = n_;
     EDSX_HIP(hipMemcpyAsync(ctl_.ptr, &hn, 8, hipMemcpyHostToDevice, st));
     u64 *cc = cum_common_.as<u64>(), *cd = cum_deg_.as<u64>();
-    EventPair ev;
-    EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_q_flags, dim3(grid_for(n_, 4096)), dim3(256), 0, st, v.sym.size, v.sym.len1, n_, cc, cd);
-    ScanSet<2> ss{{cc, cd}, {cc, cd}, {cc + n_, cd + n_}};
-    exclusive_scan_multi<2>(ss, ctl_.as<u64>(), scan_tmp_.as<u64>(), st);
-    EDSX_HIP(hipEventRecord(ev.b, st));
+    TimedRuns timed(st, nullptr);
+    timed.run("tables", [&] {
+        hipLaunchKernelGGL(k_q_flags, dim3(grid_for(n_, 4096)), dim3(256), 0, st, v.sym.size, v.sym.len1, n_, cc, cd);
+        ScanSet<2> ss{{cc, cd}, {cc, cd}, {cc + n_, cd + n_}};
+        exclusive_scan_multi<2>(ss, ctl_.as<u64>(), scan_tmp_.as<u64>(), st);
+    }, &info_.tables_ms);
     u64 h[2] = {0, 0};
     EDSX_HIP(hipMemcpyAsync(&h[0], cc + n_, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipMemcpyAsync(&h[1], cd + n_, 8, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    info_.tables_ms = ev.ms();
+    timed.harvest();
     C_ = h[0]; D_ = h[1];
     info_.num_common_chars = C_; info_.num_degenerate_strings = D_;
     return n_;
@@ -249,21 +250,19 @@ void QueryPipeline::genpatterns(DeviceEds& de, const uint8_t* eds, size_t eds_n,
     const EdsView v = de.view();
     SampleArgs a{v.sym.size, v.sym.ent_off, v.str_off, v.chars, cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, seed, 0, 0, pattern_length, out_.as<uint8_t>(),
                  witness ? wpos_.as<u64>() : nullptr, witness ? wcnt_.as<u64>() : nullptr, woff_.as<u64>(), nullptr, ctl};
-    EventPair ev;
+    TimedRuns timed(st, nullptr);
     std::vector<u64> hoff;
     for (u64 i0 = 0; i0 < count; i0 += chunk) {
         const u64 cnt = std::min(chunk, count - i0);
         a.i0 = i0; a.cnt = cnt;
         u64 hctl[2] = {NONE, cnt};
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
-        EDSX_HIP(hipEventRecord(ev.a, st));
-        hipLaunchKernelGGL(k_pat_sample<false>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a);
-        EDSX_HIP(hipEventRecord(ev.b, st));
+        timed.run("sample", [&] { hipLaunchKernelGGL(k_pat_sample<false>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a); }, &info_.kernel_ms);
         u64 err = NONE, total = 0;
         EDSX_HIP(hipMemcpyAsync(&err, ctl, 8, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
-        info_.kernel_ms += ev.ms();
+        timed.harvest();
         if (err != NONE) {
             const u64 t = err >> 40, w = err & ((1ull << 40) - 1);
             throw ParamError("Cannot generate pattern " + std::to_string(i0 + t) + ": the wrap-around reaches symbol " +
@@ -275,12 +274,10 @@ void QueryPipeline::genpatterns(DeviceEds& de, const uint8_t* eds, size_t eds_n,
             EDSX_HIP(hipStreamSynchronize(st));
             wdeg_.ensure(4 * std::max<u64>(total, 1));
             a.wdeg = wdeg_.as<int32_t>();
-            EDSX_HIP(hipEventRecord(ev.a, st));
-            hipLaunchKernelGGL(k_pat_sample<true>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a);
-            EDSX_HIP(hipEventRecord(ev.b, st));
+            timed.run("witness", [&] { hipLaunchKernelGGL(k_pat_sample<true>, dim3(grid_for(cnt, 4096)), dim3(256), 0, st, a); }, &info_.kernel_ms);
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
-            info_.kernel_ms += ev.ms();
+            timed.harvest();
         }
         const auto t0 = std::chrono::steady_clock::now();
         PinnedDownload::copy(out.data + i0 * rec, out_.ptr, cnt * rec, st);
@@ -318,14 +315,12 @@ void QueryPipeline::check(DeviceEds& de, const uint8_t* eds, size_t eds_n, const
     CheckArgs a{v.sym.size, v.sym.ent_off, v.str_off, v.chars, v.bits, v.W, cum_common_.as<u64>(), cum_deg_.as<u64>(), n, C_, D_,
                 nq, q_pos_.as<u64>(), q_coff_.as<u64>(), q_ch_.as<int32_t>(), nch, q_poff_.as<u64>(), q_pat_.as<uint8_t>(), npat,
                 q_status_.as<int8_t>()};
-    EventPair ev;
-    EDSX_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_pat_check, dim3(grid_for(nq, 4096)), dim3(256), 0, st, a);
-    EDSX_HIP(hipEventRecord(ev.b, st));
+    TimedRuns timed(st, nullptr);
+    timed.run("k_pat_check", [&] { hipLaunchKernelGGL(k_pat_check, dim3(grid_for(nq, 4096)), dim3(256), 0, st, a); }, &info_.kernel_ms);
     EDSX_HIP(hipMemcpyAsync(status, q_status_.ptr, nq, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    info_.kernel_ms = ev.ms();
+    timed.harvest();
 }
 
 } // namespace edsx

@@ -25,11 +25,11 @@
 //                                     tile's first and last, and when all 16 are kept characters of one string moves them
 //                                     with one aligned 16-byte load and one 16-byte store; the rest goes byte by byte
 #include "path_device.hpp"
+#include "slice_core.hpp"
 #include "subset_device.hpp"
 
 #include <algorithm>
 #include <chrono>
-#include <deque>
 #include <string>
 #include <vector>
 
@@ -42,21 +42,8 @@ constexpr int ST = 256;                    // threads per block
 constexpr u32 WAVES = ST / 64;             // a work item of the fill kernels is a wave's: small regions fill a workgroup four at a time
 constexpr u32 PL_TILE = 64;                // strings per place / seds tile
 constexpr u32 CP_TILE = 64 * 16;           // source characters per copy tile
-// scanned per region (R + 1 entries each, one behind the other in s_scan_): bytes of both texts, edge strings, tiles
+// scanned per region (R + 1 entries each, one behind the other in slice_.scan): bytes of both texts, edge strings, tiles
 enum { SC_EDS, SC_SEDS, SC_EDGE, SC_PTILE, SC_CTILE, SC_COUNT };
-
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the last k in [lo, hi] with a[k] <= x, given a[lo] <= x
-__device__ __forceinline__ u64 last_le(const u64* __restrict__ a, u64 lo, u64 hi, u64 x)
-{
-    while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (a[mid] <= x) lo = mid; else hi = mid - 1; }
-    return lo;
-}
 
 __device__ __forceinline__ slice::Ends ends_of(const SliceRegion& r)
 {
@@ -214,6 +201,13 @@ __global__ void __launch_bounds__(ST) k_slice_place(FillArgs a)
     }
 }
 
+// write_set_ids over the set as it is, without its bit 0
+struct OwnIds {
+    __device__ __forceinline__ u64 mask(u32 w) const { return w == 0 ? ~1ull : ~0ull; }
+    __device__ __forceinline__ u64 bytes(u32 w, u64 x) const { return slice::word_bytes(w, x); }
+    __device__ __forceinline__ u32 id(u32 w, u32 b) const { return 64u * w + b; }
+};
+
 __global__ void __launch_bounds__(ST) k_slice_seds(FillArgs a)
 {
     const u32 G = a.G, W = a.W, lane = threadIdx.x & 63, g = lane & (G - 1), per_pass = 64 / G;
@@ -236,28 +230,7 @@ __global__ void __launch_bounds__(ST) k_slice_seds(FillArgs a)
                 if (univ) a.sout[p0 + 1] = '0';
                 if (j + 1 == e1) a.sout[end] = '\n';
             }
-            u64 cur = p0 + 1;
-            for (u32 wb = 0; wb < W; wb += G) {
-                const u32 w = wb + g;
-                u64 x = (act && !univ && w < W) ? a.bits[j * W + w] : 0;
-                if (w == 0) x &= ~1ull;
-                const u64 nb = slice::word_bytes(w, x);
-                u64 incl = nb;
-                for (u32 o = 1; o < G; o <<= 1) { const u64 y = __shfl_up(incl, o, 64); if (g >= o) incl += y; }
-                const u64 total = __shfl(incl, (int)(lane | (G - 1)), 64);
-                u64 p = cur + incl - nb;
-                while (x) {
-                    const u32 b = (u32)__builtin_ctzll(x);
-                    x &= x - 1;
-                    u32 v = 64u * w + b;
-                    const u32 dg = ndigits(v);
-                    for (u32 k = dg; k-- > 0;) { a.sout[p + k] = (uint8_t)('0' + v % 10u); v /= 10u; }
-                    p += dg;
-                    a.sout[p] = p + 1 == end ? '}' : ',';
-                    p++;
-                }
-                cur += total;
-            }
+            write_set_ids(OwnIds{}, a.bits + j * W, act && !univ, W, G, g, p0 + 1, end, a.sout);
         }
     }
 }
@@ -310,41 +283,25 @@ __global__ void __launch_bounds__(ST) k_slice_copy(FillArgs a)
 
 } // namespace
 
-void KernelTimes::add(const char* name, float ms)
-{
-    for (auto& a : acc_) if (std::string(a.name) == name) { a.total_ms += ms; a.count++; return; }
-    acc_.push_back({name, ms, 1});
-}
-
-int KernelTimes::get(const char** names, float* ms, int* counts, int cap) const
-{
-    int n = 0;
-    for (const auto& a : acc_) {
-        if (n >= cap) break;
-        names[n] = a.name; ms[n] = a.total_ms; counts[n] = a.count; n++;
-    }
-    return n;
-}
-
 void PathPipeline::slice_open(hipStream_t st)
 {
     lift_open(st);                                               // col
-    if (slice_ready_ || n_ == 0) return;
+    if (slice_.ready || n_ == 0) return;
     const EdsView v = eds_.view();
-    sb_.ensure(8 * (v.m + 1));
-    symof_.ensure(8 * v.m);
+    slice_.sb.ensure(8 * (v.m + 1));
+    slice_.symof.ensure(8 * v.m);
     ctl_.ensure(8 * 8);
     scan_tmp_.ensure(8 * (v.m / SCAN_TILE + 4));
     const u64 cnt = v.m + 1;
     u64* ctl = ctl_.as<u64>();
     EDSX_HIP(hipMemcpyAsync(ctl, &cnt, 8, hipMemcpyHostToDevice, st));
     const u32 G = SubsetPipeline::group_for(v.W);
-    hipLaunchKernelGGL(k_slice_setbytes, dim3(grid_for((v.m + 1) * G, 16384)), dim3(ST), 0, st, v.bits, v.W, G, v.m, sb_.as<u64>());
-    exclusive_scan_u64(sb_.as<u64>(), sb_.as<u64>(), ctl, ctl + 1, scan_tmp_.as<u64>(), st);
-    hipLaunchKernelGGL(k_slice_symof, dim3(grid_for(v.m, 8192)), dim3(ST), 0, st, v.sym.ent_off, n_, v.m, symof_.as<u64>());
+    hipLaunchKernelGGL(k_slice_setbytes, dim3(grid_for((v.m + 1) * G, 16384)), dim3(ST), 0, st, v.bits, v.W, G, v.m, slice_.sb.as<u64>());
+    exclusive_scan_u64(slice_.sb.as<u64>(), slice_.sb.as<u64>(), ctl, ctl + 1, scan_tmp_.as<u64>(), st);
+    hipLaunchKernelGGL(k_slice_symof, dim3(grid_for(v.m, 8192)), dim3(ST), 0, st, v.sym.ent_off, n_, v.m, slice_.symof.as<u64>());
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    slice_ready_ = true;
+    slice_.ready = true;
 }
 
 void PathPipeline::slice(size_t n, const u64* path, const u64* start, const u64* end, u64 max_bytes, HostBytes& eds_out,
@@ -359,9 +316,7 @@ void PathPipeline::slice(size_t n, const u64* path, const u64* start, const u64*
         qpos.push_back(start[r]); qpos.push_back(end[r] - 1);
     }
     check_ids(qpath.data(), qpath.size());
-    const double tok = timing_.tokenise_ms;
-    timing_ = PathTiming{};
-    timing_.tokenise_ms = tok;
+    begin_call();
     eds_out.take(0); seds_out.take(0);
     if (n == 0) return;
     if (n_ == 0) {                                               // an empty EDS has no paths and no columns
@@ -373,80 +328,69 @@ void PathPipeline::slice(size_t n, const u64* path, const u64* start, const u64*
     }
     slice_open(st);
     const u64 R = n, Q = qpath.size();
-    s_site_.ensure(sizeof(LiftSite) * std::max<u64>(Q, 1)); s_sst_.ensure(std::max<u64>(Q, 1));
+    slice_.site.ensure(sizeof(LiftSite) * std::max<u64>(Q, 1)); slice_.sst.ensure(std::max<u64>(Q, 1));
     if (Q) {
-        lift_run(Q, qpath.data(), qpos.data(), nullptr, nullptr, nullptr, nullptr, nullptr, s_site_.as<LiftSite>(), s_sst_.as<uint8_t>(), st);
+        lift_run(Q, qpath.data(), qpos.data(), nullptr, nullptr, nullptr, nullptr, nullptr, slice_.site.as<LiftSite>(), slice_.sst.as<uint8_t>(), st);
         timing_.scan_ms += timing_.copy_ms;                      // the site search is part of the resolve step
         timing_.copy_ms = 0;
     }
-    struct Timed { const char* name; double* bucket; EventPair ev; Timed(const char* n, double* b) : name(n), bucket(b) {} };
-    std::deque<Timed> timed;
-    auto run = [&](const char* name, double* bucket, auto&& launch) {
-        timed.emplace_back(name, bucket);
-        EDSX_HIP(hipEventRecord(timed.back().ev.a, st));
-        launch();
-        EDSX_HIP(hipEventRecord(timed.back().ev.b, st));
-    };
-    auto harvest = [&] {                                         // after a stream synchronisation
-        for (auto& t : timed) { const float ms = t.ev.ms(); *t.bucket += ms; if (times && times->on()) times->add(t.name, ms); }
-        timed.clear();
-    };
+    TimedRuns timed(st, times);                                  // every run with a bucket: PathTiming is filled whether timing is on or not
 
     const EdsView v = eds_.view();
-    const slice::SliceTab tab{v.sym.size, v.sym.ent_off, v.str_off, sb_.as<u64>(), col_.as<u64>(), n_, v.m};
-    s_in_.ensure(8 * 4 * R); s_reg_.ensure(sizeof(SliceRegion) * R); s_st_.ensure(R); s_sum_.ensure(8 * R);
-    s_scan_.ensure(8 * SC_COUNT * (R + 1));
+    const slice::SliceTab tab{v.sym.size, v.sym.ent_off, v.str_off, slice_.sb.as<u64>(), align_.col.as<u64>(), n_, v.m};
+    slice_.in.ensure(8 * 4 * R); slice_.reg.ensure(sizeof(SliceRegion) * R); slice_.st.ensure(R); slice_.sum.ensure(8 * R);
+    slice_.scan.ensure(8 * SC_COUNT * (R + 1));
     ctl_.ensure(8 * 8);
     scan_tmp_.ensure(8 * SC_COUNT * ((R + 1) / SCAN_TILE + 4));
-    u64 *in = s_in_.as<u64>(), *sc = s_scan_.as<u64>(), *ctl = ctl_.as<u64>();
+    u64 *in = slice_.in.as<u64>(), *sc = slice_.scan.as<u64>(), *ctl = ctl_.as<u64>();
     const u64* cols[4] = {path, start, end, qidx.data()};
     for (int k = 0; k < 4; k++) EDSX_HIP(hipMemcpyAsync(in + k * R, cols[k], 8 * R, hipMemcpyHostToDevice, st));
     u64 hctl[1 + SC_COUNT] = {R + 1, 0, 0, 0, 0, 0};
     EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
-    SliceRegion* reg = s_reg_.as<SliceRegion>();
-    const EndsArgs ea{tab, in, in + R, in + 2 * R, in + 3 * R, s_site_.as<LiftSite>(), s_sst_.as<uint8_t>(), R, reg, s_st_.as<uint8_t>()};
-    run("k_slice_ends", &timing_.scan_ms, [&] { hipLaunchKernelGGL(k_slice_ends, dim3(grid_for(R, 8192)), dim3(ST), 0, st, ea); });
-    run("k_slice_count", &timing_.scan_ms, [&] {
-        hipLaunchKernelGGL(k_slice_count, dim3(grid_for((R + 1) * 64, 65536)), dim3(ST), 0, st, tab, R, reg, s_sum_.as<u64>(), sc);
-    });
-    run("scan_regions", &timing_.scan_ms, [&] {
+    SliceRegion* reg = slice_.reg.as<SliceRegion>();
+    const EndsArgs ea{tab, in, in + R, in + 2 * R, in + 3 * R, slice_.site.as<LiftSite>(), slice_.sst.as<uint8_t>(), R, reg, slice_.st.as<uint8_t>()};
+    timed.run("k_slice_ends", [&] { hipLaunchKernelGGL(k_slice_ends, dim3(grid_for(R, 8192)), dim3(ST), 0, st, ea); }, &timing_.scan_ms);
+    timed.run("k_slice_count", [&] {
+        hipLaunchKernelGGL(k_slice_count, dim3(grid_for((R + 1) * 64, 65536)), dim3(ST), 0, st, tab, R, reg, slice_.sum.as<u64>(), sc);
+    }, &timing_.scan_ms);
+    timed.run("scan_regions", [&] {
         ScanSet<SC_COUNT> ss;
         for (int k = 0; k < SC_COUNT; k++) { ss.in[k] = ss.out[k] = sc + (u64)k * (R + 1); ss.total[k] = ctl + 1 + k; }
         exclusive_scan_multi<SC_COUNT>(ss, ctl, scan_tmp_.as<u64>(), st);
-    });
-    run("k_slice_offsets", &timing_.scan_ms, [&] { hipLaunchKernelGGL(k_slice_offsets, dim3(grid_for(R, 8192)), dim3(ST), 0, st, R, sc, reg); });
+    }, &timing_.scan_ms);
+    timed.run("k_slice_offsets", [&] { hipLaunchKernelGGL(k_slice_offsets, dim3(grid_for(R, 8192)), dim3(ST), 0, st, R, sc, reg); }, &timing_.scan_ms);
     EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    harvest();
+    timed.harvest();
     const u64 E = hctl[1 + SC_EDS], S = hctl[1 + SC_SEDS], X = hctl[1 + SC_EDGE], PT = hctl[1 + SC_PTILE], CT = hctl[1 + SC_CTILE];
     if (max_bytes && E + S > max_bytes)
         throw ParamError("Slices have " + std::to_string(E + S) + " bytes, above the limit of " + std::to_string(max_bytes));
 
     // ---- fill: both buffers are sized exactly (+ 16 bytes of slack as every output buffer here)
-    s_eds_.ensure(E + 16); s_seds_.ensure(S + 16); s_edst_.ensure(8 * std::max<u64>(X, 1));
-    FillArgs fa{tab, symof_.as<u64>(), v.chars, v.bits, reg, s_sum_.as<u64>(), sc, R, PT, v.W, SubsetPipeline::group_for(v.W),
-                s_edst_.as<u64>(), s_eds_.as<uint8_t>(), s_seds_.as<uint8_t>()};
+    slice_.eds.ensure(E + 16); slice_.seds.ensure(S + 16); slice_.edst.ensure(8 * std::max<u64>(X, 1));
+    FillArgs fa{tab, slice_.symof.as<u64>(), v.chars, v.bits, reg, slice_.sum.as<u64>(), sc, R, PT, v.W, SubsetPipeline::group_for(v.W),
+                slice_.edst.as<u64>(), slice_.eds.as<uint8_t>(), slice_.seds.as<uint8_t>()};
     if (PT) {
         const unsigned grid = (unsigned)std::min<u64>((PT + WAVES - 1) / WAVES, 1u << 18);
-        run("k_slice_place", &timing_.copy_ms, [&] { hipLaunchKernelGGL(k_slice_place, dim3(grid), dim3(ST), 0, st, fa); });
-        run("k_slice_seds", &timing_.copy_ms, [&] { hipLaunchKernelGGL(k_slice_seds, dim3(grid), dim3(ST), 0, st, fa); });
+        timed.run("k_slice_place", [&] { hipLaunchKernelGGL(k_slice_place, dim3(grid), dim3(ST), 0, st, fa); }, &timing_.copy_ms);
+        timed.run("k_slice_seds", [&] { hipLaunchKernelGGL(k_slice_seds, dim3(grid), dim3(ST), 0, st, fa); }, &timing_.copy_ms);
     }
     if (CT) {
         fa.tiles = CT;
-        run("k_slice_copy", &timing_.copy_ms, [&] {
+        timed.run("k_slice_copy", [&] {
             hipLaunchKernelGGL(k_slice_copy, dim3((unsigned)std::min<u64>((CT + WAVES - 1) / WAVES, 1u << 18)), dim3(ST), 0, st, fa);
-        });
+        }, &timing_.copy_ms);
     }
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    harvest();
+    timed.harvest();
     const auto t0 = std::chrono::steady_clock::now();
     eds_out.take(E); seds_out.take(S);
-    PinnedDownload::copy(eds_out.data, s_eds_.ptr, E, st);
-    PinnedDownload::copy(seds_out.data, s_seds_.ptr, S, st);
+    PinnedDownload::copy(eds_out.data, slice_.eds.ptr, E, st);
+    PinnedDownload::copy(seds_out.data, slice_.seds.ptr, S, st);
     if (region) EDSX_HIP(hipMemcpyAsync(region, reg, sizeof(SliceRegion) * R, hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipMemcpyAsync(status, s_st_.ptr, R, hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipMemcpyAsync(status, slice_.st.ptr, R, hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
     timing_.download_ms += since_ms(t0);
     timing_.bytes_written = E + S;

@@ -30,7 +30,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <deque>
 #include <string>
 
 namespace edsx {
@@ -170,12 +169,6 @@ struct RunArgs {
     const u64* sidx; const uint8_t* rcls; const u64* cscan; const u64* headpos;
 };
 
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(ST) k_sub_runinfo(RunArgs a, u64* __restrict__ ctl, u64* __restrict__ eb, u64* __restrict__ sb,
                                                     u64* __restrict__ al)
 {
@@ -225,9 +218,7 @@ __global__ void __launch_bounds__(ST) k_sub_place(PlaceArgs a)
     for (u64 j = t0; j < a.m; j += (u64)gridDim.x * blockDim.x) {
         u64 d = NONE, sd = NONE;
         if (a.r.kscan[j + 1] != a.r.kscan[j]) {
-            u64 lo = 0, hi = a.n - 1;                                // symbol of j: the last i with ent_off[i] <= j
-            while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (a.r.ent_off[mid] <= j) lo = mid; else hi = mid - 1; }
-            const u64 i = lo, r = a.sscan[i];
+            const u64 i = last_le(a.r.ent_off, 0, a.n - 1, j), r = a.sscan[i];   // the symbol of j
             const uint8_t cls = a.r.rcls[r];
             const u64 q = a.hscan[r] + (is_head(a.r.rcls, r) ? 1 : 0) - 1, e = a.eoff[q], e_end = a.eoff[q + 1];
             if (e_end != e) {                                        // (an empty common run has no bytes)
@@ -252,25 +243,18 @@ __global__ void __launch_bounds__(ST) k_sub_place(PlaceArgs a)
     }
 }
 
-// the last j in [lo, hi] with str_off[j] <= c
-__device__ __forceinline__ u64 str_find(const u64* __restrict__ str_off, u64 lo, u64 hi, u64 c)
-{
-    while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (str_off[mid] <= c) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 __global__ void __launch_bounds__(ST) k_sub_copy(const uint8_t* __restrict__ chars, const u64* __restrict__ str_off, u64 m, u64 N,
                                                  const u64* __restrict__ dst, uint8_t* __restrict__ out)
 {
     __shared__ u64 sj[2];
     for (u64 t0 = blockIdx.x * (u64)CP_TILE; t0 < N; t0 += (u64)gridDim.x * CP_TILE) {
         const u64 t1 = min(N, t0 + (u64)CP_TILE);
-        if (threadIdx.x == 0) sj[0] = str_find(str_off, 0, m - 1, t0);
-        if (threadIdx.x == 64) sj[1] = str_find(str_off, 0, m - 1, t1 - 1);
+        if (threadIdx.x == 0) sj[0] = last_le(str_off, 0, m - 1, t0);
+        if (threadIdx.x == 64) sj[1] = last_le(str_off, 0, m - 1, t1 - 1);
         __syncthreads();
         const u64 c0 = t0 + (u64)threadIdx.x * 16;
         if (c0 < t1) {
-            u64 j = str_find(str_off, sj[0], sj[1], c0);
+            u64 j = last_le(str_off, sj[0], sj[1], c0);
             const u64 s0 = str_off[j], s1 = str_off[j + 1];
             if (c0 + 16 <= s1) {                                     // all 16 in string j (so c0 + 16 <= N)
                 const u64 d = dst[j];
@@ -288,6 +272,14 @@ __global__ void __launch_bounds__(ST) k_sub_copy(const uint8_t* __restrict__ cha
     }
 }
 
+// write_set_ids over S & K with the renumbered ids
+struct KeptIds {
+    const KeepSet& ks;
+    __device__ __forceinline__ u64 mask(u32 w) const { return ks.mask[w]; }
+    __device__ __forceinline__ u64 bytes(u32 w, u64 x) const { return word_bytes(ks, w, x); }
+    __device__ __forceinline__ u32 id(u32 w, u32 b) const { return new_id(ks, w, b); }
+};
+
 __global__ void __launch_bounds__(ST) k_sub_seds(const u64* __restrict__ bits, u64 m, KeepSet ks, u32 G, const u64* __restrict__ sdst,
                                                  const u64* __restrict__ bscan, uint8_t* __restrict__ sout)
 {
@@ -298,27 +290,7 @@ __global__ void __launch_bounds__(ST) k_sub_seds(const u64* __restrict__ bits, u
         const bool act = p0 != NONE;
         const u64 end = act ? p0 + (bscan[j + 1] - bscan[j]) : 0;     // one past the closing brace
         if (act && g == 0) sout[p0] = '{';
-        u64 cur = p0 + 1;
-        for (u32 wb = 0; wb < ks.W; wb += G) {
-            const u32 w = wb + g;
-            u64 x = (act && w < ks.W) ? bits[j * ks.W + w] & ks.mask[w] : 0;
-            const u64 nb = word_bytes(ks, w < ks.W ? w : 0, x);
-            u64 incl = nb;
-            for (u32 o = 1; o < G; o <<= 1) { const u64 t = __shfl_up(incl, o, 64); if (g >= o) incl += t; }
-            const u64 total = __shfl(incl, (int)((threadIdx.x & 63u) | (G - 1)), 64);
-            u64 p = cur + incl - nb;
-            while (x) {
-                const u32 b = (u32)__builtin_ctzll(x);
-                x &= x - 1;
-                u32 v = new_id(ks, w, b);
-                const u32 dg = ndigits(v);
-                for (u32 k = dg; k-- > 0;) { sout[p + k] = (uint8_t)('0' + v % 10u); v /= 10u; }
-                p += dg;
-                sout[p] = p + 1 == end ? '}' : ',';
-                p++;
-            }
-            cur += total;
-        }
+        write_set_ids(KeptIds{ks}, bits + j * ks.W, act, ks.W, G, g, p0 + 1, end, sout);
     }
 }
 
@@ -326,43 +298,13 @@ u32 digits_of(u64 v) { u32 d = 1; while (v >= 10) { v /= 10; d++; } return d; }
 
 } // namespace
 
-struct SubsetPipeline::Timed {
-    const char* name;
-    EventPair ev;
-    explicit Timed(const char* n) : name(n) {}
-};
-
-void SubsetPipeline::add_time(const char* name, float ms)
-{
-    for (auto& a : acc_) if (std::string(a.name) == name) { a.total_ms += ms; a.count++; return; }
-    acc_.push_back({name, ms, 1});
-}
-
-int SubsetPipeline::get_timing(const char** names, float* ms, int* counts, int cap) const
-{
-    int n = 0;
-    for (const auto& a : acc_) {
-        if (n >= cap) break;
-        names[n] = a.name; ms[n] = a.total_ms; counts[n] = a.count; n++;
-    }
-    return n;
-}
-
 void SubsetPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n, const u64* ids, size_t nids,
                          bool keep_ids, HostBytes& eds_out, HostBytes& seds_out, SubsetInfo& info, hipStream_t st)
 {
     if (!seds) throw ParamError("Path subsetting needs sources (.seds)");
     if (nids == 0) throw ParamError("No paths selected");
     info = SubsetInfo{};
-    std::deque<Timed> timed;
-    auto timed_run = [&](const char* name, auto&& launch) {
-        if (!timing_) { launch(); return; }
-        timed.emplace_back(name);
-        EDSX_HIP(hipEventRecord(timed.back().ev.a, st));
-        launch();
-        EDSX_HIP(hipEventRecord(timed.back().ev.b, st));
-    };
-    auto harvest = [&] { for (auto& t : timed) add_time(t.name, t.ev.ms()); timed.clear(); };
+    TimedRuns timed(st, &times_);
 
     de.load(eds, eds_n, seds, seds_n, true, st);
     const u64 n = de.n(), m = de.m(), N = de.n_chars();
@@ -375,7 +317,7 @@ void SubsetPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const 
         v = de.view();
         orbits_.ensure(8 * (size_t)W);
         EDSX_HIP(hipMemsetAsync(orbits_.ptr, 0, 8 * (size_t)W, st));
-        timed_run("k_sub_or", [&] { hipLaunchKernelGGL(k_sub_or, dim3(1024), dim3(ST), 0, st, v.bits, W, m, orbits_.as<u64>()); });
+        timed.run("k_sub_or", [&] { hipLaunchKernelGGL(k_sub_or, dim3(1024), dim3(ST), 0, st, v.bits, W, m, orbits_.as<u64>()); });
         std::vector<u64> orb(W, 0);
         EDSX_HIP(hipMemcpyAsync(orb.data(), orbits_.ptr, 8 * (size_t)W, hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
@@ -432,34 +374,34 @@ void SubsetPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const 
     for (u64* p : {kscan + m, lscan + m, bscan + m, sscan + n}) EDSX_HIP(hipMemsetAsync(p, 0, 8, st));
 
     // ---- strings
-    timed_run("k_sub_filter", [&] {
+    timed.run("k_sub_filter", [&] {
         hipLaunchKernelGGL(k_sub_filter, dim3(grid_for(m * G, 16384)), dim3(ST), 0, st, v.bits, v.elen, m, ks, G, kscan, lscan, bscan, sflag);
     });
-    timed_run("scan_strings", [&] {
+    timed.run("scan_strings", [&] {
         ScanSet<3> ss{{kscan, lscan, bscan}, {kscan, lscan, bscan}, {ctl + CT_T0, ctl + CT_T1, ctl + CT_T2}};
         exclusive_scan_multi<3>(ss, ctl + CT_M1, tmp, st);
     });
     // ---- symbols
-    timed_run("k_sub_classify", [&] {
+    timed.run("k_sub_classify", [&] {
         hipLaunchKernelGGL(k_sub_classify, dim3(grid_for(n, 8192)), dim3(ST), 0, st, v.sym.size, v.sym.ent_off, n, kscan, sflag, sscan, scls, kj);
     });
-    timed_run("scan_symbols", [&] { exclusive_scan_u64(sscan, sscan, ctl + CT_N1, ctl + CT_R, tmp, st); });
+    timed.run("scan_symbols", [&] { exclusive_scan_u64(sscan, sscan, ctl + CT_N1, ctl + CT_R, tmp, st); });
     // ---- survivors
-    timed_run("k_sub_compact", [&] {
+    timed.run("k_sub_compact", [&] {
         hipLaunchKernelGGL(k_sub_compact, dim3(grid_for(n, 8192)), dim3(ST), 0, st, n, sscan, scls, kj, v.elen, sidx, rcls, cscan, ctl);
         hipLaunchKernelGGL(k_sub_heads, dim3(grid_for(n, 8192)), dim3(ST), 0, st, ctl, rcls, hscan);
     });
-    timed_run("scan_survivors", [&] {
+    timed.run("scan_survivors", [&] {
         ScanSet<2> ss{{hscan, cscan}, {hscan, cscan}, {ctl + CT_Q, ctl + CT_CCH}};
         exclusive_scan_multi<2>(ss, ctl + CT_R1, tmp, st);
     });
     // ---- runs
     const RunArgs ra{v.sym.size, v.sym.ent_off, kscan, lscan, bscan, sidx, rcls, cscan, headpos};
-    timed_run("k_sub_runs", [&] {
+    timed.run("k_sub_runs", [&] {
         hipLaunchKernelGGL(k_sub_runs, dim3(grid_for(n, 8192)), dim3(ST), 0, st, ctl, rcls, hscan, headpos);
         hipLaunchKernelGGL(k_sub_runinfo, dim3(grid_for(n, 8192)), dim3(ST), 0, st, ra, ctl, eoff, soff, aoff);
     });
-    timed_run("scan_runs", [&] {
+    timed.run("scan_runs", [&] {
         ScanSet<3> ss{{eoff, soff, aoff}, {eoff, soff, aoff}, {ctl + CT_E, ctl + CT_S, ctl + CT_SYMS}};
         exclusive_scan_multi<3>(ss, ctl + CT_Q1, tmp, st);
     });
@@ -475,18 +417,18 @@ void SubsetPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const 
     out_eds_.ensure(E + 1 + 16); out_seds_.ensure(S + 1 + 16);
     uint8_t *oe = out_eds_.as<uint8_t>(), *os = out_seds_.as<uint8_t>();
     const PlaceArgs pa{ra, sflag, sscan, hscan, eoff, soff, n, m, E, S, dst_.as<u64>(), sdst_.as<u64>(), oe, os};
-    timed_run("k_sub_place", [&] { hipLaunchKernelGGL(k_sub_place, dim3(grid_for(m, 8192)), dim3(ST), 0, st, pa); });
+    timed.run("k_sub_place", [&] { hipLaunchKernelGGL(k_sub_place, dim3(grid_for(m, 8192)), dim3(ST), 0, st, pa); });
     if (N)
-        timed_run("k_sub_copy", [&] {
+        timed.run("k_sub_copy", [&] {
             hipLaunchKernelGGL(k_sub_copy, dim3((unsigned)std::min<u64>((N + CP_TILE - 1) / CP_TILE, 1u << 16)), dim3(ST), 0, st, v.chars,
                                v.str_off, m, N, dst_.as<u64>(), oe);
         });
-    timed_run("k_sub_seds", [&] {
+    timed.run("k_sub_seds", [&] {
         hipLaunchKernelGGL(k_sub_seds, dim3(grid_for(m * G, 16384)), dim3(ST), 0, st, v.bits, m, ks, G, sdst_.as<u64>(), bscan, os);
     });
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    harvest();
+    timed.harvest();
     eds_out.take(E + 1);
     seds_out.take(S + 1);
     PinnedDownload::copy(eds_out.data, oe, E + 1, st);

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "eds_device.hpp"
+#include "kernel_times.hpp"
 
 #include <vector>
 
@@ -25,8 +26,8 @@ public:
              bool keep_ids, HostBytes& eds_out, HostBytes& seds_out, SubsetInfo& info, hipStream_t st);
 
     // device time per kernel, accumulated while on (edsx_set_timing / edsx_get_timing)
-    void set_timing(bool on) { timing_ = on; acc_.clear(); }
-    int get_timing(const char** names, float* ms, int* counts, int cap) const;
+    void set_timing(bool on) { times_.set(on); }
+    int get_timing(const char** names, float* ms, int* counts, int cap) const { return times_.get(names, ms, counts, cap); }
 
     // lanes per string for bitsets of W words: the power of two that covers W, at most a wave
     static u32 group_for(u32 W)
@@ -37,12 +38,7 @@ public:
     }
 
 private:
-    struct Acc { const char* name; float total_ms; int count; };
-    struct Timed;
-    void add_time(const char* name, float ms);
-
-    bool timing_ = false;
-    std::vector<Acc> acc_;
+    KernelTimes times_;
     DevBuf ctl_, scan_tmp_, orbits_, mask_, below_, dig_;
     DevBuf kscan_, lscan_, bscan_, sflag_;                       // per string (m + 1)
     DevBuf sscan_, scls_, kj_;                                   // per symbol (n + 1)

@@ -32,7 +32,6 @@
 //                 refpos, 16 bytes of output per lane with the line feeds put in on the way
 #include "vcf_export_device.hpp"
 
-#include <deque>
 #include <string>
 
 namespace edsx {
@@ -318,41 +317,11 @@ bool is_space(char ch) { return ch == ' ' || (ch >= '\t' && ch <= '\r'); }
 
 } // namespace
 
-struct VcfExportPipeline::Timed {
-    const char* name;
-    EventPair ev;
-    explicit Timed(const char* n) : name(n) {}
-};
-
-void VcfExportPipeline::add_time(const char* name, float ms)
-{
-    for (auto& a : acc_) if (std::string(a.name) == name) { a.total_ms += ms; a.count++; return; }
-    acc_.push_back({name, ms, 1});
-}
-
-int VcfExportPipeline::get_timing(const char** names, float* ms, int* counts, int cap) const
-{
-    int n = 0;
-    for (const auto& a : acc_) {
-        if (n >= cap) break;
-        names[n] = a.name; ms[n] = a.total_ms; counts[n] = a.count; n++;
-    }
-    return n;
-}
-
 void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, const uint8_t* seds, size_t seds_n,
                             const VcfExportOpts& opts, HostBytes& vcf_out, HostBytes* fasta, VcfExportInfo& info, hipStream_t st)
 {
     info = VcfExportInfo{};
-    std::deque<Timed> timed;
-    auto timed_run = [&](const char* name, auto&& launch) {
-        if (!timing_) { launch(); return; }
-        timed.emplace_back(name);
-        EDSX_HIP(hipEventRecord(timed.back().ev.a, st));
-        launch();
-        EDSX_HIP(hipEventRecord(timed.back().ev.b, st));
-    };
-    auto harvest = [&] { for (auto& t : timed) add_time(t.name, t.ev.ms()); timed.clear(); };
+    TimedRuns timed(st, &times_);
 
     bool bad_chrom = opts.chrom.empty();
     for (char ch : opts.chrom) bad_chrom = bad_chrom || is_space(ch);
@@ -380,7 +349,7 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
         if (with_gt) {
             orb_.ensure(8 * (size_t)W);
             EDSX_HIP(hipMemsetAsync(orb_.ptr, 0, 8 * (size_t)W, st));
-            timed_run("k_vcf_or", [&] { hipLaunchKernelGGL(k_vcf_or, dim3(1024), dim3(VT), 0, st, v.bits, W, m, orb_.as<u64>()); });
+            timed.run("k_vcf_or", [&] { hipLaunchKernelGGL(k_vcf_or, dim3(1024), dim3(VT), 0, st, v.bits, W, m, orb_.as<u64>()); });
             std::vector<u64> orb(W, 0);
             EDSX_HIP(hipMemcpyAsync(orb.data(), orb_.ptr, 8 * (size_t)W, hipMemcpyDeviceToHost, st));
             EDSX_HIP(hipStreamSynchronize(st));
@@ -389,7 +358,7 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
         }
         info.paths = P;
         if (opts.ref_path > P) {
-            harvest();
+            timed.harvest();
             throw ParamError("Path id " + std::to_string(opts.ref_path) + " out of range (1.." + std::to_string(P) + ")");
         }
         NT = with_gt && P ? P / vcf::TILE_PATHS + 1 : 0;
@@ -397,28 +366,28 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
         u64 *ctl = ctl_.as<u64>(), *tmp = scan_tmp_.as<u64>(), *refidx = refidx_.as<u64>(), *refpos = refpos_.as<u64>(),
             *rank = rank_.as<u64>(), *anchor = anchor_.as<u64>(), *recsym = recsym_.as<u64>();
         EDSX_HIP(hipMemcpyAsync(ctl, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
-        timed_run("k_vcf_sym", [&] {
+        timed.run("k_vcf_sym", [&] {
             hipLaunchKernelGGL(k_vcf_sym, dim3(grid_for(n + 1, 8192)), dim3(VT), 0, st, v.sym.size, v.sym.ent_off, v.str_off, v.bits, W, n,
                                opts.ref_path, refidx, refpos, rank, anchor, ctl);
         });
-        timed_run("scan_symbols", [&] {
+        timed.run("scan_symbols", [&] {
             ScanSet<2> ss{{refpos, rank}, {refpos, rank}, {ctl + CT_L, ctl + CT_RECS}};
             exclusive_scan_multi<2>(ss, ctl + CT_N1, tmp, st);
         });
         t = vcf::Tab{v.sym.size, v.sym.ent_off, v.str_off, v.chars, v.bits, W, refidx, refpos, anchor, n, P,
                      chrom_.as<uint8_t>(), (u32)opts.chrom.size(), with_gt ? 1u : 0u};
-        timed_run("k_vcf_anchor", [&] {
+        timed.run("k_vcf_anchor", [&] {
             hipLaunchKernelGGL(k_vcf_anchor, dim3(grid_for(n, 8192)), dim3(VT), 0, st, t, rank, anchor, recsym, ctl);
         });
         EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
         EDSX_HIP(hipStreamSynchronize(st));
         EDSX_HIP(hipGetLastError());
         if (hctl[CT_ERRREF] != vcf::NONE) {
-            harvest();
+            timed.harvest();
             throw ParamError("Path " + std::to_string(opts.ref_path) + " takes no string of symbol " + std::to_string(hctl[CT_ERRREF]));
         }
         if (hctl[CT_ERRANC] != vcf::NONE) {
-            harvest();
+            timed.harvest();
             throw FormatError("Symbol " + std::to_string(hctl[CT_ERRANC]) + " has an empty string and no reference base to anchor it");
         }
         const u64 R = hctl[CT_RECS];
@@ -429,15 +398,15 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
             tmp = scan_tmp_.as<u64>();
             u64* table = table_.as<u64>();
             EDSX_HIP(hipMemcpyAsync(ctl + CT_TABN, &tabn, 8, hipMemcpyHostToDevice, st));
-            timed_run("k_vcf_fixedlen", [&] {
+            timed.run("k_vcf_fixedlen", [&] {
                 hipLaunchKernelGGL(k_vcf_fixedlen, dim3(grid_for(R, 8192)), dim3(VT), 0, st, t, recsym, R, NT, table, ctl);
             });
             if (NT)
-                timed_run("k_vcf_count", [&] {
+                timed.run("k_vcf_count", [&] {
                     hipLaunchKernelGGL(k_vcf_count, dim3((unsigned)std::min<u64>(R * NT, 1u << 18)), dim3(64 * std::min<u32>(4, W)), 0, st,
                                        t, recsym, R, NT, table);
                 });
-            timed_run("scan_table", [&] { exclusive_scan_u64(table, table, ctl + CT_TABN, ctl + CT_BODY, tmp, st); });
+            timed.run("scan_table", [&] { exclusive_scan_u64(table, table, ctl + CT_TABN, ctl + CT_BODY, tmp, st); });
             EDSX_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
             EDSX_HIP(hipStreamSynchronize(st));
             EDSX_HIP(hipGetLastError());
@@ -466,7 +435,7 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
     head += "\n";
     info.header_bytes = head.size();
     if (opts.max_bytes && body > opts.max_bytes) {
-        harvest();
+        timed.harvest();
         throw LimitError("VCF body of " + std::to_string(body) + " bytes is above the limit of " + std::to_string(opts.max_bytes));
     }
 
@@ -476,11 +445,11 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
         uint8_t* o = out_.as<uint8_t>();
         const u64* table = table_.as<u64>();
         const u64* recsym = recsym_.as<u64>();
-        timed_run("k_vcf_fixed", [&] {
+        timed.run("k_vcf_fixed", [&] {
             hipLaunchKernelGGL(k_vcf_fixed, dim3(grid_for(R * FIX_LANES, 1u << 16)), dim3(VT), 0, st, t, recsym, R, NT, table, o);
         });
         if (NT)
-            timed_run("k_vcf_cells", [&] {
+            timed.run("k_vcf_cells", [&] {
                 hipLaunchKernelGGL(k_vcf_cells, dim3((unsigned)std::min<u64>(R * NT, 1u << 18)), dim3(64 * std::min<u32>(4, t.W)), 0, st, t,
                                    recsym, R, NT, table, o);
             });
@@ -490,14 +459,14 @@ void VcfExportPipeline::run(DeviceEds& de, const uint8_t* eds, size_t eds_n, con
     const u64 fbody = L ? L + (L + lw - 1) / lw : 0;
     if (fasta && fbody) {
         fa_.ensure(fbody + 16);
-        timed_run("k_vcf_ref", [&] {
+        timed.run("k_vcf_ref", [&] {
             hipLaunchKernelGGL(k_vcf_ref, dim3((unsigned)std::min<u64>((fbody + REF_TILE - 1) / REF_TILE, 1u << 16)), dim3(VT), 0, st, t, L, lw,
                                fbody, fa_.as<uint8_t>());
         });
     }
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
-    harvest();
+    timed.harvest();
     vcf_out.take(head.size() + body);
     std::memcpy(vcf_out.data, head.data(), head.size());
     PinnedDownload::copy(vcf_out.data + head.size(), out_.ptr, body, st);

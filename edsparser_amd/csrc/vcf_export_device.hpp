@@ -4,6 +4,7 @@
 #pragma once
 
 #include "eds_device.hpp"
+#include "kernel_times.hpp"
 #include "vcf_text.hpp"
 
 #include <string>
@@ -33,16 +34,11 @@ public:
              HostBytes& vcf, HostBytes* fasta, VcfExportInfo& info, hipStream_t st);
 
     // device time per kernel, accumulated while on (edsx_set_timing / edsx_get_timing)
-    void set_timing(bool on) { timing_ = on; acc_.clear(); }
-    int get_timing(const char** names, float* ms, int* counts, int cap) const;
+    void set_timing(bool on) { times_.set(on); }
+    int get_timing(const char** names, float* ms, int* counts, int cap) const { return times_.get(names, ms, counts, cap); }
 
 private:
-    struct Acc { const char* name; float total_ms; int count; };
-    struct Timed;
-    void add_time(const char* name, float ms);
-
-    bool timing_ = false;
-    std::vector<Acc> acc_;
+    KernelTimes times_;
     DevBuf ctl_, scan_tmp_, orb_, chrom_;
     DevBuf refidx_, refpos_, rank_, anchor_, recsym_;            // per symbol (n + 1)
     DevBuf table_;                                               // per record: fixed part, tile 0, tile 1, ... (+ 1)

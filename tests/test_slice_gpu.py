@@ -250,6 +250,19 @@ def s_spell(ctx, eds, seds, p):
         return bytes(s.spell([p], 0)[0]).split(b"\n")[1]
 
 
+def test_session_timing_is_filled_with_kernel_timing_off(ctx):
+    """The two timings are separate: with edsx_set_timing off no slice kernel is listed by name, and the session's own
+    timing of the call is filled all the same"""
+    eds, seds = b"{AC,G}{T}{,GA}", b"{1}{2}{0}{2}{1}"
+    ctx.set_timing(False)
+    with ctx.paths_open(eds, seds) as s:
+        got = s.slice([1], [1], [4])
+        t = s.timing
+    assert (bytes(got[0]), bytes(got[1])) == (b"{C,}{T}{,G}\n", b"{1}{2}{0}{2}{1}\n")
+    assert not [name for name, *_ in ctx.get_timing() if name.startswith("k_slice_")]
+    assert t["scan_ms"] > 0 and t["copy_ms"] > 0 and t["bytes_written"] == len(got[0]) + len(got[1])
+
+
 def test_kernels_come_back_by_name(ctx):
     eds, seds = TINY[0]
     ctx.set_timing(True)
