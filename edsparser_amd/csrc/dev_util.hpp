@@ -6,6 +6,7 @@
 
 #include "draw.hpp"
 #include "byte_ops.hpp"
+#include "errors.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -17,7 +18,7 @@
 
 namespace edsx {
 
-struct DeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
+// DeviceError: errors.hpp
 struct OutOfDeviceMemory : DeviceError { using DeviceError::DeviceError; };     // hipMalloc said so: the caller may retry with less
 
 #define EDSX_HIP(call)                                                                        \

@@ -8,16 +8,13 @@
 #include <new>
 
 #include "dev_util.hpp"
+#include "errors.hpp"
 
 #include <vector>
 
 namespace edsx {
 
-struct FormatError : std::runtime_error { using std::runtime_error::runtime_error; };   // EDSX_ERR_INVALID_FORMAT
-struct ParamError : std::runtime_error { using std::runtime_error::runtime_error; };    // EDSX_ERR_INVALID_PARAMETER
-// a well-formed input beyond a limit of this build (more than MsaPipeline::MAX_ROWS sequences): EDSX_ERR_BUILD_FAILED,
-// not a format error - the reference has no such limit
-struct LimitError : std::runtime_error { using std::runtime_error::runtime_error; };
+// FormatError, ParamError, LimitError: errors.hpp
 
 // Where device memory comes from (dev_alloc.hip): the only hipMalloc / hipFree of the library.  dev_alloc releases *ptr when
 // it is set, then allocates `bytes` rounded up to 256 and stores the pointer and the rounded size; a failure leaves *ptr

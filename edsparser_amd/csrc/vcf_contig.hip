@@ -247,16 +247,18 @@ void VcfSession::index_fasta(hipStream_t st)
     const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
     DevBuf hdr, nonnl, tmp, ctl, hstart;
     hdr.ensure(8 * (nblk + 2)); nonnl.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((nblk + 2) / SCAN_TILE + 4)); ctl.ensure(8 * 8);
-    u64 hctl[8] = {nblk, 0, 0, 0, 0, 0, 0, 0};
-    EDSX_HIP(hipMemcpyAsync(ctl.ptr, hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
+    struct FiCtl { u64 n, nhdr; };                                           // the header scan's element count and total
+    FiCtl hctl{nblk, 0};
+    FiCtl* dctl = ctl.as<FiCtl>();
+    EDSX_HIP(hipMemcpyAsync(dctl, &hctl, sizeof(hctl), hipMemcpyHostToDevice, st));
     const uint8_t* f = d_fasta_.as<uint8_t>();
     TraceSpan span(st, "fasta record index", n);
     hipLaunchKernelGGL(k_fi_count, dim3(2048), dim3(256), 0, st, f, n, hdr.as<u64>(), nonnl.as<u64>());
-    exclusive_scan_u64(hdr.as<u64>(), hdr.as<u64>(), ctl.as<u64>() + 0, ctl.as<u64>() + 1, tmp.as<u64>(), st);
-    exclusive_scan_u64(nonnl.as<u64>(), nonnl.as<u64>(), ctl.as<u64>() + 0, nonnl.as<u64>() + nblk, tmp.as<u64>(), st);
-    EDSX_HIP(hipMemcpyAsync(hctl, ctl.ptr, sizeof(hctl), hipMemcpyDeviceToHost, st));
+    exclusive_scan_u64(hdr.as<u64>(), hdr.as<u64>(), &dctl->n, &dctl->nhdr, tmp.as<u64>(), st);
+    exclusive_scan_u64(nonnl.as<u64>(), nonnl.as<u64>(), &dctl->n, nonnl.as<u64>() + nblk, tmp.as<u64>(), st);
+    EDSX_HIP(hipMemcpyAsync(&hctl, dctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
     EDSX_HIP(hipStreamSynchronize(st));
-    const u64 nhdr = hctl[1];                                               // >= 1: byte 0 is a '>'
+    const u64 nhdr = hctl.nhdr;                                             // >= 1: byte 0 is a '>'
     if (nhdr == 0 || nhdr >= 0xffffffffull) throw DeviceError("FASTA record index: " + std::to_string(nhdr) + " records");
     hstart.ensure(8 * (nhdr + 1));
     d_recs_.ensure(sizeof(ContigRec) * (nhdr + 1));
@@ -285,32 +287,25 @@ bool VcfSession::classify_device(hipStream_t st)
     { const char* e = getenv("EDSX_HOST_TOKENIZER"); if (e && atoi(e)) return false; }
     const u64 n = vcf_n_;
     if (!device_scratch_fits(6 * n)) return false;
-    d_vcf_.ensure(n + 16);
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    d_vcf_.ensure(vcf_size::text(n));
     DevBuf idx, tmp, ctlb, lstart, keys, keys2, ord1, ord2, table, first, thash, trec;
-    idx.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((n + 2) / SCAN_TILE + 4)); ctlb.ensure(8 * 32);
-    VtCtl* ctl = ctlb.as<VtCtl>();
-    VcCtl* vctl = reinterpret_cast<VcCtl*>(ctlb.as<u64>() + 16);
-    VtCtl h{};
-    h.n = nblk;
-    EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
+    struct ClassifyCtl { VtCtl vt; VcCtl vc; };                             // the line-start step's and the classification's
+    ctlb.ensure(8 * 32);
+    VtCtl* ctl = &ctlb.as<ClassifyCtl>()->vt;
+    VcCtl* vctl = &ctlb.as<ClassifyCtl>()->vc;
+    vt_line_starts_reset(n, ctl, idx, tmp, st);
     if (!vcf_resident_) {
         EDSX_HIP(hipMemcpyAsync(d_vcf_.ptr, vcf_, n, hipMemcpyHostToDevice, st));
         vcf_h2d += n;
     }
     const uint8_t* raw = d_vcf_.as<uint8_t>();
     TraceSpan lines(st, "vcf line starts", 2 * n);     // (count pass + fill pass: the text is read twice)
-    hipLaunchKernelGGL(k_vt_line_count, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), ctl);
-    exclusive_scan_u64(idx.as<u64>(), idx.as<u64>(), &ctl->n, &ctl->nrec, tmp.as<u64>(), st);
-    EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-    EDSX_HIP(hipStreamSynchronize(st));
-    if (h.bad || h.nrec >= 0xffffffffull) return false;                     // '\r' somewhere, or too many lines
-    const u64 nr = h.nrec, K = recs_.size();
-    first_.assign(K + 2, ~0ull);
-    if (nr == 0) { lines.end(); records_total = 0; return true; }
-    lstart.ensure(8 * (nr + 1));
-    hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), lstart.as<u64>());
+    const u64 nr = vt_line_starts(raw, n, ctl, idx, lstart, tmp, st);
+    if (nr == VT_NOT_PLAIN) return false;                                    // '\r' somewhere, or too many lines
     lines.end();
+    const u64 K = recs_.size();
+    first_.assign(K + 2, ~0ull);
+    if (nr == 0) { records_total = 0; return true; }
     if (ignore_chrom_) {                                                     // every record line belongs to record 0, file order
         EDSX_HIP(hipStreamSynchronize(st));
         std::swap(lsorted_.ptr, lstart.ptr); std::swap(lsorted_.cap, lstart.cap);

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "msa_device.hpp"
+#include "vcf_host.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -11,34 +12,8 @@
 
 namespace edsx {
 
-struct VcfCounters {   // vcf_transforms.hpp:24-35
-    u64 total_variants = 0, processed_variants = 0, skipped_malformed = 0, skipped_unsupported_sv = 0, variant_groups = 0;
-};
-
-// FASTA metadata of a partitioned run, found once over the slices of all ranks (VcfPipeline::fasta_slice, vcf_multi.hip).
-// regular: the file is one record without '\r' or blank lines, and every line but its last (non-empty) one has exactly the first
-// line's width lw, so position p sits at file offset seq_start + p + p / lw (vcf_transforms.cpp:98-129 read it there)
-// and a range of positions can be read from a window of the file.
-struct FastaMeta { u64 seq_size = 0; bool regular = false; };
-// one rank's slice [a, b) of the FASTA body, exchanged as it is: the first "\n>" in it (its '>', ~0: none), and in front of
-// that: the bytes that are not '\n', flags (1: '\r', 2: a byte on the line grid of width lw + 1 that is not '\n'), the
-// first '\n' off that grid (~0: none)
-struct FaSlice { u64 rec_end, count, flags, offgrid; };
-// header line and first sequence line (:51-86) with the reference's error texts: sequence start, width of the first
-// line, offset of the second line
-void fasta_head(const uint8_t* fasta, size_t fasta_n, u64& seq_start, u64& lw, u64& rest_from);
-
-// One position range of a partitioned run: the records are handed over in their final order, the
-// walk starts at cur0 (no common text in front of the first group when cur0 is its start) and the closing common
-// text stops at the first group of the next range.
-struct VcfRange {
-    bool presorted = false;
-    u64 cur0 = 0;
-    u64 next_start = ~0ull;        // ~0: last (or only) range, flush to the end of the reference
-    // set: seq_size comes from here, and a regular file is read from the window [off(cur0), off(end)) only (end =
-    // next_start, or seq_size for the last range; 16 bytes of slack, clipped to the file); otherwise the whole file
-    const FastaMeta* fasta = nullptr;
-};
+// VcfCounters, FastaMeta, FaSlice, VcfRange, fasta_head, vcf_index, vcf_sort_order and the rest of the host code of this
+// path: vcf_host.hpp, which has no HIP include
 
 // Inputs that are already in HBM (a contig session, vcf_contig.hpp): nothing of them is uploaded again.
 struct VcfResident {
@@ -74,11 +49,16 @@ struct TraceSpan {
     ~TraceSpan() { if (a) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } }
 };
 
-// index pass of a partitioned run: positions, REF lengths and line spans of the accepted records, file order
-void vcf_index(const uint8_t* vcf, size_t vcf_n, std::vector<u64>& pos, std::vector<u64>& reflen, std::vector<u64>& line_off,
-               std::vector<u64>& line_len, VcfCounters& stats);
-// permutation the reference's std::sort (vcf_transforms.cpp:715-718) gives an array with these positions
-void vcf_sort_order(const u64* pos, size_t n, u32* order_out);
+// the state of one VcfPipeline::run, handed from stage to stage
+struct VcfWalk {
+    VcfDev d{}; GrpArrays ga{}; HapArrays ha{};
+    RefWindow w{};                 // what of the FASTA the device holds
+    u64 max_samples = 0;
+    u64 ngrp = 0, E = 0, Q = 0;    // groups and the bytes of their symbols (EDS, sEDS; common text in front included)
+    u64 cur = 0, tail = 0;         // reference position behind the last group; bases of the closing common text
+    u64 Etot() const { return E + (tail ? tail + 2 : 0); }
+    u64 Qtot() const { return Q + (tail ? 3 : 0); }
+};
 
 class VcfPipeline {
 public:
@@ -103,6 +83,21 @@ private:
                          VcfCounters& stats);
     bool tokenize_lines(const uint8_t* raw, u64 n, const u64* lstart, u64 nr, bool presorted, hipStream_t st, u64& nrec,
                         u64& max_samples, VcfCounters& stats);
+    // the stages of run(), in its order (vcf_device.hip)
+    void reference_stream(VcfWalk& k, const uint8_t* fasta, u64 rest_from, const FastaMeta* meta, const VcfRange& range,
+                          const uint8_t* d_resident, hipStream_t st);
+    void host_records(VcfWalk& k, const VcfSoA& s, hipStream_t st);
+    void grouping(VcfWalk& k, const VcfSoA* host, hipStream_t st);
+    void haplotypes_and_sizes(VcfWalk& k, hipStream_t st);
+    void tail(VcfWalk& k, u64 next_start, hipStream_t st);
+    void emit(const VcfWalk& k, hipStream_t st);
+    void download(const VcfWalk& k, HostBytes& eds, HostBytes& seds, hipStream_t st);
+    void window_check(const VcfWalk& k, u64 v) const;
+    // ctl_ holds one VcfCtl (vcf_walk.hpp); hctl_ is the host's image of it
+    VtCtl* vt_ctl() { ctl_.ensure(vcf_size::ctl()); return &ctl_.as<VcfCtl>()->vt; }
+    void read_ctl(hipStream_t st);
+    void set_scan_count(u64 n, hipStream_t st);
+    VcfCtl hctl_{};
     DevBuf vt_raw_, vt_idx_, vt_lstart_, vt_pos_, vt_reflen_, vt_nalt_, vt_altc_, vt_ngt_, vt_nall_, vt_s1_, vt_s2_, vt_s3_,
            vt_s4_, vt_order_, vt_sorttmp_;
     DevBuf d_fasta_, refc_, blkpre_, scan_tmp_, ctl_, start_, reflen_, alt0_, altoff_, altchars_, pair0_, pa0_, alleles_,

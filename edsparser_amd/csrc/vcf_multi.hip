@@ -19,29 +19,17 @@
 
 #include <algorithm>
 #include <cstring>
-#include <numeric>
 
 namespace edsx {
 
 namespace {
 
-// start of the first line at or after byte n * k / world (the same rule on every rank: vcf_byte_range)
-u64 vcf_cut(const uint8_t* v, u64 n, int k, int world)
-{
-    if (k <= 0) return 0;
-    if (k >= world) return n;
-    const u64 g = (u64)((unsigned __int128)n * (unsigned)k / (unsigned)world);
-    if (g == 0) return 0;
-    const void* nl = std::memchr(v + g - 1, '\n', n - (g - 1));
-    return nl ? (u64)(static_cast<const uint8_t*>(nl) - v) + 1 : n;
-}
+// vcf_cut, fasta_meta, plan_vcf_cuts, line_runs and Run: vcf_host.hpp (plain host code, tested on the CPU)
 
 struct VcfHead {                // exchanged as it is
     u64 nrec, total, processed, malformed, unsupported;
     FaSlice slice;
 };
-
-struct Run { u64 k; const uint8_t* p; u64 n; };   // lines of sorted records k, k+1, ... back to back (inner '\n' kept)
 
 } // namespace
 
@@ -93,25 +81,14 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
     if (!phase([&] { xch_->all_gather(r, &mine, sizeof(VcfHead), heads.data()); })) return;
     std::vector<u64> base(N + 1, 0);
     VcfCounters tot;
-    FastaMeta meta;
-    u64 rec_end = sh.fasta_n, flags = 0, offgrid = ~0ull;
+    std::vector<FaSlice> slices(N);
     for (int k = 0; k < N; k++) {
         base[k + 1] = base[k] + heads[k].nrec;
         tot.total_variants += heads[k].total; tot.processed_variants += heads[k].processed;
         tot.skipped_malformed += heads[k].malformed; tot.skipped_unsupported_sv += heads[k].unsupported;
-        rec_end = std::min(rec_end, heads[k].slice.rec_end);
+        slices[k] = heads[k].slice;
     }
-    for (int k = 0; k < N; k++) {
-        const u64 a = sh.seq_start + (u64)((unsigned __int128)body * (unsigned)k / (unsigned)N);
-        if (a >= rec_end) continue;                            // slices behind the first record
-        meta.seq_size += heads[k].slice.count;
-        flags |= heads[k].slice.flags;
-        offgrid = std::min(offgrid, heads[k].slice.offgrid);
-    }
-    // regular: one record, no '\r', every grid byte a '\n', and no '\n' off the grid but the one that ends a shorter
-    // (non-empty) last line
-    meta.regular = sh.lw > 0 && rec_end == sh.fasta_n && flags == 0 &&
-                   (offgrid == ~0ull || (offgrid + 1 == rec_end && (offgrid - sh.seq_start) % (sh.lw + 1) != 0));
+    const FastaMeta meta = fasta_meta(slices.data(), N, sh.seq_start, sh.lw, sh.fasta_n);
     const u64 n = base[N];
     if (r == 0) *sh.stats = tot;
     if (!phase([&] {
@@ -126,10 +103,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
     if (!phase([&] { xch_->all_gather_v(r, N, pr.data(), pr.size(), all, sizes); })) return;
 
     // ---- 4. the same order and cuts on every rank; 5. (local) my lines for every destination
-    std::vector<u32> order;
-    std::vector<u64> start;                                    // sorted record starts (POS - 1)
-    std::vector<u64> cuts(N + 1, 0);
-    bool wraps = false;
+    VcfPlan plan;                                              // order, sorted record starts (POS - 1), cuts, wraps
     std::vector<Run> keep;                                     // my lines that stay here
     std::vector<uint8_t> payload;                              // per destination: nruns, nbytes, k[], nbytes[], text
     u64 moved = 0;
@@ -143,49 +117,11 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
                 std::memcpy(gref.data() + base[k], all.data() + (size_t)k * cap + 8 * m, 8 * m);
             }
             std::vector<uint8_t>().swap(all);
-            order.resize(n);
-            std::iota(order.begin(), order.end(), 0u);
-            bool ascending = true;
-            for (u64 j = 1; j < n && ascending; j++) ascending = gpos[j - 1] < gpos[j];
-            if (!ascending) {
-                std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return gpos[x] < gpos[y]; });
-                bool equal = false;
-                for (u64 j = 1; j < n && !equal; j++) equal = gpos[order[j - 1]] == gpos[order[j]];
-                if (equal) vcf_sort_order(gpos.data(), n, order.data());      // the reference's std::sort decides
-            }
-            start.resize(n);
-            std::vector<u64> end(n);
-            for (u64 j = 0; j < n; j++) {
-                start[j] = gpos[order[j]] - 1;                     // wraps for POS 0 like the reference's size_t
-                end[j] = start[j] + gref[order[j]];
-                wraps |= start[j] == ~0ull || end[j] < start[j];
-            }
-            cuts[N] = n;
-            if (wraps) { for (int k = 1; k < N; k++) cuts[k] = n; return; }
-            // group starts: start[j] >= every earlier end (:510); cut k at the first group start at or after n * k / N
-            std::vector<u64> gstarts;
-            u64 mx = 0;
-            for (u64 j = 0; j < n; j++) {
-                if (j == 0 || start[j] >= mx) gstarts.push_back(j);
-                mx = j == 0 ? end[j] : std::max(mx, end[j]);
-            }
-            for (int k = 1; k < N; k++) {
-                const u64 target = (u64)((unsigned __int128)n * (unsigned)k / (unsigned)N);
-                auto it = std::lower_bound(gstarts.begin(), gstarts.end(), target);
-                cuts[k] = std::max(cuts[k - 1], it == gstarts.end() ? n : *it);
-            }
-            // my records of every destination's range, as runs of lines (multigpu.py, _line_runs)
+            plan = plan_vcf_cuts(gpos, gref, N);
+            if (plan.wraps) return;
+            // my records of every destination's range, as runs of lines
             for (int d = 0; d < N; d++) {
-                std::vector<Run> runs;
-                u64 prev_loc = ~0ull, prev_end = 0;
-                for (u64 k = cuts[d]; k < cuts[d + 1]; k++) {
-                    const u64 g = order[k];
-                    if (g < base[r] || g >= base[r + 1]) { prev_loc = ~0ull; continue; }
-                    const u64 loc = g - base[r], o = lo + loff[loc], len = llen[loc];
-                    if (prev_loc != ~0ull && loc == prev_loc + 1 && prev_end + 1 == o) runs.back().n = o + len - (u64)(runs.back().p - sh.vcf);
-                    else runs.push_back(Run{k, sh.vcf + o, len});
-                    prev_loc = loc; prev_end = o + len;
-                }
+                std::vector<Run> runs = line_runs(plan.order, plan.cuts[d], plan.cuts[d + 1], base[r], base[r + 1], sh.vcf, lo, loff, llen);
                 if (d == r) { keep = std::move(runs); continue; }
                 u64 nb = 0;
                 for (const Run& x : runs) nb += x.n;
@@ -202,7 +138,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
         })) return;
 
     // ---- wrapped positions: not partitioned, rank 0 runs the unpartitioned transform on the whole file
-    if (wraps) {
+    if (plan.wraps) {
         if (!phase([&] {
                 if (r != 0) return;
                 VcfCounters c;
@@ -225,6 +161,7 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
     if (!phase([&] { xch_->all_gather_v(r, N, payload.data(), payload.size(), got, got_sizes); })) return;
 
     // ---- 6. my lines in sorted order -> my range of the transform
+    const std::vector<u64>&cuts = plan.cuts, &start = plan.start;
     std::vector<int> nonempty;
     for (int k = 0; k < N; k++) if (cuts[k] < cuts[k + 1]) nonempty.push_back(k);
     const u64 n_mine = cuts[r + 1] - cuts[r];

@@ -3,7 +3,7 @@
 // the kernels are static, every translation unit that includes this gets its own copy.
 #pragma once
 
-#include "dev_util.hpp"
+#include "msa_device.hpp"
 #include "vcf_walk.hpp"
 
 namespace edsx {
@@ -37,6 +37,35 @@ static __global__ void __launch_bounds__(256) k_vt_line_fill(const uint8_t* __re
         u64 at = base[b] + (incl - c);
         while (m) { lstart[at++] = i0 + (u32)__builtin_ctz(m); m &= m - 1; }
     }
+}
+
+// The line starts of a text in HBM (raw: n bytes, 256-byte aligned, vcf_size::text(n) allocated), in two steps so that a
+// caller can put a trace span around the device work alone.  vt_line_starts_reset sizes idx (the scanned block counts)
+// and tmp (the scan's scratch) and resets ctl (n = the number of blocks); vt_line_starts then runs count pass, block
+// scan and fill pass, sizes lstart and returns the number of record lines, or VT_NOT_PLAIN ('\r' somewhere, or 2^32
+// lines and more).
+constexpr u64 VT_NOT_PLAIN = ~0ull;
+static void vt_line_starts_reset(u64 n, VtCtl* ctl, DevBuf& idx, DevBuf& tmp, hipStream_t st)
+{
+    idx.ensure(vcf_size::line_counts(vcf_size::line_blocks(n)));           // line starts per 1 KB block of the text
+    tmp.ensure(8 * ((n + 2) / SCAN_TILE + 4));
+    VtCtl h{};
+    h.n = vcf_size::line_blocks(n);                                         // element count of the block scan
+    EDSX_HIP(hipMemcpyAsync(ctl, &h, sizeof(h), hipMemcpyHostToDevice, st));
+}
+static u64 vt_line_starts(const uint8_t* raw, u64 n, VtCtl* ctl, DevBuf& idx, DevBuf& lstart, DevBuf& tmp, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_vt_line_count, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), ctl);
+    exclusive_scan_u64(idx.as<u64>(), idx.as<u64>(), &ctl->n, &ctl->nrec, tmp.as<u64>(), st);
+    VtCtl h{};
+    EDSX_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    EDSX_HIP(hipStreamSynchronize(st));
+    if (h.bad || h.nrec >= 0xffffffffull) return VT_NOT_PLAIN;
+    if (h.nrec) {
+        lstart.ensure(vcf_size::line_starts(h.nrec));
+        hipLaunchKernelGGL(k_vt_line_fill, dim3(2048), dim3(256), 0, st, raw, n, idx.as<u64>(), lstart.as<u64>());
+    }
+    return h.nrec;
 }
 
 // ---- LSD radix sort of (u64 key, u32 value) pairs: eight stable passes of eight bits (unsorted VCFs with distinct

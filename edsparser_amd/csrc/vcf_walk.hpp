@@ -62,6 +62,18 @@ struct HostGrid { u64 f, s; u64 first() const { return f; } u64 stride() const {
 
 struct VtCtl { u64 n, bad, nrec, max_samples, t_alt, t_altc, t_pair, t_all, oob; };
 
+// The control block of a VcfPipeline (ctl_, vcf_size::ctl() bytes in HBM): what the host and the kernels of one run()
+// tell each other.  Every word has one name and one meaning; the host addresses a field as &ctl->field and reads the
+// block back as a whole.  Who writes what: DESIGN 5.
+struct VcfCtl {
+    u64 n;                       // element count of the scan in flight (blocks, records, groups)
+    u64 refc_n, max_end, ngrp, nraw, rawchars, bitwords, eds, seds;   // totals of the scans, in the order run() makes them
+    u64 cpos;                    // k_cpos: place of the tail's first base in refc
+    u64 rec_end, rest_bytes;     // k_fa_record_end (atomicMin from fasta_n), k_fa_seq_bytes: bytes of the later lines
+    u64 oob;                     // window mode: VcfDev::oob points here
+    VtCtl vt;                    // the tokeniser's own (tokenize_device, tokenize_lines, index_device)
+};
+
 // The bytes of the VCF text through 8-byte aligned loads.  A thread walks its line from left to right, so seven of
 // eight byte reads come out of the register window instead of a one-byte load each (k_vt_count 0.80 -> 0.65 ms,
 // k_vt_fill 0.96 -> 0.75 ms per 10^6 records, round 2).  Bounds: the text buffer starts 256-byte aligned (hipMalloc) and
@@ -188,7 +200,6 @@ struct GrpArrays {
     u64* bitwords;                           // ndist * sample words
     u64* eds_len; u64* seds_len;             // group symbol + preceding common region
     u64* commonlen; u64* cur_after;          // common region before the group, reference position after it
-    u64* err;                                // [0] first failing group, [1] offset, [2] span length
 };
 
 // apply_variant_to_span :356-390: span.substr(0, off) + alt + (off + |ref| < |span| ? span.substr(off + |ref|) : "").
@@ -591,7 +602,7 @@ inline u64 fasta(u64 up_n) { return up_n + 16; }                    // d_fasta_:
 inline u64 ref_blocks(u64 body) { return (body + 255) / 256; }
 inline u64 blkpre(u64 nblk) { return 8 * (nblk + 2); }
 inline u64 refc(u64 body) { return body + 16; }
-inline u64 ctl() { return 8 * 32; }
+constexpr u64 ctl() { return 8 * 32; }                             // ctl_: one VcfCtl
 inline u64 per_group(u64 ngrp) { return 8 * (ngrp + 2); }           // every u64-per-group array
 inline u64 per_raw(u64 nraw_total) { return 8 * (nraw_total + 2); } // rawlen_, rawoff_
 inline u64 canon(u64 nraw_total) { return 4 * (nraw_total + 2); }
@@ -599,5 +610,6 @@ inline u64 hapchars(u64 rawchars_total) { return rawchars_total + 16; }
 inline u64 carried(u64 bitwords_total) { return 8 * (bitwords_total + 2); }
 inline u64 eds(u64 total) { return total + 16; }                    // d_eds_, d_seds_
 }
+static_assert(sizeof(VcfCtl) <= vcf_size::ctl(), "VcfCtl must fit the control buffer");
 
 } // namespace edsx

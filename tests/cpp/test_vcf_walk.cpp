@@ -1,27 +1,27 @@
 // test_vcf_walk.cpp — the VCF -> EDS overlay on the CPU: the per-thread device code of edsparser_amd/csrc/vcf_walk.hpp run
-// one "thread" after another over a case file written by tests/vcf_walk_cases.py; meant to be built with
-// -fsanitize=address,undefined.  Every buffer is a heap block of its own, of exactly the size VcfPipeline asks for
-// (vcf_size::*), filled with a byte the case chooses, so the first byte nobody asked for is a redzone; the two texts are
-// 256-byte aligned as on the device.  The steps the device does with wave operations (line starts, reference compaction,
-// scans, the sort of distinct positions, the common-text copy) are the plain loops below.
+// one "thread" after another, and the host code of the path (csrc/vcf_host.hpp: FASTA head, host tokeniser, records -> SoA,
+// the sweep for wrapped positions, window and tail arithmetic, the planner of a partitioned run) as the library compiles
+// it, over a case file written by tests/vcf_walk_cases.py; meant to be built with -fsanitize=address,undefined.  Every
+// buffer is a heap block of its own, of exactly the size VcfPipeline asks for (vcf_size::*, and upload()'s for the host
+// tokeniser's arrays), filled with a byte the case chooses, so the first byte nobody asked for is a redzone; the two texts
+// are 256-byte aligned as on the device.  The steps the device does with wave operations (line starts, reference
+// compaction, scans, the sort of distinct positions, the common-text copy, the FASTA slice scan) are the plain loops below.
 //
 // Case records (little endian): u32 mode, u32 nfills, nfills bytes, u32 name_len, name, u64 vcf_len, vcf, u64 fasta_len,
-// fasta, u64 up0, u64 up1.   mode 0: whole transform   1: up to the count pass   2: fa_cpos over the window [up0, up1)
-// 3: fa_cpos over the whole file.   One result per (case, fill): u32 name_len, name, u32 fill, u32 verdict, u64 detail,
-// u64 eds_len, eds, u64 seds_len, seds.   verdict 0: accepted (mode 0: texts follow)   1: not plain, the host tokeniser's
-// 2: equal positions (out of scope here)   3: a byte index outside the text was reported (detail)   4: refused input
-// 5: fa_cpos differs from the byte-by-byte count at file offset `detail`
-#include "vcf_walk.hpp"
+// fasta, u64 a0, a1, a2, a3.
+//   mode 0: whole transform, device tokeniser only   1: up to the count pass   2: fa_cpos over the window [a0, a1)
+//   3: fa_cpos over the whole file   4: whole transform as the library runs it: the host tokeniser where the count pass
+//   says "not plain"   5: one position range: the lines are presorted, cur0 = a0, next_start = a1, FastaMeta{a2, a3}
+//   6: the planner of a partitioned run over a0 ranks (result: u64 words in `eds`, the runs' text in `seds`, see plan())
+// One result per (case, fill): u32 name_len, name, u32 fill, u32 verdict, u64 detail, u64 eds_len, eds, u64 seds_len,
+// seds.   verdict 0: accepted (texts follow)   1: not plain, the host tokeniser's   3: a byte index outside the text or
+// the window was reported (detail)   4: refused input (the library throws)   5: fa_cpos differs from the byte-by-byte
+// count at file offset `detail`
+#include "vcf_host.hpp"
 
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <iterator>
-#include <string>
-#include <utility>
-#include <vector>
 
 using namespace edsx;
 
@@ -44,6 +44,12 @@ struct Arena {                   // the DevBufs of one call
         blocks.push_back(p);
         return static_cast<T*>(p);
     }
+    template <class T> T* upload(const std::vector<T>& v)  // upload() of vcf_device.hip
+    {
+        T* p = get<T>(sizeof(T) * (v.size() + 1) + 16);
+        if (!v.empty()) std::memcpy(p, v.data(), sizeof(T) * v.size());
+        return p;
+    }
 };
 
 template <class F> void each_thread(F f) { for (u64 t = 0; t < THREADS; t++) f(HostGrid{t, THREADS}); }
@@ -63,14 +69,16 @@ void inclusive_max_scan(const u64* in, u64* out, u64 n, u64* total)
 
 struct Result { u32 verdict = 0; u64 detail = 0; std::vector<uint8_t> eds, seds; };
 
-struct Tokens {                   // what tokenize_device leaves behind
+struct Tokens {                   // the record SoA in "HBM", from either tokeniser
     u64 nrec = 0, max_samples = 0;
     u64 *start = nullptr, *reflen = nullptr, *alt0 = nullptr, *altoff = nullptr, *pair0 = nullptr, *pa0 = nullptr;
     uint8_t* altchars = nullptr; int* alleles = nullptr;
+    VcfSoA host;                  // host tokeniser: the arrays on the host (grouping looks at them for wrapped positions)
+    bool from_host = false;
 };
 
 // VcfPipeline::tokenize_device + tokenize_lines.  false: r.verdict says why
-bool tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool count_only, u64* ctlbuf, Tokens& tk, Result& r)
+bool device_tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool count_only, bool presorted, VtCtl* ctl, Tokens& tk, Result& r)
 {
     const u64 n = vcf.size();
     if (n == 0) { r.verdict = 1; return false; }
@@ -78,7 +86,6 @@ bool tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool count_only, u64* c
     std::memcpy(raw, vcf.data(), n);
     const u64 nblk = vcf_size::line_blocks(n);
     u64* idx = A.get<u64>(vcf_size::line_counts(nblk));
-    VtCtl* ctl = reinterpret_cast<VtCtl*>(ctlbuf + 16);
     *ctl = VtCtl{};
     ctl->n = nblk;
     bool cr = false;
@@ -113,16 +120,18 @@ bool tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool count_only, u64* c
     if (ctl->bad) { r.verdict = 1; return false; }
     if (count_only) return true;
     const u32* order = nullptr;
-    if (ctl->t_alt) {                                                  // not ascending: the radix sort's result for distinct keys
+    if (ctl->t_alt && !presorted) {            // not ascending: the radix sort's result for distinct keys, else the host's sort
         std::vector<std::pair<u64, u32>> ord(nr);
         for (u64 i = 0; i < nr; i++) ord[i] = {vr.pos[i], (u32)i};
         std::sort(ord.begin(), ord.end());
-        for (u64 i = 0; i + 1 < nr; i++) if (ord[i].first == ord[i + 1].first) { r.verdict = 2; return false; }
+        bool equal = false;
+        for (u64 i = 0; i + 1 < nr; i++) equal |= ord[i].first == ord[i + 1].first;
         u32* o = A.get<u32>(vcf_size::order(nr));
-        for (u64 i = 0; i < nr; i++) o[i] = ord[i].second;
+        if (equal) vcf_sort_order(vr.pos, nr, o);
+        else for (u64 i = 0; i < nr; i++) o[i] = ord[i].second;
         order = o;
-        ctl->t_alt = 0;
     }
+    ctl->t_alt = 0;
     ctl->n = nr;
     each_thread([&](HostGrid g) { vt_gather_body(vr, order, nr, s1, s2, s3, s4, g); });
     tk.alt0 = A.get<u64>(vcf_size::per_record(nr)); tk.pair0 = A.get<u64>(vcf_size::per_record(nr));
@@ -140,121 +149,150 @@ bool tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool count_only, u64* c
     return true;
 }
 
-// fasta_head of vcf_device.hip: header line, first sequence line
-bool fasta_head(const std::vector<uint8_t>& fa, u64& seq_start, u64& lw, u64& rest_from)
+// the host tokeniser's way of VcfPipeline::run: tokenise -> order -> SoA -> the eight uploads
+void host_tokenise(Arena& A, const std::vector<uint8_t>& vcf, bool presorted, Tokens& tk)
 {
-    const u64 n = fa.size();
-    if (n == 0 || fa[0] != '>') return false;
-    u64 e = 0;
-    while (e < n && fa[e] != '\n') e++;
-    if (e == n) { seq_start = n; return false; }                       // no second line: "FASTA file is empty"
-    seq_start = e + 1;
-    if (seq_start >= n) return false;
-    u64 e2 = seq_start;
-    while (e2 < n && fa[e2] != '\n') e2++;
-    lw = e2 - seq_start;
-    rest_from = e2 < n ? e2 + 1 : n;
-    return lw != 0;
+    static const uint8_t none = 0;
+    std::vector<VcfPart> parts;
+    std::vector<u64> part_base;
+    VcfCounters stats;
+    tokenise(vcf.empty() ? &none : vcf.data(), vcf.size(), parts, part_base, stats, false);
+    tk.host = build_soa(parts, part_base, host_order(parts, part_base, presorted));
+    const VcfSoA& s = tk.host;
+    tk.from_host = true;
+    tk.nrec = s.start.size(); tk.max_samples = s.max_samples;
+    tk.start = A.upload(s.start); tk.reflen = A.upload(s.reflen); tk.alt0 = A.upload(s.alt0); tk.altoff = A.upload(s.altoff);
+    tk.altchars = A.upload(s.altchars); tk.pair0 = A.upload(s.pair0); tk.pa0 = A.upload(s.pa0); tk.alleles = A.upload(s.alleles);
 }
 
 // the reference stream of run(): text [up0, up1) of the file on the "device", blkpre / refc from file offset cbase on
 struct RefStream { uint8_t* dfa; u64* blkpre; uint8_t* refc; u64 refc_n; };
-RefStream reference_stream(Arena& A, const std::vector<uint8_t>& fa, u64 up0, u64 up1, bool window, u64 seq_start, u64* ctl)
+RefStream reference_stream(Arena& A, const std::vector<uint8_t>& fa, const RefWindow& w, u64 seq_start, VcfCtl* ctl)
 {
     RefStream s{};
-    const u64 fasta_n = fa.size(), up_n = up1 - up0;
+    const u64 fasta_n = fa.size(), up_n = w.up1 - w.up0;
     s.dfa = A.get<uint8_t>(vcf_size::fasta(up_n), true);
-    if (up_n) std::memcpy(s.dfa, fa.data() + up0, up_n);
-    const u64 body = window ? up_n : fasta_n > seq_start ? fasta_n - seq_start : 0;
+    if (up_n) std::memcpy(s.dfa, fa.data() + w.up0, up_n);
+    const u64 body = w.window ? up_n : fasta_n > seq_start ? fasta_n - seq_start : 0;
     const u64 nblk = vcf_size::ref_blocks(body);
     s.blkpre = A.get<u64>(vcf_size::blkpre(nblk));
     s.refc = A.get<uint8_t>(vcf_size::refc(body));
-    ctl[0] = nblk;
-    const u64 kn = window ? up_n : fasta_n, ks = window ? 0 : seq_start;
+    ctl->n = nblk;
+    const u64 kn = w.window ? up_n : fasta_n, ks = w.window ? 0 : seq_start;
     auto kept = [](uint8_t ch) { return ch != '\n' && ch != '\r'; };
     for (u64 b = 0; b < nblk; b++) {                                   // k_fa_count
         u64 c = 0;
         for (u64 i = ks + b * 256; i < ks + b * 256 + 256 && i < kn; i++) c += kept(s.dfa[i]);
         s.blkpre[b] = c;
     }
-    if (nblk) exclusive_scan(s.blkpre, s.blkpre, ctl[0], &ctl[1]);
+    if (nblk) exclusive_scan(s.blkpre, s.blkpre, ctl->n, &ctl->refc_n);
     for (u64 b = 0; b < nblk; b++) {                                   // k_fa_compact
         u64 o = s.blkpre[b];
         for (u64 i = ks + b * 256; i < ks + b * 256 + 256 && i < kn; i++) if (kept(s.dfa[i])) s.refc[o++] = s.dfa[i];
     }
-    s.refc_n = nblk ? ctl[1] : 0;
+    s.refc_n = nblk ? ctl->refc_n : 0;
     return s;
 }
 
-// VcfPipeline::run on the whole file (no position range, nothing resident)
-Result transform(uint8_t fill, const std::vector<uint8_t>& vcf, const std::vector<uint8_t>& fa, bool count_only)
+bool head_of(const std::vector<uint8_t>& fa, u64& seq_start, u64& lw, u64& rest_from)      // false: the library refuses the file
+{
+    static const uint8_t none = 0;
+    try { fasta_head(fa.empty() ? &none : fa.data(), fa.size(), seq_start, lw, rest_from); } catch (const FormatError&) { return false; }
+    return lw != 0;
+}
+
+// VcfPipeline::run, nothing resident.  host: take the host tokeniser where the device tokeniser says "not plain"
+Result transform(uint8_t fill, const std::vector<uint8_t>& vcf, const std::vector<uint8_t>& fa, bool count_only, bool host,
+                 const VcfRange& range = VcfRange())
 {
     Result r;
     Arena A(fill);
-    u64* ctl = A.get<u64>(vcf_size::ctl());
+    VcfCtl* ctl = A.get<VcfCtl>(vcf_size::ctl());
     u64 seq_start = 0, lw = 0, rest_from = 0;
-    const bool fasta_ok = fasta_head(fa, seq_start, lw, rest_from);
+    const bool fasta_ok = head_of(fa, seq_start, lw, rest_from);
     if (!count_only && !fasta_ok) { r.verdict = 4; return r; }
     Tokens tk;
-    if (!tokenise(A, vcf, count_only, ctl, tk, r) || count_only) return r;
-    const u64 fasta_n = fa.size(), nrec = tk.nrec;
-    std::memset(ctl, 0, vcf_size::ctl());
-    ctl[10] = ~0ull; ctl[12] = fasta_n;
-    const RefStream rs = reference_stream(A, fa, 0, fasta_n, false, seq_start, ctl);
-    if (rest_from < fasta_n) {
-        each_thread([&](HostGrid g) { fa_record_end_body(rs.dfa, fasta_n, rest_from, ctl + 12, g); });
-        for (u64 i = rest_from; i < ctl[12]; i++) ctl[13] += rs.dfa[i] != '\n';        // k_fa_seq_bytes
+    if (!device_tokenise(A, vcf, count_only, range.presorted, &ctl->vt, tk, r)) {
+        if (!(host && r.verdict == 1)) return r;
+        r = Result();
+        try { host_tokenise(A, vcf, range.presorted, tk); } catch (const FormatError&) { r.verdict = 4; return r; }
     }
-    const u64 seq_size = lw + ctl[13];
+    if (count_only) return r;
+    const u64 fasta_n = fa.size(), nrec = tk.nrec;
+    const FastaMeta* meta = range.fasta;
+    // reference stream
+    const RefWindow w = reference_window(range, meta, seq_start, lw, fasta_n);
+    *ctl = VcfCtl{};
+    ctl->rec_end = fasta_n;
+    const RefStream rs = reference_stream(A, fa, w, seq_start, ctl);
+    if (!meta && rest_from < fasta_n) {
+        each_thread([&](HostGrid g) { fa_record_end_body(rs.dfa, fasta_n, rest_from, &ctl->rec_end, g); });
+        for (u64 i = rest_from; i < ctl->rec_end; i++) ctl->rest_bytes += rs.dfa[i] != '\n';      // k_fa_seq_bytes
+    }
+    const u64 seq_size = meta ? meta->seq_size : lw + ctl->rest_bytes;
 
     VcfDev d{};
-    d.fasta = rs.dfa + seq_start; d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
+    d.fasta = rs.dfa + (w.cbase - w.up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.seq_size = seq_size; d.lw = lw;
     d.refc = rs.refc; d.refc_n = rs.refc_n; d.blkpre = rs.blkpre;
-    d.cbase = seq_start; d.wend = fasta_n; d.oob = nullptr;
-    d.nrec = nrec; d.cur0 = 0;
-    u64 cur = 0, ngrp = 0, E = 0, Q = 0;
+    d.cbase = w.cbase; d.wend = w.up1; d.oob = w.window ? &ctl->oob : nullptr;
+    d.nrec = nrec; d.cur0 = range.cur0;
+    auto window_check = [&](u64 v) { if (v) { r.verdict = 3; r.detail = v; } return v != 0; };
+    u64 cur = range.cur0, ngrp = 0, E = 0, Q = 0;
     GrpArrays ga{};
     HapArrays ha{};
     if (nrec) {
+        // grouping
         d.start = tk.start; d.reflen = tk.reflen; d.alt0 = tk.alt0; d.altstr_off = tk.altoff; d.altchars = tk.altchars;
         d.pair0 = tk.pair0; d.pair_a0 = tk.pa0; d.alleles = tk.alleles;
         u64* ends = A.get<u64>(vcf_size::per_record(nrec)); u64* flag = A.get<u64>(vcf_size::per_record(nrec));
         u64* gidx = A.get<u64>(vcf_size::per_record(nrec)); u64* grp_r0 = A.get<u64>(vcf_size::per_record(nrec));
-        ctl[0] = nrec;
-        each_thread([&](HostGrid g) { rec_ends_body(d.start, d.reflen, nrec, ends, g); });
-        inclusive_max_scan(ends, ends, ctl[0], ctl + 2);
-        each_thread([&](HostGrid g) { mark_groups_body(d.start, ends, nrec, flag, g); });
-        exclusive_scan(flag, gidx, ctl[0], ctl + 3);
-        each_thread([&](HostGrid g) { group_firsts_body(flag, gidx, nrec, grp_r0, ctl + 3, g); });
-        ngrp = ctl[3];
+        ctl->n = nrec;
+        if (!(tk.from_host && positions_wrap(tk.host.start, tk.host.reflen))) {
+            each_thread([&](HostGrid g) { rec_ends_body(d.start, d.reflen, nrec, ends, g); });
+            inclusive_max_scan(ends, ends, ctl->n, &ctl->max_end);
+            each_thread([&](HostGrid g) { mark_groups_body(d.start, ends, nrec, flag, g); });
+        } else {
+            std::vector<u64> hflag, hend;
+            sweep_groups(tk.host.start, tk.host.reflen, hflag, hend);
+            std::memcpy(flag, hflag.data(), 8 * nrec);
+            std::memcpy(ends, hend.data(), 8 * nrec);
+        }
+        exclusive_scan(flag, gidx, ctl->n, &ctl->ngrp);
+        each_thread([&](HostGrid g) { group_firsts_body(flag, gidx, nrec, grp_r0, &ctl->ngrp, g); });
+        ngrp = ctl->ngrp;
         d.ngrp = ngrp; d.grp_r0 = grp_r0; d.incl_end = ends;
+        // haplotypes and sizes
         u64* gb[14];
         for (u64*& p : gb) p = A.get<u64>(vcf_size::per_group(ngrp));
-        ga = GrpArrays{gb[0], gb[1], gb[2], gb[3], gb[4], gb[5], gb[6], gb[7], gb[8], gb[9], gb[10], ctl + 10};
+        ga = GrpArrays{gb[0], gb[1], gb[2], gb[3], gb[4], gb[5], gb[6], gb[7], gb[8], gb[9], gb[10]};
         u64 *raw0 = gb[11], *rawc0 = gb[12], *bit0 = gb[13];
-        ctl[0] = ngrp;
+        ctl->n = ngrp;
         each_thread([&](HostGrid g) { grp_count_body(d, ga, g); });
-        exclusive_scan(ga.nraw, raw0, ctl[0], ctl + 4);
-        exclusive_scan(ga.rawchars, rawc0, ctl[0], ctl + 5);
-        const u64 nraw_total = ctl[4], rawchars_total = ctl[5];
+        exclusive_scan(ga.nraw, raw0, ctl->n, &ctl->nraw);
+        exclusive_scan(ga.rawchars, rawc0, ctl->n, &ctl->rawchars);
+        const u64 nraw_total = ctl->nraw, rawchars_total = ctl->rawchars;
         const u32 sw = (u32)std::max<u64>(1, (tk.max_samples + 63) / 64);
         ha = HapArrays{raw0, rawc0, A.get<u64>(vcf_size::per_raw(nraw_total)), A.get<u64>(vcf_size::per_raw(nraw_total)),
                        A.get<u32>(vcf_size::canon(nraw_total)), A.get<uint8_t>(vcf_size::hapchars(rawchars_total)), bit0, nullptr, sw};
         each_thread([&](HostGrid g) { grp_haps_body(d, ga, ha, g); });
-        exclusive_scan(ga.bitwords, bit0, ctl[0], ctl + 6);
-        ha.carried = A.get<u64>(vcf_size::carried(ctl[6]));
+        exclusive_scan(ga.bitwords, bit0, ctl->n, &ctl->bitwords);
+        ha.carried = A.get<u64>(vcf_size::carried(ctl->bitwords));
         each_thread([&](HostGrid g) { grp_samples_body(d, ga, ha, g); });
         each_thread([&](HostGrid g) { grp_common_body(d, ga, g); });
-        exclusive_scan(ga.eds_len, ga.eds_len, ctl[0], ctl + 7);
-        exclusive_scan(ga.seds_len, ga.seds_len, ctl[0], ctl + 8);
-        E = ctl[7]; Q = ctl[8]; cur = ga.cur_after[ngrp - 1];
+        exclusive_scan(ga.eds_len, ga.eds_len, ctl->n, &ctl->eds);
+        exclusive_scan(ga.seds_len, ga.seds_len, ctl->n, &ctl->seds);
+        E = ctl->eds; Q = ctl->seds; cur = ga.cur_after[ngrp - 1];
+        if (w.window && window_check(ctl->oob)) return r;
     }
+    // tail
     u64 tail = 0;
-    if (cur < seq_size) {
-        const u64 length = seq_size - cur;
-        cpos_body(d, seq_start + cur + cur / lw, ctl + 11, HostGrid{0, 1});
-        tail = std::min<u64>(length, rs.refc_n - ctl[11]);
+    if (const u64 length = tail_length(cur, seq_size, range.next_start)) {
+        const u64 off = seq_start + cur + cur / lw;
+        cpos_body(d, off, &ctl->cpos, HostGrid{0, 1});
+        tail = tail_clamp(length, rs.refc_n, ctl->cpos);
+        if (w.window && tail < length && window_check(off | (1ull << 62))) return r;
     }
+    // emit
     const u64 Etot = E + (tail ? tail + 2 : 0), Qtot = Q + (tail ? 3 : 0);
     uint8_t* eds = A.get<uint8_t>(vcf_size::eds(Etot)); uint8_t* seds = A.get<uint8_t>(vcf_size::eds(Qtot));
     if (ngrp) {
@@ -271,6 +309,7 @@ Result transform(uint8_t fill, const std::vector<uint8_t>& vcf, const std::vecto
         each_thread([&](HostGrid g) { grp_emit_body(d, ga, ha, ea, g); });
     }
     if (tail) each_thread([&](HostGrid g) { tail_body(d, cur, tail, eds + E, seds + Q, g); });
+    if (w.window && window_check(ctl->oob)) return r;
     r.eds.assign(eds, eds + Etot); r.seds.assign(seds, seds + Qtot);
     return r;
 }
@@ -280,27 +319,95 @@ Result cpos_sweep(uint8_t fill, const std::vector<uint8_t>& fa, u64 up0, u64 up1
 {
     Result r;
     Arena A(fill);
-    u64* ctl = A.get<u64>(vcf_size::ctl());
-    std::memset(ctl, 0, vcf_size::ctl());
+    VcfCtl* ctl = A.get<VcfCtl>(vcf_size::ctl());
+    *ctl = VcfCtl{};
     u64 seq_start = 0, lw = 0, rest_from = 0;
     const u64 fasta_n = fa.size();
-    if (!fasta_head(fa, seq_start, lw, rest_from) || up0 > up1 || up1 > fasta_n || (window && up0 < seq_start)) { r.verdict = 4; return r; }
+    if (!head_of(fa, seq_start, lw, rest_from) || up0 > up1 || up1 > fasta_n || (window && up0 < seq_start)) { r.verdict = 4; return r; }
     if (!window) { up0 = 0; up1 = fasta_n; }
-    const RefStream rs = reference_stream(A, fa, up0, up1, window, seq_start, ctl);
-    const u64 cbase = window ? up0 : seq_start;
+    const RefWindow w{window, up0, up1, window ? up0 : seq_start};
+    const RefStream rs = reference_stream(A, fa, w, seq_start, ctl);
     VcfDev d{};
-    d.fasta = rs.dfa + (cbase - up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.lw = lw;
-    d.refc = rs.refc; d.refc_n = rs.refc_n; d.blkpre = rs.blkpre; d.cbase = cbase; d.wend = up1; d.oob = window ? ctl + 20 : nullptr;
+    d.fasta = rs.dfa + (w.cbase - up0); d.fasta_n = fasta_n; d.seq_start = seq_start; d.lw = lw;
+    d.refc = rs.refc; d.refc_n = rs.refc_n; d.blkpre = rs.blkpre; d.cbase = w.cbase; d.wend = up1; d.oob = window ? &ctl->oob : nullptr;
     u64 want = 0;                                                      // kept bytes in [cbase, off)
-    for (u64 off = cbase; off < fasta_n + 2; off++) {
-        ctl[20] = 0;
-        cpos_body(d, off, ctl + 11, HostGrid{0, 1});
+    for (u64 off = w.cbase; off < fasta_n + 2; off++) {
+        ctl->oob = 0;
+        cpos_body(d, off, &ctl->cpos, HostGrid{0, 1});
         const bool outside = off >= fasta_n || off >= up1;
         const u64 expect = outside ? rs.refc_n : want;
         const u64 expect_oob = window && off < fasta_n && off > up1 ? (off | (1ull << 63)) : 0;
-        if (ctl[11] != expect || ctl[20] != expect_oob) { r.verdict = 5; r.detail = off; return r; }
+        if (ctl->cpos != expect || ctl->oob != expect_oob) { r.verdict = 5; r.detail = off; return r; }
         if (off < up1) want += fa[off] != '\n' && fa[off] != '\r';
     }
+    return r;
+}
+
+// VcfPipeline::fasta_slice with its two kernels as loops: slice [a, b) of the FASTA body
+FaSlice fasta_slice(const std::vector<uint8_t>& fa, u64 a, u64 b, u64 seq_start, u64 rest_from, u64 lw)
+{
+    FaSlice r{~0ull, 0, 0, ~0ull};
+    if (a >= b) return r;
+    for (u64 i = std::max(a, rest_from); i < b; i++) if (fa[i] == '>' && fa[i - 1] == '\n') { r.rec_end = i; break; }   // k_fa_slice_end
+    const u64 hi = std::min(r.rec_end, b), period = lw + 1;                                                           // k_fa_slice_scan
+    for (u64 i = a; i < hi; i++) {
+        const bool grid = (i - seq_start) % period == lw;
+        r.count += fa[i] != '\n';
+        if (fa[i] == '\r') r.flags |= 1;
+        if (grid && fa[i] != '\n') r.flags |= 2;
+        if (!grid && fa[i] == '\n' && i < r.offgrid) r.offgrid = i;
+    }
+    return r;
+}
+
+// Phases 1 to 4 of MultiMsa::run_rank_vcf for all N ranks at once, without the exchanges.  Words: has_meta, seq_size,
+// regular; per rank lo, hi; n, wraps, cuts[N + 1], order[n], start[n]; unless wraps, per (rank, destination): the number of
+// runs, their k, their byte counts - and their text, back to back, in `seds`.
+Result plan(const std::vector<uint8_t>& vcf, const std::vector<uint8_t>& fa, int N)
+{
+    static const uint8_t none = 0;
+    Result r;
+    std::vector<u64> words;
+    const uint8_t* v = vcf.empty() ? &none : vcf.data();
+    u64 seq_start = 0, lw = 0, rest_from = 0;
+    FastaMeta meta;
+    const bool has_meta = head_of(fa, seq_start, lw, rest_from);
+    if (has_meta) {
+        std::vector<FaSlice> slices(N);
+        const u64 body = fa.size() - seq_start;
+        for (int k = 0; k < N; k++)
+            slices[k] = fasta_slice(fa, seq_start + (u64)((unsigned __int128)body * (unsigned)k / (unsigned)N),
+                                    seq_start + (u64)((unsigned __int128)body * (unsigned)(k + 1) / (unsigned)N), seq_start, rest_from, lw);
+        meta = fasta_meta(slices.data(), N, seq_start, lw, fa.size());
+    }
+    words.insert(words.end(), {(u64)has_meta, meta.seq_size, (u64)meta.regular});
+    std::vector<u64> gpos, gref, base(N + 1, 0), lo(N), hi(N);
+    std::vector<std::vector<u64>> loff(N), llen(N);
+    for (int k = 0; k < N; k++) {
+        lo[k] = vcf_cut(v, vcf.size(), k, N); hi[k] = vcf_cut(v, vcf.size(), k + 1, N);
+        words.push_back(lo[k]); words.push_back(hi[k]);
+        std::vector<u64> pos, reflen;
+        VcfCounters c;
+        vcf_index(hi[k] > lo[k] ? v + lo[k] : &none, hi[k] - lo[k], pos, reflen, loff[k], llen[k], c);
+        gpos.insert(gpos.end(), pos.begin(), pos.end()); gref.insert(gref.end(), reflen.begin(), reflen.end());
+        base[k + 1] = gpos.size();
+    }
+    const VcfPlan p = plan_vcf_cuts(gpos, gref, N);
+    words.push_back(gpos.size()); words.push_back(p.wraps);
+    words.insert(words.end(), p.cuts.begin(), p.cuts.end());
+    words.insert(words.end(), p.order.begin(), p.order.end());
+    words.insert(words.end(), p.start.begin(), p.start.end());
+    if (!p.wraps)
+        for (int k = 0; k < N; k++)
+            for (int d = 0; d < N; d++) {
+                const std::vector<Run> runs = line_runs(p.order, p.cuts[d], p.cuts[d + 1], base[k], base[k + 1], v, lo[k], loff[k], llen[k]);
+                words.push_back(runs.size());
+                for (const Run& x : runs) words.push_back(x.k);
+                for (const Run& x : runs) words.push_back(x.n);
+                for (const Run& x : runs) r.seds.insert(r.seds.end(), x.p, x.p + x.n);
+            }
+    r.eds.resize(8 * words.size());
+    if (!words.empty()) std::memcpy(r.eds.data(), words.data(), r.eds.size());
     return r;
 }
 
@@ -324,9 +431,19 @@ int main(int argc, char** argv)
         const std::vector<uint8_t> name = bytes(u32at());
         const std::vector<uint8_t> vcf = bytes(u64at());
         const std::vector<uint8_t> fa = bytes(u64at());
-        const u64 up0 = u64at(), up1 = u64at();
+        u64 a[4];
+        for (u64& x : a) x = u64at();
         for (uint8_t fill : fills) {
-            const Result r = mode <= 1 ? transform(fill, vcf, fa, mode == 1) : cpos_sweep(fill, fa, up0, up1, mode == 2);
+            Result r;
+            if (mode <= 1) r = transform(fill, vcf, fa, mode == 1, false);
+            else if (mode <= 3) r = cpos_sweep(fill, fa, a[0], a[1], mode == 2);
+            else if (mode == 4) r = transform(fill, vcf, fa, false, true);
+            else if (mode == 5) {
+                const FastaMeta meta{a[2], a[3] != 0};
+                VcfRange range;
+                range.presorted = true; range.cur0 = a[0]; range.next_start = a[1]; range.fasta = &meta;
+                r = transform(fill, vcf, fa, false, true, range);
+            } else r = plan(vcf, fa, (int)a[0]);
             put32((uint32_t)name.size()); out.write(reinterpret_cast<const char*>(name.data()), name.size());
             put32(fill); put32(r.verdict); put64(r.detail);
             put64(r.eds.size()); out.write(reinterpret_cast<const char*>(r.eds.data()), r.eds.size());

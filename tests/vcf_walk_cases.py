@@ -1,5 +1,5 @@
 """Inputs of the host twin of the VCF transform (tests/cpp/test_vcf_walk.cpp: the device's per-thread code, csrc/vcf_walk.hpp,
-run on the CPU under the address and undefined-behaviour sanitizers) and the twin itself: case files, the build, the
+and the path's host code, csrc/vcf_host.hpp, on the CPU under the address and undefined-behaviour sanitizers) and the twin itself: case files, the build, the
 results.  No oracle imports: tests/test_vcf_walk_cpu.py and tests/test_vcf_walk_gpu.py bring the expected bytes."""
 import json
 import os
@@ -12,8 +12,8 @@ import vcf_cases as vc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FILLS = (0x00, 0x0A, 0xFF, 0x09)                 # what a fresh buffer may hold: NUL, line feeds, 0xFF, tabs
-FULL, COUNT, CPOS_WINDOW, CPOS_FILE = 0, 1, 2, 3
-ACCEPTED, NOT_PLAIN, EQUAL_POS, OOB, REFUSED, CPOS_DIFFERS = 0, 1, 2, 3, 4, 5
+FULL, COUNT, CPOS_WINDOW, CPOS_FILE, HOST, RANGE, PLAN = 0, 1, 2, 3, 4, 5, 6
+ACCEPTED, NOT_PLAIN, OOB, REFUSED, CPOS_DIFFERS = 0, 1, 3, 4, 5
 HEAD = ["##fileformat=VCFv4.2", "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"])]
 
 
@@ -22,20 +22,21 @@ def build_test_vcf_walk(root, out, sanitize=True):
     """tests/cpp/test_vcf_walk.cpp (host code only: no device library) with the address and undefined-behaviour sanitizers,
     or plain (sanitize=False: for a caller that wants the program's verdicts only, as the GPU tests do)."""
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan"] if sanitize else []
-    cmd = ["g++", "-std=c++17", "-O1", "-g"] + san + ["-I", root + "/edsparser_amd/csrc", root + "/tests/cpp/test_vcf_walk.cpp", "-o", out]
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread"] + san + ["-I", root + "/edsparser_amd/csrc", root + "/tests/cpp/test_vcf_walk.cpp", "-o", out]
     subprocess.run(cmd, check=True)
     return out
 
 
 def write_cases(path, cases):
-    """cases: (mode, fills, name, vcf, fasta[, up0, up1])"""
+    """cases: (mode, fills, name, vcf, fasta[, up to four numbers]): the window [up0, up1) of the fa_cpos modes, (cur0,
+    next_start, seq_size, regular) of RANGE, the world of PLAN"""
     with open(path, "wb") as f:
         for c in cases:
             mode, fills, name, vcf, fasta = c[:5]
-            up0, up1 = (c[5], c[6]) if len(c) > 5 else (0, 0)
+            a = (list(c[5:]) + [0, 0, 0, 0])[:4]
             nm = name.encode()
             f.write(struct.pack("<II", mode, len(fills)) + bytes(fills) + struct.pack("<I", len(nm)) + nm +
-                    struct.pack("<Q", len(vcf)) + vcf + struct.pack("<Q", len(fasta)) + fasta + struct.pack("<QQ", up0, up1))
+                    struct.pack("<Q", len(vcf)) + vcf + struct.pack("<Q", len(fasta)) + fasta + struct.pack("<QQQQ", *a))
 
 
 def read_results(path):
