@@ -23,27 +23,10 @@
 
 namespace edsx {
 
-namespace {
-
-constexpr u64 FNV_OFFSET = 1469598103934665603ull, FNV_PRIME = 1099511628211ull;
-
-inline bool host_isspace(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // what operator>> skips ("C" locale)
-
-} // namespace
+// fi_header_mask, FiBlocks and the walks over them, the bodies of the thread-per-item kernels, and the host arithmetic of
+// the session (name table, radix passes, counts, host classification): vcf_contig_walk.hpp, which the host twin compiles too
 
 // ---- FASTA record index ----------------------------------------------------------------------------------
-// bit i: byte i0 + i is a '>' that starts a line; nn: bytes of the chunk that are not '\n'
-__device__ __forceinline__ u32 fi_header_mask(const uint8_t* __restrict__ f, u64 n, u64 i0, u32& nn)
-{
-    nn = 0;
-    if (i0 >= n) return 0;
-    const uint4 v = *reinterpret_cast<const uint4*>(f + i0);              // (256-byte aligned buffer, 16 bytes of slack)
-    const u32 valid = n - i0 >= 16 ? 0xffffu : (1u << (n - i0)) - 1u;
-    const u32 nl = chunk_eq16b(v, 0x0a0a0a0au), gt = chunk_eq16b(v, 0x3e3e3e3eu);
-    const u32 prev_nl = ((nl << 1) | (i0 == 0 || f[i0 - 1] == '\n' ? 1u : 0u)) & 0xffffu;
-    nn = (u32)__builtin_popcount(~nl & valid);
-    return gt & prev_nl & valid;
-}
 static __global__ void __launch_bounds__(256) k_fi_count(const uint8_t* __restrict__ f, u64 n, u64* __restrict__ hdr, u64* __restrict__ nonnl)
 {
     const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
@@ -72,132 +55,24 @@ static __global__ void __launch_bounds__(256) k_fi_fill(const uint8_t* __restric
     }
 }
 
-// nnpre[b] = bytes that are not '\n' in front of block b (b <= nblk; nnpre[nblk] = all of them)
-struct FiBlocks { const uint8_t* f; u64 n; const u64* nnpre; u64 nblk; };
-__device__ __forceinline__ u64 fi_newlines_before(const FiBlocks& k, u64 b)
-{
-    const u64 bytes = b * VT_BLOCK < k.n ? b * VT_BLOCK : k.n;
-    return bytes - k.nnpre[b];
-}
-// the first '\n' in [from, limit), or limit (limit <= n): the rest of from's block byte by byte, then a binary search over
-// the block counts for the next block that holds a newline, then that block
-__device__ u64 fi_next_newline(const FiBlocks& k, u64 from, u64 limit)
-{
-    if (from >= limit) return limit;
-    const u64 b = from / VT_BLOCK;
-    const u64 e = (b + 1) * VT_BLOCK < limit ? (b + 1) * VT_BLOCK : limit;
-    for (u64 i = from; i < e; i++) if (k.f[i] == '\n') return i;
-    if (e >= limit) return limit;
-    const u64 have = fi_newlines_before(k, b + 1);
-    u64 lo = b + 1, hi = (limit + VT_BLOCK - 1) / VT_BLOCK;                 // blocks [lo, hi) overlap [e, limit); hi <= nblk
-    const u64 end = hi;
-    while (lo < hi) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (fi_newlines_before(k, mid + 1) > have) hi = mid; else lo = mid + 1;
-    }
-    if (lo >= end) return limit;
-    const u64 e2 = (lo + 1) * VT_BLOCK < limit ? (lo + 1) * VT_BLOCK : limit;
-    for (u64 i = lo * VT_BLOCK; i < e2; i++) if (k.f[i] == '\n') return i;
-    return limit;
-}
-// bytes of [0, x) that are not '\n' (x <= n)
-__device__ u64 fi_nonnl_before(const FiBlocks& k, u64 x)
-{
-    const u64 b = x / VT_BLOCK;
-    u64 c = k.nnpre[b];
-    for (u64 i = b * VT_BLOCK; i < x; i++) c += k.f[i] != '\n';
-    return c;
-}
 static __global__ void k_fi_records(FiBlocks k, const u64* __restrict__ hstart, u64 nhdr, ContigRec* __restrict__ out)
 {
-    for (u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x; r < nhdr; r += (u64)gridDim.x * blockDim.x) {
-        const u64 rs = hstart[r], re = r + 1 < nhdr ? hstart[r + 1] : k.n;
-        const u64 hl = fi_next_newline(k, rs, re);                          // end of the header line
-        u64 ne = rs + 1;
-        while (ne < hl && k.f[ne] != ' ') ne++;
-        const u64 ss = hl < re ? hl + 1 : re;
-        ContigRec c;
-        c.name_off = rs + 1; c.name_len = ne - (rs + 1);
-        c.rec_start = rs; c.rec_end = re;
-        c.seq_start = ss; c.line_width = fi_next_newline(k, ss, re) - ss;
-        c.seq_size = fi_nonnl_before(k, re) - fi_nonnl_before(k, ss);
-        c.vcf_records = 0; c.duplicate = 0;
-        out[r] = c;
-    }
+    fi_records_body(k, hstart, nhdr, out, WALK_THREAD);
 }
 
 // ---- contig of every record line ---------------------------------------------------------------------------
-// names: the records that are not duplicates, sorted by the FNV-1a hash of their name
-struct VcTable { const u64* hash; const u32* rec; u32 T; const ContigRec* recs; const uint8_t* fasta; u64 nrecs; };
-struct VcCtl { u64 n, total, undecidable, oob; };
-
 static __global__ void k_vc_classify(const uint8_t* __restrict__ raw, u64 n, const u64* __restrict__ lstart, u64 nrec, VcTable t,
                                      u64* __restrict__ keys, VcCtl* ctl)
 {
-    bool und = false;
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
-        ByteWindow win(raw, n);
-        const u64 lo = lstart[j];
-        u64 i = lo, h = FNV_OFFSET;
-        bool ws = false;
-        for (; i < n; i++) {
-            const uint8_t ch = win[i];
-            if (ch == '\t' || ch == '\n') break;
-            ws |= ch == ' ' || ch == '\r' || ch == '\v' || ch == '\f';
-            h = (h ^ ch) * FNV_PRIME;
-        }
-        const u64 len = i - lo;
-        u64 key = t.nrecs;                                                  // no such contig
-        if (len == 0 || ws) und = true;                                     // tab rule and whitespace rule may differ: host
-        else {
-            u32 a = 0, b = t.T;
-            while (a < b) { const u32 m = a + (b - a) / 2; if (t.hash[m] < h) a = m + 1; else b = m; }
-            for (; a < t.T && t.hash[a] == h && key == t.nrecs; a++) {      // the hash finds, the bytes decide
-                const ContigRec& c = t.recs[t.rec[a]];
-                if (c.name_len != len) continue;
-                bool eq = true;
-                for (u64 x = 0; x < len && eq; x++) eq = win[lo + x] == t.fasta[c.name_off + x];
-                if (eq) key = t.rec[a];
-            }
-        }
-        if (win.oob) ctl->oob = win.oob;
-        keys[j] = key;
-    }
-    if (und) ctl->undecidable = 1;
+    vc_classify_body<~0ull>(raw, n, lstart, nrec, t, keys, ctl, WALK_THREAD);
 }
-// line starts in regrouped order, and the first line of every contig that has one (first[] is preset to ~0)
 static __global__ void k_vc_regroup(const u64* __restrict__ keys, const u32* __restrict__ order, const u64* __restrict__ lstart, u64 nrec,
                                     u64* __restrict__ lsorted, u64* __restrict__ first)
 {
-    for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < nrec; j += (u64)gridDim.x * blockDim.x) {
-        lsorted[j] = lstart[order[j]];
-        if (j == 0 || keys[j] != keys[j - 1]) first[keys[j]] = j;
-    }
+    vc_regroup_body(keys, order, lstart, nrec, lsorted, first, WALK_THREAD);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-namespace {
-
-u64 fnv1a(const uint8_t* p, size_t n)
-{
-    u64 h = FNV_OFFSET;
-    for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * FNV_PRIME;
-    return h;
-}
-
-// first token of a record line [p, p + n): the first maximal run of bytes that are not whitespace
-bool first_token(const uint8_t* p, size_t n, size_t& lo, size_t& len)
-{
-    size_t i = 0;
-    while (i < n && host_isspace(p[i])) i++;
-    size_t j = i;
-    while (j < n && !host_isspace(p[j])) j++;
-    lo = i; len = j - i;
-    return j > i;
-}
-
-} // namespace
-
 VcfSession::VcfSession(GzText& vcf, GzText& fasta, bool own, bool ignore_chrom) : vcf_(nullptr), vcf_n_(0), fasta_(nullptr), fasta_n_(0)
 {
     static const uint8_t none = 0;
@@ -240,13 +115,13 @@ void VcfSession::index_fasta(hipStream_t st)
     if (n) fetch_fasta(0, 1, &first);
     if (n == 0 || first != '>') throw FormatError("Invalid FASTA format: expected header line starting with '>'");
     if (!fasta_resident_) {
-        d_fasta_.ensure(n + 16);
+        d_fasta_.ensure(contig_size::fasta(n));
         EDSX_HIP(hipMemcpyAsync(d_fasta_.ptr, fasta_, n, hipMemcpyHostToDevice, st));
         fasta_h2d += n;
     }
-    const u64 nblk = (n + VT_BLOCK - 1) / VT_BLOCK;
+    const u64 nblk = contig_size::blocks(n);
     DevBuf hdr, nonnl, tmp, ctl, hstart;
-    hdr.ensure(8 * (nblk + 2)); nonnl.ensure(8 * (nblk + 2)); tmp.ensure(8 * ((nblk + 2) / SCAN_TILE + 4)); ctl.ensure(8 * 8);
+    hdr.ensure(contig_size::block_counts(nblk)); nonnl.ensure(contig_size::block_counts(nblk)); tmp.ensure(8 * ((nblk + 2) / SCAN_TILE + 4)); ctl.ensure(8 * 8);
     struct FiCtl { u64 n, nhdr; };                                           // the header scan's element count and total
     FiCtl hctl{nblk, 0};
     FiCtl* dctl = ctl.as<FiCtl>();
@@ -260,8 +135,8 @@ void VcfSession::index_fasta(hipStream_t st)
     EDSX_HIP(hipStreamSynchronize(st));
     const u64 nhdr = hctl.nhdr;                                             // >= 1: byte 0 is a '>'
     if (nhdr == 0 || nhdr >= 0xffffffffull) throw DeviceError("FASTA record index: " + std::to_string(nhdr) + " records");
-    hstart.ensure(8 * (nhdr + 1));
-    d_recs_.ensure(sizeof(ContigRec) * (nhdr + 1));
+    hstart.ensure(contig_size::hstart(nhdr));
+    d_recs_.ensure(contig_size::records(nhdr));
     hipLaunchKernelGGL(k_fi_fill, dim3(2048), dim3(256), 0, st, f, n, hdr.as<u64>(), nhdr, hstart.as<u64>());
     hipLaunchKernelGGL(k_fi_records, dim3((unsigned)std::min<u64>((nhdr + 255) / 256, 1024)), dim3(256), 0, st, FiBlocks{f, n, nonnl.as<u64>(), nblk},
                        hstart.as<u64>(), nhdr, d_recs_.as<ContigRec>());
@@ -277,9 +152,8 @@ void VcfSession::index_fasta(hipStream_t st)
             throw DeviceError("FASTA record index: record " + std::to_string(r) + " out of bounds");
         names_[r].resize(c.name_len);
         if (c.name_len) fetch_fasta(c.name_off, c.name_len, &names_[r][0]);
-        const bool fresh = by_name_.emplace(names_[r], r).second;
-        c.duplicate = fresh ? 0 : 1;
     }
+    mark_duplicates(names_, recs_, by_name_);
 }
 
 bool VcfSession::classify_device(hipStream_t st)
@@ -287,7 +161,7 @@ bool VcfSession::classify_device(hipStream_t st)
     { const char* e = getenv("EDSX_HOST_TOKENIZER"); if (e && atoi(e)) return false; }
     const u64 n = vcf_n_;
     if (!device_scratch_fits(6 * n)) return false;
-    d_vcf_.ensure(vcf_size::text(n));
+    d_vcf_.ensure(contig_size::vcf(n));
     DevBuf idx, tmp, ctlb, lstart, keys, keys2, ord1, ord2, table, first, thash, trec;
     struct ClassifyCtl { VtCtl vt; VcCtl vc; };                             // the line-start step's and the classification's
     ctlb.ensure(8 * 32);
@@ -316,21 +190,16 @@ bool VcfSession::classify_device(hipStream_t st)
     }
 
     // name table: one entry per distinct name, sorted by hash
-    std::vector<std::pair<u64, u32>> tab;
-    tab.reserve(by_name_.size());
-    for (size_t r = 0; r < K; r++)
-        if (!recs_[r].duplicate) tab.push_back({fnv1a(reinterpret_cast<const uint8_t*>(names_[r].data()), names_[r].size()), (u32)r});
-    std::sort(tab.begin(), tab.end());
-    std::vector<u64> hh(tab.size());
-    std::vector<u32> hr(tab.size());
-    for (size_t i = 0; i < tab.size(); i++) { hh[i] = tab[i].first; hr[i] = tab[i].second; }
-    thash.ensure(8 * (tab.size() + 1)); trec.ensure(4 * (tab.size() + 1));
+    std::vector<u64> hh;
+    std::vector<u32> hr;
+    name_table(recs_, names_, hh, hr);
+    thash.ensure(contig_size::table_hash(hh.size())); trec.ensure(contig_size::table_rec(hr.size()));
     EDSX_HIP(hipMemcpyAsync(thash.ptr, hh.data(), 8 * hh.size(), hipMemcpyHostToDevice, st));
     EDSX_HIP(hipMemcpyAsync(trec.ptr, hr.data(), 4 * hr.size(), hipMemcpyHostToDevice, st));
     VcCtl vz{};
     EDSX_HIP(hipMemcpyAsync(vctl, &vz, sizeof(vz), hipMemcpyHostToDevice, st));
-    keys.ensure(8 * (nr + 2));
-    const VcTable t{thash.as<u64>(), trec.as<u32>(), (u32)tab.size(), d_recs_.as<ContigRec>(), d_fasta_.as<uint8_t>(), K};
+    keys.ensure(contig_size::keys(nr));
+    const VcTable t{thash.as<u64>(), trec.as<u32>(), (u32)hh.size(), d_recs_.as<ContigRec>(), d_fasta_.as<uint8_t>(), K};
     TraceSpan cls(st, "contig classification", n);
     hipLaunchKernelGGL(k_vc_classify, dim3(2048), dim3(256), 0, st, raw, n, lstart.as<u64>(), nr, t, keys.as<u64>(), vctl);
     cls.end();
@@ -341,15 +210,14 @@ bool VcfSession::classify_device(hipStream_t st)
     if (vz.undecidable) return false;
 
     // stable regrouping by record index (K = no such contig, last): one 8-bit pass per byte of K
-    u32 passes = 1;
-    while (passes < 4 && (K >> (8 * passes))) passes++;
+    const u32 passes = radix_passes(K);
     const u64 ntiles = (nr + RS_TILE - 1) / RS_TILE, nbins = 256 * ntiles;
-    keys2.ensure(8 * (nr + 2)); ord1.ensure(4 * (nr + 2)); ord2.ensure(4 * (nr + 2)); table.ensure(8 * (nbins + 2));
+    keys2.ensure(contig_size::keys(nr)); ord1.ensure(contig_size::order(nr)); ord2.ensure(contig_size::order(nr)); table.ensure(8 * (nbins + 2));
     tmp.ensure(8 * (nbins / SCAN_TILE + 4));
-    first.ensure(8 * (K + 2));
-    lsorted_.ensure(8 * (nr + 2));
+    first.ensure(contig_size::first(K));
+    lsorted_.ensure(contig_size::keys(nr));
     EDSX_HIP(hipMemcpyAsync(&vctl->n, &nbins, 8, hipMemcpyHostToDevice, st));
-    EDSX_HIP(hipMemsetAsync(first.ptr, 0xff, 8 * (K + 2), st));
+    EDSX_HIP(hipMemsetAsync(first.ptr, 0xff, contig_size::first(K), st));
     const unsigned grid = (unsigned)std::min<u64>(ntiles, 1u << 16);
     TraceSpan srt(st, "regrouping (radix sort)", 0);
     // keys -> (keys2, ord1) -> (keys, ord2) -> (keys2, ord1) ...
@@ -369,30 +237,19 @@ bool VcfSession::classify_device(hipStream_t st)
     EDSX_HIP(hipStreamSynchronize(st));
     EDSX_HIP(hipGetLastError());
     // counts: a contig's lines end where the next contig that has lines begins
-    u64 next = nr;
-    for (size_t r = K + 1; r-- > 0;) {
-        if (first_[r] == ~0ull) continue;
-        if (first_[r] >= next) throw DeviceError("contig regrouping: first lines out of order");
-        const u64 cnt = next - first_[r];
-        if (r < K) recs_[r].vcf_records = cnt; else records_unknown = cnt;
-        next = first_[r];
-    }
-    if (next != 0) throw DeviceError("contig regrouping: lines without a contig");
+    contig_counts(first_, nr, recs_, records_unknown);
     records_total = nr;
     if (records_unknown) {                                                   // their names, for the caller's warnings
         std::vector<u64> ls(records_unknown);
         EDSX_HIP(hipMemcpy(ls.data(), lsorted_.as<u64>() + first_[K], 8 * records_unknown, hipMemcpyDeviceToHost));
-        std::unordered_map<std::string, size_t> at;
-        std::vector<std::pair<std::string, u64>> names;
+        UnknownNames un;
         const uint8_t* hv = host_vcf();
         for (u64 lo : ls) {
             size_t e = lo;
             while (e < n && hv[e] != '\t' && hv[e] != '\n') e++;
-            const auto ins = at.emplace(std::string(reinterpret_cast<const char*>(hv + lo), e - lo), names.size());
-            if (ins.second) names.push_back({ins.first->first, 0});
-            names[ins.first->second].second++;
+            un.add(std::string(reinterpret_cast<const char*>(hv + lo), e - lo));
         }
-        for (const auto& nm : names) unknown_text_ += nm.first + "\t" + std::to_string(nm.second) + "\n";
+        unknown_text_ = un.text();
     }
     return true;
 }
@@ -401,34 +258,9 @@ void VcfSession::classify_host()
 {
     host_vcf();
     if (ignore_chrom_) return;                                               // (the whole text is record 0's)
-    for (ContigRec& c : recs_) c.vcf_records = 0;
-    records_total = records_without_token = records_unknown = 0;
-    unknown_text_.clear();
-    std::unordered_map<std::string, size_t> at;
-    std::vector<std::pair<std::string, u64>> names;
-    std::string key;
-    for (size_t pos = 0; pos < vcf_n_;) {
-        const uint8_t* nl = static_cast<const uint8_t*>(memchr(vcf_ + pos, '\n', vcf_n_ - pos));
-        const size_t end = nl ? static_cast<size_t>(nl - vcf_) : vcf_n_;
-        if (end > pos && vcf_[pos] != '#') {
-            records_total++;
-            size_t lo, len;
-            if (!first_token(vcf_ + pos, end - pos, lo, len)) records_without_token++;
-            else {
-                key.assign(reinterpret_cast<const char*>(vcf_ + pos + lo), len);
-                const auto it = by_name_.find(key);
-                if (it != by_name_.end()) recs_[it->second].vcf_records++;
-                else {
-                    records_unknown++;
-                    const auto ins = at.emplace(key, names.size());
-                    if (ins.second) names.push_back({key, 0});
-                    names[ins.first->second].second++;
-                }
-            }
-        }
-        pos = nl ? end + 1 : vcf_n_;
-    }
-    for (const auto& nm : names) unknown_text_ += nm.first + "\t" + std::to_string(nm.second) + "\n";
+    const HostClassified h = classify_lines_host(vcf_, vcf_n_, by_name_, recs_);
+    records_total = h.total; records_without_token = h.without_token; records_unknown = h.unknown;
+    unknown_text_ = h.unknown_text;
 }
 
 void VcfSession::open(hipStream_t st)
@@ -456,22 +288,8 @@ bool VcfSession::find(const std::string& name, size_t& index) const
 // V_c: every line that is empty, starts with '#', or is a record line whose first token is the record's name
 void VcfSession::host_text_of(size_t index, std::vector<uint8_t>& out)
 {
-    const ContigRec& c = recs_[index];
-    const uint8_t* name = reinterpret_cast<const uint8_t*>(names_[index].data());
     host_vcf();
-    out.clear();
-    for (size_t pos = 0; pos < vcf_n_;) {
-        const uint8_t* nl = static_cast<const uint8_t*>(memchr(vcf_ + pos, '\n', vcf_n_ - pos));
-        const size_t end = nl ? static_cast<size_t>(nl - vcf_) : vcf_n_;
-        bool keep = end == pos || vcf_[pos] == '#';
-        if (!keep) {
-            size_t lo, len;
-            keep = first_token(vcf_ + pos, end - pos, lo, len) && len == c.name_len && memcmp(vcf_ + pos + lo, name, len) == 0;
-        }
-        const size_t upto = nl ? end + 1 : vcf_n_;
-        if (keep) out.insert(out.end(), vcf_ + pos, vcf_ + upto);
-        pos = upto;
-    }
+    contig_text_of(vcf_, vcf_n_, reinterpret_cast<const uint8_t*>(names_[index].data()), recs_[index].name_len, out);
 }
 
 void VcfSession::transform(VcfPipeline& pipe, size_t index, HostBytes& eds, HostBytes& seds, VcfCounters& stats, hipStream_t st)

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "bgzf_device.hpp"
+#include "vcf_contig_walk.hpp"
 #include "vcf_device.hpp"
 
 #include <string>
@@ -12,15 +13,7 @@
 
 namespace edsx {
 
-// one FASTA record (the layout of edsx_contig, include/edsx.h)
-struct ContigRec {
-    u64 name_off, name_len;        // name bytes inside the FASTA: behind '>' up to the first ' ' or the end of the header line
-    u64 rec_start, rec_end;        // the record: from its '>' up to the next '>' at a line start (or the end of the file)
-    u64 seq_start, line_width;     // first sequence line (vcf_transforms.cpp:59-67); seq_start == rec_end: no such line
-    u64 seq_size;                  // bytes of [seq_start, rec_end) that are not '\n' (:69-84)
-    u64 vcf_records;               // record lines of the VCF whose first token is this name
-    u64 duplicate;                 // 1: an earlier record has the same name
-};
+// ContigRec, one FASTA record: vcf_contig_walk.hpp
 
 class VcfSession {
 public:

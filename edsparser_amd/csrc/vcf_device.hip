@@ -33,13 +33,7 @@ namespace edsx {
 
 // VcfDev, fa_cpos and the bodies of the thread-per-item kernels below: vcf_walk.hpp
 
-struct WalkGrid {                                            // the grid of a thread-per-item kernel, as its body asks for it
-    u32 bi, bd, ti, gd;                                      // (read in the kernel itself; the products are taken where the body uses them)
-    __device__ __forceinline__ u64 first() const { return bi * (u64)bd + ti; }
-    __device__ __forceinline__ u64 stride() const { return (u64)gd * bd; }
-    __device__ __forceinline__ bool lead() const { return bi == 0 && ti == 0; }
-};
-#define WALK_THREAD WalkGrid{blockIdx.x, blockDim.x, threadIdx.x, gridDim.x}      /* last argument of every body */
+// WalkGrid / WALK_THREAD, the grid argument of those bodies: vcf_text_kernels.hpp
 
 // ---- reference stream ---------------------------------------------------------------------------
 __global__ void k_fa_count(const uint8_t* __restrict__ f, u64 n, u64 seq_start, u64* __restrict__ blkcnt, u64 nblk)

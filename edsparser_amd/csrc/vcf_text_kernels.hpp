@@ -8,6 +8,14 @@
 
 namespace edsx {
 
+struct WalkGrid {                                            // the grid of a thread-per-item kernel, as its body asks for it
+    u32 bi, bd, ti, gd;                                      // (read in the kernel itself; the products are taken where the body uses them)
+    __device__ __forceinline__ u64 first() const { return bi * (u64)bd + ti; }
+    __device__ __forceinline__ u64 stride() const { return (u64)gd * bd; }
+    __device__ __forceinline__ bool lead() const { return bi == 0 && ti == 0; }
+};
+#define WALK_THREAD WalkGrid{blockIdx.x, blockDim.x, threadIdx.x, gridDim.x}      /* last argument of every body */
+
 // VtCtl, ByteWindow (the text through 8-byte aligned loads), VT_BLOCK and vt_line_start_mask: vcf_walk.hpp, which the
 // host twin compiles too.  A wave owns VT_BLOCK bytes of the text (16 per lane); pass 1 counts the line starts of every
 // such block, a scan over the block counts numbers them, pass 2 finds them again and writes their positions.

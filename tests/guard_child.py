@@ -461,6 +461,42 @@ def multi_rank_one_device():
     g.finish("multi_rank_one_device", 3)
 
 
+# ---- contig selection: the inputs whose subject is where a byte falls (tests/contig_walk_cases.py) ----------------------------
+
+def contig_edges():
+    import contig_walk_cases as cw
+    import contig_walk_expect as cx
+    g = Guard()
+    fam = cw.families()
+    shifts = fam["shift"][::len(fam["shift"]) // 12][:12]                 # a dozen values of p, spread over the sweep
+    cases = shifts + fam["ends"] + fam["walks"] + [c for c in fam["counts"] if c["name"] == "counts/K256"]
+    assert len(shifts) == 12 and len(cases) == 12 + len(fam["ends"]) + len(fam["walks"]) + 1
+
+    def session(case):
+        def call(ctx):
+            with ctx.vcf_session(case["V"], case["F"]) as ses:
+                info = ses.info()
+                recs = [tuple(r[f] for f in cw.REC_FIELDS) for r in ses.contigs()]
+                texts = []
+                for nm in case["pick"]:
+                    try:
+                        e, s, st = ses.transform(nm, 0)
+                        texts.append({"eds": e, "seds": s, "stats": st})
+                    except edsparser_amd.EdsxError as ex:
+                        texts.append({"error": ex.message})
+                return (recs, info["classified_on_device"], info["records_total"], info["records_without_token"], info["records_unknown_contig"],
+                        ses.unknown_contigs(), texts)
+        return call
+
+    for case in cases:
+        e = cx.expected(case)
+        recs = [tuple(int(v) for v in e["recs"][i]) + (int(e["counts"][i]), int(e["duplicate"][i])) for i in range(e["K"])]
+        want = (recs, 0 if e["host"] else 1, e["nr"], e["without_token"], e["unknown"], e["unknown_names"],
+                [cx.expected_texts(case, nm) for nm in case["pick"]])
+        g.case(case["name"], session(case), want, VCF_FILLS + (ord(">"),))
+    g.finish("contig_edges", len(cases))
+
+
 if __name__ == "__main__":
     {"selftest": selftest, "msa": msa, "vcf": vcf, "merge": merge, "eds_consumers": eds_consumers,
-     "multi_rank_one_device": multi_rank_one_device}[sys.argv[1]]()
+     "multi_rank_one_device": multi_rank_one_device, "contig_edges": contig_edges}[sys.argv[1]]()

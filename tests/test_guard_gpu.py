@@ -58,3 +58,9 @@ def test_guard_eds_consumers():
 
 def test_guard_multi_rank_one_device():
     _child("multi_rank_one_device", 3)
+
+
+def test_guard_contig_edges():
+    """the FASTA index and the classification at lane, block and buffer ends (tests/contig_walk_cases.py): a dozen shifts
+    of the sweep, the ends, the long walks and K = 256"""
+    _child("contig_edges", 69)
