@@ -91,6 +91,10 @@ class AlignInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("n_symbols", "n_columns", "n_zero_width_symbols", "widest_symbol", "num_paths")]
 
 
+class DistInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("units", "variable_units", "class_columns", "chunk_columns", "chunks")]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -287,6 +291,9 @@ def load_library():
     lib.edsx_paths_slice.argtypes = [V, ctypes.c_size_t, V, V, V, ctypes.c_uint64, P(_Buf), P(_Buf), V, V]
     lib.edsx_eds_slice.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, V, V, V,
                                    ctypes.c_uint64, P(_Buf), P(_Buf), V, V]
+    lib.edsx_paths_distances.argtypes = [V, V, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, V, V, P(DistInfo)]
+    lib.edsx_eds_distances.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t,
+                                       ctypes.c_int, ctypes.c_uint64, V, V, P(DistInfo)]
     _LIB = lib
     return lib
 
@@ -300,6 +307,19 @@ LIFT_SAME, LIFT_ALIGNED, LIFT_GAP, LIFT_MISSING, LIFT_RANGE = 0, 1, 2, 3, 4
 SLICE_REGION = [(f, "<u8") for f in ("symbol_first", "symbol_last", "cut_first", "cut_end", "column_first", "column_end", "strings",
                                      "chars", "eds_off", "eds_len", "seds_off", "seds_len")]
 SLICE_RANGE = 4
+
+
+# the metrics of the path distances (EDSX_DIST_*)
+DIST_METRICS = {"columns": 0, "strings": 1}
+
+
+def _metric(metric):
+    """The metric parameter of the distance calls as the C int: a name of DIST_METRICS, or the number itself."""
+    if isinstance(metric, str):
+        if metric not in DIST_METRICS:
+            raise ValueError("the metric is one of %s" % ", ".join(sorted(DIST_METRICS)))
+        return DIST_METRICS[metric]
+    return int(metric)
 
 
 def _slice_regions(reg, st):
@@ -706,6 +726,26 @@ class Context(_Handle):
                                              int(max_bytes), ctypes.byref(e), ctypes.byref(q), reg.ctypes.data, st.ctypes.data))
         return self._take(e), self._take(q), _slice_regions(reg, st)
 
+    # ---- path distances (edsparser-dist)
+    def eds_distances(self, eds, seds, paths=None, metric="columns", max_bytes=0):
+        """One-shot edsx_eds_distances: PathSession.distances on a session opened and closed for this call."""
+        import numpy as np
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        ids = np.ascontiguousarray([] if paths is None else list(paths), dtype=np.uint64)
+        K = len(ids)
+        if K == 0:                                                # all paths: P x P, learnt from the text
+            K = max([int(x) for x in _re_ids(sb)] + [0]) if sb else 0
+        if max_bytes and 8 * K * K > max_bytes:                   # refused by the library before it writes: no matrix needed
+            mat = np.zeros((0, 0), dtype=np.uint64)
+        else:
+            mat = np.zeros((K, K), dtype=np.uint64)
+        miss, info = np.zeros(max(K, 1), dtype=np.uint64), DistInfo()
+        self._check(self._lib.edsx_eds_distances(self._h, eds, len(eds), sb, sn, ids.ctypes.data if len(ids) else None, len(ids),
+                                                 _metric(metric), int(max_bytes), mat.ctypes.data if mat.size else None,
+                                                 miss.ctypes.data, ctypes.byref(info)))
+        return mat, miss[:K], _fields(info)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -1067,6 +1107,26 @@ class PathSession(_Handle):
         self._ctx._check(self._lib.edsx_paths_slice(self._h, n, path.ctypes.data, start.ctypes.data, end.ctypes.data, int(max_bytes),
                                                     ctypes.byref(e), ctypes.byref(q), reg.ctypes.data, st.ctypes.data))
         return self._ctx._take(e), self._ctx._take(q), _slice_regions(reg, st)
+
+    def distances(self, paths=None, metric="columns", max_bytes=0):
+        """(matrix, missing, info): the pairwise distances of the requested paths in request order (None or empty: all paths
+        1..P; duplicates allowed) as a numpy uint64 (K, K) array, symmetric with a zero diagonal, the missing counts and
+        the info dict of edsx_dist_info (edsx_paths_distances).  metric "columns": the columns of the alignment of align()
+        at which two rows differ, "no character" being a value of its own; "strings": the symbols at which two paths
+        take different strings.  info["units"] is the denominator of a normalised distance.  max_bytes (0: none):
+        EdsxError when the matrix is larger."""
+        import numpy as np
+        ids = np.ascontiguousarray([] if paths is None else list(paths), dtype=np.uint64)
+        K = len(ids) if len(ids) else self.info["num_paths"]
+        if max_bytes and 8 * K * K > max_bytes:                   # refused by the library before it writes: no matrix needed
+            mat = np.zeros((0, 0), dtype=np.uint64)
+        else:
+            mat = np.zeros((K, K), dtype=np.uint64)
+        miss, info = np.zeros(max(K, 1), dtype=np.uint64), DistInfo()
+        self._ctx._check(self._lib.edsx_paths_distances(self._h, ids.ctypes.data if len(ids) else None, len(ids), _metric(metric),
+                                                        int(max_bytes), mat.ctypes.data if mat.size else None, miss.ctypes.data,
+                                                        ctypes.byref(info)))
+        return mat, miss[:K], _fields(info)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

@@ -53,6 +53,7 @@ struct edsx_ctx {
     GfaPipeline gfa;                         // edsx_eds_gfa_graph
     VcfExportPipeline vcf_export;            // edsx_eds_vcf
     KernelTimes slice_times;                 // edsx_paths_slice, of every session of this context
+    KernelTimes dist_times;                  // edsx_paths_distances, likewise
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -420,6 +421,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->gfa.set_timing(enabled != 0);
     ctx->vcf_export.set_timing(enabled != 0);
     ctx->slice_times.set(enabled != 0);
+    ctx->dist_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -428,7 +430,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     n += ctx->subset.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1166,6 +1169,45 @@ int edsx_eds_slice(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uin
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_slice(s, n, path, start, end, max_bytes, eds_out, seds_out, region, status); });
+}
+
+// ---- edsparser-dist (dist_device.hip, dist_core.hpp)
+static_assert(sizeof(DistInfo) == sizeof(edsx_dist_info) && offsetof(DistInfo, chunks) == offsetof(edsx_dist_info, chunks),
+              "edsx_dist_info is DistInfo");
+static_assert(EDSX_DIST_COLUMNS == dist::COLUMNS && EDSX_DIST_STRINGS == dist::STRINGS, "EDSX_DIST_*");
+
+int edsx_paths_distances(edsx_paths_session* s, const uint64_t* ids, size_t n, int metric, uint64_t max_bytes, uint64_t* matrix,
+                         uint64_t* missing, edsx_dist_info* info)
+{
+    zero(info);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (n && !ids) throw ParamError("null argument");
+        std::vector<u64> all;
+        if (n == 0) {                                            // every path
+            all.resize(s->p.info().num_paths);
+            for (size_t k = 0; k < all.size(); k++) all[k] = k + 1;
+        }
+        const size_t K = n ? n : all.size();
+        DistInfo di;                                             // (a null matrix: refused behind the limit check, which needs none)
+        try {
+            s->p.distances(n ? reinterpret_cast<const u64*>(ids) : all.data(), K, metric, max_bytes, reinterpret_cast<u64*>(matrix),
+                           reinterpret_cast<u64*>(missing), di, &s->ctx->dist_times, nullptr);
+        } catch (const LimitError&) {                            // the budget: the geometry is known
+            if (info) std::memcpy(info, &di, sizeof(di));
+            throw;
+        }
+        if (info) std::memcpy(info, &di, sizeof(di));
+    });
+}
+
+int edsx_eds_distances(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                       size_t n, int metric, uint64_t max_bytes, uint64_t* matrix, uint64_t* missing, edsx_dist_info* info)
+{
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_distances(s, ids, n, metric, max_bytes, matrix, missing, info); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

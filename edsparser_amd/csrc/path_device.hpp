@@ -1,8 +1,10 @@
 // path_device.hpp — host driver of the path spelling kernels (see path_device.hip): the sequence of every path of an
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
-// The session's coordinate lift and region slice: lift_device.hip, slice_device.hip (where an operation goes).
+// The session's coordinate lift, region slice and path distances: lift_device.hip, slice_device.hip, dist_device.hip
+// (where an operation goes).
 #pragma once
 
+#include "dist_core.hpp"
 #include "eds_device.hpp"
 #include "kernel_times.hpp"
 #include "lift_core.hpp"
@@ -35,6 +37,9 @@ struct LiftColumns { const u64* symbol; const u64* string; const u64* offset; };
 
 // edsx_slice_region (include/edsx.h)
 struct SliceRegion { u64 symbol_first, symbol_last, cut_first, cut_end, column_first, column_end, strings, chars, eds_off, eds_len, seds_off, seds_len; };
+
+// edsx_dist_info (include/edsx.h)
+struct DistInfo { u64 units = 0, variable_units = 0, class_columns = 0, chunk_columns = 0, chunks = 0; };
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -80,6 +85,14 @@ public:
     void slice(size_t n, const u64* path, const u64* start, const u64* end, u64 max_bytes, HostBytes& eds_out, HostBytes& seds_out,
                SliceRegion* region, uint8_t* status, KernelTimes* times, hipStream_t st);
 
+    // Pairwise distances between n paths in request order, duplicates allowed (dist_core.hpp, dist_device.hip):
+    // matrix has n x n entries, row-major; missing (nullable) n.  metric: dist::COLUMNS - the columns of the alignment of
+    // align() at which two rows differ - or dist::STRINGS - the symbols at which two paths take different strings; anything
+    // else is a ParamError, and so is a matrix above max_bytes (0: none), found before anything is allocated.  The bit
+    // rows and the matrix have to fit budget(2): LimitError.
+    void distances(const u64* ids, size_t n, int metric, u64 max_bytes, u64* matrix, u64* missing, DistInfo& info, KernelTimes* times,
+                   hipStream_t st);
+
 private:
     // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
     // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
@@ -94,6 +107,13 @@ private:
     // as given (in), the sites of their ends, the regions resolved (reg, st), A per region (sum), the five scanned counts
     // (scan), the destinations of the edge strings (edst) and both texts
     struct SliceState { bool ready = false; DevBuf sb, symof, in, site, sst, reg, st, sum, scan, edst, eds, seds; };
+
+    // distances: per choice symbol whether it may leave a path without a string (may_miss, nc bytes) and its first column
+    // among the columns of the choice symbols (ccol, nc + 1; CW of them); per metric, from its first call, the class list
+    // (desc: one descriptor per class column, C of them, over V listed units); per call the classes per unit while they
+    // are counted (cnt), the bit rows of all requested paths (rows) and the K x K sums that become the matrix (sums)
+    struct DistClasses { bool ready = false; u64 V = 0, C = 0; DevBuf desc; };
+    struct DistState { bool ready = false; u64 CW = 0; DevBuf may_miss, ccol, cnt, rows, sums; DistClasses cls[2]; };
 
     // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
@@ -121,6 +141,10 @@ private:
                   u64* dst_pos, uint8_t* status, LiftSite* dev_site, uint8_t* dev_status, hipStream_t st);
     // ---- slice (slice_device.hip): made by the first slice() of a session
     void slice_open(hipStream_t st);
+    // ---- distances (dist_device.hip): the symbol tables by the first distances() of a session, a class list by the first
+    // of its metric
+    void dist_open(hipStream_t st);
+    void dist_classes(dist::Metric metric, TimedRuns& timed, hipStream_t st);
 
     DeviceEds eds_;
     PathInfo info_;
@@ -131,6 +155,7 @@ private:
     AlignState align_;
     LiftState lift_;
     SliceState slice_;
+    DistState dist_;
 };
 
 } // namespace edsx

@@ -116,6 +116,31 @@ std::vector<LiftResult> lift_positions(std::istream& eds_in, std::istream& seds_
     return res;
 }
 
+PathDistances path_distances(std::istream& eds_in, std::istream& seds_in, const std::vector<int>& paths, DistanceMetric metric)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    edsx_ctx* ctx = detail::context();
+    edsx_paths_session* s = nullptr;
+    int rc = edsx_paths_open(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(),
+                             reinterpret_cast<const uint8_t*>(seds.data()), seds.size(), &s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    edsx_paths_info_t pi;
+    edsx_paths_info(s, &pi);
+    PathDistances d;
+    d.K = ids.empty() ? pi.num_paths : ids.size();
+    std::vector<uint64_t> miss(d.K);
+    edsx_dist_info di;
+    try { d.matrix.resize(d.K * d.K); } catch (...) { edsx_paths_close(s); throw; }
+    rc = edsx_paths_distances(s, ids.data(), ids.size(), static_cast<int>(metric), 0, d.matrix.data(), miss.data(), &di);
+    edsx_paths_close(s);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    d.units = di.units; d.variable_units = di.variable_units; d.class_columns = di.class_columns;
+    d.missing.assign(miss.begin(), miss.end());
+    return d;
+}
+
 void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
 {

@@ -63,6 +63,22 @@ struct LiftResult {
 };
 std::vector<LiftResult> lift_positions(std::istream& eds, std::istream& seds, const std::vector<LiftQuery>& queries);
 
+// edsparser-dist: the pairwise distances of the given paths (empty: all paths 1..P; duplicates allowed), K x K row-major in
+// request order, symmetric with a zero diagonal.  COLUMNS: the columns of the alignment of eds_to_msa at which two rows
+// differ, where "no character" is a value of its own (there is no gap parameter); STRINGS: the symbols at which two paths
+// take different strings, compared as string indices (edsx_paths_distances states the rules in full).  `units` is the
+// denominator of a normalised distance: the columns of the alignment, or the number of symbols.
+// std::invalid_argument for a path outside 1..P.
+enum class DistanceMetric : int { COLUMNS = 0, STRINGS = 1 };
+struct PathDistances {
+    size_t K = 0, units = 0, variable_units = 0, class_columns = 0;
+    std::vector<uint64_t> matrix;              // K * K
+    std::vector<size_t> missing;               // per requested path
+    uint64_t at(size_t a, size_t b) const { return matrix[a * K + b]; }
+};
+PathDistances path_distances(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {},
+                             DistanceMetric metric = DistanceMetric::COLUMNS);
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

@@ -565,6 +565,43 @@ int edsx_eds_slice(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uin
                    const uint64_t* path, const uint64_t* start, const uint64_t* end, uint64_t max_bytes, edsx_buf* eds_out,
                    edsx_buf* seds_out, edsx_slice_region* region, uint8_t* status);
 
+/* ---- edsparser-dist: pairwise distances between the paths of an EDS with sources (dist_device.hip, dist_core.hpp) ----
+ * Input: a path session and K path ids in request order; duplicates are allowed; n == 0 means all paths 1..P.  An id of 0
+ * or above P is EDSX_ERR_INVALID_PARAMETER, "Path id <p> out of range (1..<P>)".
+ *   Chosen string.  chosen(p, i) is the session's rule: the first string of symbol i, in file order, whose source set holds
+ *      p or 0.  Otherwise it is none, and missing[p] counts those symbols.
+ *   Metric EDSX_DIST_COLUMNS.  D[a][b] is the number of columns of the edsx_paths_align alignment at which the rows of the
+ *      two paths differ.  Symbol i owns w[i] columns, where w[i] is the length of its longest string over all strings.  A
+ *      path shows its chosen string left-justified and no character elsewhere - everywhere in the symbol when it has none.
+ *      "No character" is a value of its own: it equals itself and differs from every byte; a '-' inside a string is an
+ *      ordinary byte, and the metric has no gap parameter.
+ *   Metric EDSX_DIST_STRINGS.  D[a][b] is the number of symbols i with chosen(a, i) != chosen(b, i), compared as string
+ *      indices.  Two none are equal.  Equal texts are not merged, the convention of eds2gfa and eds2vcf.
+ *   Any other metric is EDSX_ERR_INVALID_PARAMETER.
+ *   Output.  matrix: K x K uint64, row-major, in request order, allocated by the caller (for n == 0, K = P from
+ *      edsx_paths_info); it is symmetric and has a zero diagonal.  missing (may be NULL): K counts.  info (may be NULL):
+ *      units            W for COLUMNS, the number of symbols for STRINGS: the denominator of a normalised distance
+ *      variable_units   the units that got class columns (the others cannot tell two paths apart)
+ *      class_columns    the bits of a path's row: one per class of every variable unit
+ *      chunk_columns    class columns per chunk of the pair kernel
+ *      chunks           the number of chunks
+ *   Limits.  max_bytes (0: none) is held against 8 * K * K before anything is allocated: EDSX_ERR_INVALID_PARAMETER,
+ *      "Distance matrix has <n> bytes, above the limit of <max>".  The bit rows (K * ceil(class_columns / 64) * 8 bytes)
+ *      and the matrix must fit the session's budget: otherwise EDSX_ERR_BUILD_FAILED, with both sizes in the text and info
+ *      filled in.  An EDS without choice symbols gives a zero matrix, P = 0 an empty one.
+ * edsx_paths_last_timing: choose_ms the choice tables, scan_ms the class list (made by the first call per metric and kept
+ * with the session) and the tables' scan, copy_ms the bit rows, the pair kernel and the finish, bytes_written the matrix;
+ * under edsx_set_timing the kernels come back by name from edsx_get_timing. */
+#define EDSX_DIST_COLUMNS 0
+#define EDSX_DIST_STRINGS 1
+typedef struct { uint64_t units, variable_units, class_columns, chunk_columns, chunks; } edsx_dist_info;
+int edsx_paths_distances(edsx_paths_session* s, const uint64_t* ids, size_t n, int metric, uint64_t max_bytes, uint64_t* matrix,
+                         uint64_t* missing, edsx_dist_info* info);
+/* open + distances + close (n == 0: the caller learns P, and so the size of matrix, from the .seds or a session) */
+int edsx_eds_distances(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                       const uint64_t* ids, size_t n, int metric, uint64_t max_bytes, uint64_t* matrix, uint64_t* missing,
+                       edsx_dist_info* info);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
