@@ -95,6 +95,16 @@ class DistInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("units", "variable_units", "class_columns", "chunk_columns", "chunks")]
 
 
+class LdInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("paths", "choice_symbols", "alleles", "candidate_pairs", "undefined_pairs", "pairs",
+                                                "row_words", "tiles")]
+
+
+class LdOpts(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_uint64), ("min_r2", ctypes.c_double), ("min_count", ctypes.c_uint64), ("all_strings", ctypes.c_int),
+                ("max_pairs", ctypes.c_uint64)]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -294,6 +304,9 @@ def load_library():
     lib.edsx_paths_distances.argtypes = [V, V, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, V, V, P(DistInfo)]
     lib.edsx_eds_distances.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t,
                                        ctypes.c_int, ctypes.c_uint64, V, V, P(DistInfo)]
+    lib.edsx_paths_ld.argtypes = [V, V, ctypes.c_size_t, P(LdOpts), P(_Buf), P(_Buf), P(LdInfo)]
+    lib.edsx_eds_ld.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, P(LdOpts),
+                                P(_Buf), P(_Buf), P(LdInfo)]
     _LIB = lib
     return lib
 
@@ -307,6 +320,27 @@ LIFT_SAME, LIFT_ALIGNED, LIFT_GAP, LIFT_MISSING, LIFT_RANGE = 0, 1, 2, 3, 4
 SLICE_REGION = [(f, "<u8") for f in ("symbol_first", "symbol_last", "cut_first", "cut_end", "column_first", "column_end", "strings",
                                      "chars", "eds_off", "eds_len", "seds_off", "seds_len")]
 SLICE_RANGE = 4
+
+
+# edsx_ld_pair and edsx_ld_allele as numpy structured types
+LD_PAIR = [(f, "<u8") for f in ("symbol_a", "string_a", "symbol_b", "string_b", "n_ab", "n_a", "n_b", "n")] + [("r2", "<f8")]
+LD_ALLELE = [(f, "<u8") for f in ("symbol", "string", "count", "present")]
+
+
+def _ld_call(ctx, fn, head, paths, window, min_r2, min_count, all_strings, max_pairs):
+    """edsx_paths_ld / edsx_eds_ld behind their leading arguments -> (pairs, alleles, info); an EdsxError carries the info
+    dict, filled in as far as the call got, as its `info`"""
+    import numpy as np
+    ids = np.ascontiguousarray([] if paths is None else list(paths), dtype=np.uint64)
+    opts = LdOpts(int(window), float(min_r2), int(min_count), 1 if all_strings else 0, int(max_pairs))
+    p, a, info = _Buf(), _Buf(), LdInfo()
+    rc = fn(*head, ids.ctypes.data if len(ids) else None, len(ids), ctypes.byref(opts), ctypes.byref(p), ctypes.byref(a), ctypes.byref(info))
+    try:
+        ctx._check(rc)
+    except EdsxError as ex:
+        ex.info = _fields(info)
+        raise
+    return (np.frombuffer(ctx._take(p), dtype=LD_PAIR), np.frombuffer(ctx._take(a), dtype=LD_ALLELE), _fields(info))
 
 
 # the metrics of the path distances (EDSX_DIST_*)
@@ -746,6 +780,14 @@ class Context(_Handle):
                                                  miss.ctypes.data, ctypes.byref(info)))
         return mat, miss[:K], _fields(info)
 
+    # ---- linkage disequilibrium (edsparser-ld)
+    def eds_ld(self, eds, seds, paths=None, window=100, min_r2=0.0, min_count=1, all_strings=False, max_pairs=0):
+        """One-shot edsx_eds_ld: PathSession.ld on a session opened and closed for this call."""
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        return _ld_call(self, self._lib.edsx_eds_ld, (self._h, eds, len(eds), sb, sn), paths, window, min_r2, min_count, all_strings,
+                        max_pairs)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -1127,6 +1169,16 @@ class PathSession(_Handle):
                                                         int(max_bytes), mat.ctypes.data if mat.size else None, miss.ctypes.data,
                                                         ctypes.byref(info)))
         return mat, miss[:K], _fields(info)
+
+    def ld(self, paths=None, window=100, min_r2=0.0, min_count=1, all_strings=False, max_pairs=0):
+        """(pairs, alleles, info): r² between the alleles of the EDS over the paths `paths` (None or empty: all paths 1..P;
+        duplicates count once), for every pair of listed alleles whose choice symbols lie at most `window` choice symbols
+        apart (edsx_paths_ld).  An allele is a string of a choice symbol - string 0 only with all_strings - that between
+        min_count and present - min_count of the paths take.  pairs: numpy structured array (LD_PAIR) of the pairs with
+        r2 >= min_r2 in (symbol_a, string_a, symbol_b, string_b) order; alleles: the listed alleles with their counts
+        (LD_ALLELE), the allele frequency table of the panel; info: the dict of edsx_ld_info.  max_pairs (0: none):
+        EdsxError when more pairs would be reported."""
+        return _ld_call(self._ctx, self._lib.edsx_paths_ld, (self._h,), paths, window, min_r2, min_count, all_strings, max_pairs)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

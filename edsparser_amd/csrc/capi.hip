@@ -54,6 +54,7 @@ struct edsx_ctx {
     VcfExportPipeline vcf_export;            // edsx_eds_vcf
     KernelTimes slice_times;                 // edsx_paths_slice, of every session of this context
     KernelTimes dist_times;                  // edsx_paths_distances, likewise
+    KernelTimes ld_times;                    // edsx_paths_ld, likewise
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -422,6 +423,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->vcf_export.set_timing(enabled != 0);
     ctx->slice_times.set(enabled != 0);
     ctx->dist_times.set(enabled != 0);
+    ctx->ld_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -431,7 +433,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     n += ctx->gfa.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->ld_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1208,6 +1211,47 @@ int edsx_eds_distances(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_distances(s, ids, n, metric, max_bytes, matrix, missing, info); });
+}
+
+// ---- edsparser-ld (ld_device.hip, ld_core.hpp)
+static_assert(sizeof(LdInfo) == sizeof(edsx_ld_info) && offsetof(LdInfo, tiles) == offsetof(edsx_ld_info, tiles), "edsx_ld_info is LdInfo");
+static_assert(sizeof(LdOpts) == sizeof(edsx_ld_opts) && offsetof(LdOpts, max_pairs) == offsetof(edsx_ld_opts, max_pairs), "edsx_ld_opts is LdOpts");
+static_assert(sizeof(LdPair) == sizeof(edsx_ld_pair) && offsetof(LdPair, r2) == offsetof(edsx_ld_pair, r2), "edsx_ld_pair is LdPair");
+static_assert(sizeof(LdAllele) == sizeof(edsx_ld_allele) && offsetof(LdAllele, present) == offsetof(edsx_ld_allele, present),
+              "edsx_ld_allele is LdAllele");
+
+int edsx_paths_ld(edsx_paths_session* s, const uint64_t* ids, size_t n, const edsx_ld_opts* opts, edsx_buf* pairs, edsx_buf* alleles,
+                  edsx_ld_info* info)
+{
+    clear(pairs, alleles);
+    zero(info);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!pairs || !opts || (n && !ids)) throw ParamError("null argument");
+        LdOpts o;
+        std::memcpy(&o, opts, sizeof(o));
+        LdInfo li;
+        HostBytes p, a;
+        try {
+            s->p.ld(reinterpret_cast<const u64*>(ids), n, o, p, alleles ? &a : nullptr, li, &s->ctx->ld_times, nullptr);
+        } catch (...) {                                          // as far as the call got
+            if (info) std::memcpy(info, &li, sizeof(li));
+            throw;
+        }
+        if (info) std::memcpy(info, &li, sizeof(li));
+        give(pairs, p);
+        if (alleles) give(alleles, a);
+    });
+}
+
+int edsx_eds_ld(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids, size_t n,
+                const edsx_ld_opts* opts, edsx_buf* pairs, edsx_buf* alleles, edsx_ld_info* info)
+{
+    clear(pairs, alleles);
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_ld(s, ids, n, opts, pairs, alleles, info); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

@@ -1,12 +1,13 @@
 // path_device.hpp — host driver of the path spelling kernels (see path_device.hip): the sequence of every path of an
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
-// The session's coordinate lift, region slice and path distances: lift_device.hip, slice_device.hip, dist_device.hip
-// (where an operation goes).
+// The session's coordinate lift, region slice, path distances and linkage disequilibrium: lift_device.hip,
+// slice_device.hip, dist_device.hip, ld_device.hip (where an operation goes).
 #pragma once
 
 #include "dist_core.hpp"
 #include "eds_device.hpp"
 #include "kernel_times.hpp"
+#include "ld_core.hpp"
 #include "lift_core.hpp"
 #include "path_records.hpp"
 
@@ -40,6 +41,12 @@ struct SliceRegion { u64 symbol_first, symbol_last, cut_first, cut_end, column_f
 
 // edsx_dist_info (include/edsx.h)
 struct DistInfo { u64 units = 0, variable_units = 0, class_columns = 0, chunk_columns = 0, chunks = 0; };
+
+// edsx_ld_opts, edsx_ld_info, edsx_ld_pair, edsx_ld_allele (include/edsx.h)
+struct LdOpts { u64 window; double min_r2; u64 min_count; int all_strings; u64 max_pairs; };
+struct LdInfo { u64 paths = 0, choice_symbols = 0, alleles = 0, candidate_pairs = 0, undefined_pairs = 0, pairs = 0, row_words = 0, tiles = 0; };
+struct LdPair { u64 symbol_a, string_a, symbol_b, string_b, n_ab, n_a, n_b, n; double r2; };
+struct LdAllele { u64 symbol, string, count, present; };
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -93,6 +100,14 @@ public:
     void distances(const u64* ids, size_t n, int metric, u64 max_bytes, u64* matrix, u64* missing, DistInfo& info, KernelTimes* times,
                    hipStream_t st);
 
+    // Linkage disequilibrium between the alleles of the EDS over the paths ids[0..n) (n == 0: all paths; duplicates count
+    // once) (ld_core.hpp, ld_device.hip): the reported pairs as LdPair in (x, y) order, the listed alleles as
+    // LdAllele (nullable).  window == 0 or min_r2 outside [0, 1]: ParamError, and so are more pairs than max_pairs (0:
+    // none), found from the counts before the pairs are allocated.  The allele and presence rows have to fit budget(2):
+    // LimitError.  info is filled in as far as the call got.
+    void ld(const u64* ids, size_t n, const LdOpts& opts, HostBytes& pairs, HostBytes* alleles, LdInfo& info, KernelTimes* times,
+            hipStream_t st);
+
 private:
     // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
     // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
@@ -114,6 +129,13 @@ private:
     // are counted (cnt), the bit rows of all requested paths (rows) and the K x K sums that become the matrix (sums)
     struct DistClasses { bool ready = false; u64 V = 0, C = 0; DevBuf desc; };
     struct DistState { bool ready = false; u64 CW = 0; DevBuf may_miss, ccol, cnt, rows, sums; DistClasses cls[2]; };
+
+    // ld: the strings of the choice symbols in front of every choice symbol (soff, nc + 1; S of them), session state; per
+    // call the row of the requested paths (mask), per string its carriers (cnt, S), per choice symbol the paths present
+    // (pres), its listed alleles and whether it needs a presence row, both scanned (afirst, uidx: nc + 1), the allele rows
+    // (trows, A x WP) and presence rows (urows), the alleles as they are returned (al) and their choice symbols (ar), the
+    // column tiles per row tile, scanned (tstart), the reported pairs per (allele, column tile), scanned (cntx), the pairs
+    struct LdState { bool ready = false; u64 S = 0; DevBuf soff, mask, cnt, pres, afirst, uidx, trows, urows, al, ar, tstart, cntx, pairs; };
 
     // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
@@ -145,6 +167,8 @@ private:
     // of its metric
     void dist_open(hipStream_t st);
     void dist_classes(dist::Metric metric, TimedRuns& timed, hipStream_t st);
+    // ---- linkage disequilibrium (ld_device.hip): made by the first ld() of a session
+    void ld_open(hipStream_t st);
 
     DeviceEds eds_;
     PathInfo info_;
@@ -156,6 +180,7 @@ private:
     LiftState lift_;
     SliceState slice_;
     DistState dist_;
+    LdState ld_;
 };
 
 } // namespace edsx

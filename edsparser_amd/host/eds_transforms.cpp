@@ -3,6 +3,8 @@
 #include "edsparser/transforms/eds_transforms.hpp"
 #include "device.hpp"
 
+#include <cstring>
+
 namespace edsparser {
 
 static void run_merge(std::istream& input, std::ostream& output, Length context_length, std::istream* phasing_input,
@@ -138,6 +140,34 @@ PathDistances path_distances(std::istream& eds_in, std::istream& seds_in, const 
     if (rc != EDSX_OK) detail::throw_status(rc, ctx);
     d.units = di.units; d.variable_units = di.variable_units; d.class_columns = di.class_columns;
     d.missing.assign(miss.begin(), miss.end());
+    return d;
+}
+
+PathLd path_ld(std::istream& eds_in, std::istream& seds_in, const std::vector<int>& paths, const LdOptions& options)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    edsx_ctx* ctx = detail::context();
+    edsx_ld_opts lo;
+    lo.window = options.window; lo.min_r2 = options.min_r2; lo.min_count = options.min_count;
+    lo.all_strings = options.all_strings ? 1 : 0; lo.max_pairs = options.max_pairs;
+    edsx_buf pb{nullptr, 0}, ab{nullptr, 0};
+    edsx_ld_info li;
+    const int rc = edsx_eds_ld(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(), reinterpret_cast<const uint8_t*>(seds.data()),
+                               seds.size(), ids.data(), ids.size(), &lo, &pb, &ab, &li);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    PathLd d;
+    static_assert(sizeof(LdPair) == sizeof(edsx_ld_pair) && sizeof(LdAllele) == sizeof(edsx_ld_allele), "the records of edsx_paths_ld");
+    try {
+        d.pairs.resize(li.pairs);
+        d.alleles.resize(li.alleles);
+    } catch (...) { edsx_buf_free(&pb); edsx_buf_free(&ab); throw; }
+    if (li.pairs) std::memcpy(d.pairs.data(), pb.data, sizeof(LdPair) * li.pairs);
+    if (li.alleles) std::memcpy(d.alleles.data(), ab.data, sizeof(LdAllele) * li.alleles);
+    edsx_buf_free(&pb);
+    edsx_buf_free(&ab);
+    d.paths = li.paths; d.choice_symbols = li.choice_symbols; d.candidate_pairs = li.candidate_pairs; d.undefined_pairs = li.undefined_pairs;
     return d;
 }
 

@@ -79,6 +79,26 @@ struct PathDistances {
 PathDistances path_distances(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {},
                              DistanceMetric metric = DistanceMetric::COLUMNS);
 
+// edsparser-ld: r² between the alleles of the EDS over the given paths (empty: all paths 1..P; duplicates count once), for
+// every two listed alleles whose choice symbols lie at most `window` choice symbols apart, the pairs with r2 >= min_r2 in
+// (symbol_a, string_a, symbol_b, string_b) order, and the listed alleles with their counts (edsx_paths_ld states the rules
+// in full).  std::invalid_argument for a path outside 1..P, window == 0 or min_r2 outside [0, 1].
+struct LdOptions {
+    uint64_t window = 100;
+    double min_r2 = 0.2;
+    uint64_t min_count = 1;
+    bool all_strings = false;
+    uint64_t max_pairs = 0;                    // 0: no limit
+};
+struct LdPair { uint64_t symbol_a, string_a, symbol_b, string_b, n_ab, n_a, n_b, n; double r2; };
+struct LdAllele { uint64_t symbol, string, count, present; };
+struct PathLd {
+    std::vector<LdPair> pairs;
+    std::vector<LdAllele> alleles;
+    size_t paths = 0, choice_symbols = 0, candidate_pairs = 0, undefined_pairs = 0;
+};
+PathLd path_ld(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {}, const LdOptions& options = LdOptions());
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

@@ -602,6 +602,52 @@ int edsx_eds_distances(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const
                        const uint64_t* ids, size_t n, int metric, uint64_t max_bytes, uint64_t* matrix, uint64_t* missing,
                        edsx_dist_info* info);
 
+/* ---- edsparser-ld: linkage disequilibrium between the alleles of an EDS with sources (ld_device.hip, ld_core.hpp) ----
+ * Input: a path session and a set M of path ids; n == 0 means all paths 1..P; duplicates count once; K = |M|.  An id of 0
+ * or above P is EDSX_ERR_INVALID_PARAMETER, "Path id <p> out of range (1..<P>)".
+ *   Choice symbols.  The symbols that are not a single universal string, numbered r = 0..nc-1 in file order
+ *      (n_choice_symbols of edsx_paths_info); every symbol with two strings or more is one.
+ *   Carrier rule.  chosen(p, i) is the session's rule: the first string of symbol i, in file order, whose source set holds
+ *      p or 0.  Overlapping sets therefore do not count a path twice: the alleles of a symbol partition the paths that
+ *      have a string there.  T(r, j) = { p in M : chosen(p, symbol r) = string j }, U(r) = the union over j of T(r, j),
+ *      the paths present at r; count(r, j) = |T(r, j)|, present(r) = |U(r)|.
+ *   Listed alleles.  By default j >= 1: string 0 is REF in eds2vcf's convention, and for a biallelic site its r2 equals
+ *      that of string 1; all_strings != 0 lists j = 0 too.  An allele is listed iff min_count <= count <= present -
+ *      min_count; min_count = 0 lists everything, zero counts included.  Listed alleles are numbered 0..A-1 in (r, j)
+ *      order.  Equal texts are not merged, the convention of eds2gfa, eds2vcf and the distances.
+ *   Candidate pairs.  Listed alleles x = (r, j) and y = (r', j') with r < r' <= r + window.  window counts choice symbols
+ *      and must be >= 1: window == 0 is EDSX_ERR_INVALID_PARAMETER.  Two alleles of one symbol are never a pair.
+ *   Counts of a pair, over the paths present at both symbols: n = |U(r) & U(r')|, n_a = |T(x) & U(r')|, n_b = |T(y) & U(r)|,
+ *      n_ab = |T(x) & T(y)|.  Where neither symbol leaves a path of M without a string these are K, count(x), count(y).
+ *   r2.  With da = n_a (n - n_a), db = n_b (n - n_b) and D = n n_ab - n_a n_b (signed 64-bit): a pair with da db == 0 is
+ *      undefined; it is never reported and is counted in info.undefined_pairs.  Otherwise
+ *      r2 = ((double)D / (double)da) * ((double)D / (double)db), computed in exactly this form: with P <= 9 999 999 all
+ *      three integers are below 2^53, so the value is two correctly rounded divisions and one multiplication.
+ *   Filter and order.  A pair is reported iff r2 >= min_r2; min_r2 must lie in [0, 1], NaN or a value outside is
+ *      EDSX_ERR_INVALID_PARAMETER.  Pairs come back in (x, y) order: ascending symbol_a, string_a, symbol_b, string_b.
+ *   Output.  pairs: edsx_ld_pair records; alleles (may be NULL): the A listed alleles as edsx_ld_allele; both are
+ *      edsx_buf, freed by edsx_buf_free.  symbol is the index among all symbols, as in locate and lift, string the index
+ *      within the symbol.  info (may be NULL), filled in as far as the call got, on errors too:
+ *      paths K, choice_symbols nc, alleles A, candidate_pairs the sum over x of its partners in the band (a closed form),
+ *      undefined_pairs, pairs the reported ones, row_words ceil(P / 64), tiles the 64 x 64 allele tiles of the band.
+ *   Limits.  max_pairs (0: none) is held against the counted number of reported pairs before the pair buffer is
+ *      allocated: EDSX_ERR_INVALID_PARAMETER, "LD has <n> pairs, above the limit of <max>".  The allele rows (A * row_words
+ *      * 8 bytes) and the presence rows must fit the session's budget: otherwise EDSX_ERR_BUILD_FAILED, with the sizes
+ *      and the budget in the text.  An EDS without choice symbols, A = 0 or K = 0 gives empty buffers and status 0.  Every
+ *      error leaves the session usable.
+ * edsx_paths_last_timing: scan_ms the allele list and the tile list (and the scan between the pair passes), copy_ms the
+ * rows and both pair passes, bytes_written the pairs and the alleles; under edsx_set_timing the kernels come back by name
+ * from edsx_get_timing. */
+typedef struct { uint64_t symbol_a, string_a, symbol_b, string_b, n_ab, n_a, n_b, n; double r2; } edsx_ld_pair;
+typedef struct { uint64_t symbol, string, count, present; } edsx_ld_allele;
+typedef struct { uint64_t window; double min_r2; uint64_t min_count; int all_strings; uint64_t max_pairs; } edsx_ld_opts;
+typedef struct { uint64_t paths, choice_symbols, alleles, candidate_pairs, undefined_pairs, pairs, row_words, tiles; } edsx_ld_info;
+int edsx_paths_ld(edsx_paths_session* s, const uint64_t* ids, size_t n, const edsx_ld_opts* opts, edsx_buf* pairs,
+                  edsx_buf* alleles, edsx_ld_info* info);
+/* open + ld + close */
+int edsx_eds_ld(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                size_t n, const edsx_ld_opts* opts, edsx_buf* pairs, edsx_buf* alleles, edsx_ld_info* info);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
