@@ -105,6 +105,11 @@ class LdOpts(ctypes.Structure):
                 ("max_pairs", ctypes.c_uint64)]
 
 
+class IbsInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("paths", "choice_symbols", "class_columns", "chunk_columns", "chunks", "pairs",
+                                                "candidate_segments", "segments")]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -307,6 +312,10 @@ def load_library():
     lib.edsx_paths_ld.argtypes = [V, V, ctypes.c_size_t, P(LdOpts), P(_Buf), P(_Buf), P(LdInfo)]
     lib.edsx_eds_ld.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, P(LdOpts),
                                 P(_Buf), P(_Buf), P(LdInfo)]
+    U64 = ctypes.c_uint64
+    lib.edsx_paths_ibs.argtypes = [V, V, ctypes.c_size_t, U64, U64, U64, P(_Buf), P(_Buf), P(IbsInfo)]
+    lib.edsx_eds_ibs.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, U64, U64, U64,
+                                 P(_Buf), P(_Buf), P(IbsInfo)]
     _LIB = lib
     return lib
 
@@ -341,6 +350,26 @@ def _ld_call(ctx, fn, head, paths, window, min_r2, min_count, all_strings, max_p
         ex.info = _fields(info)
         raise
     return (np.frombuffer(ctx._take(p), dtype=LD_PAIR), np.frombuffer(ctx._take(a), dtype=LD_ALLELE), _fields(info))
+
+
+# edsx_ibs_segment as a numpy structured type
+IBS_SEGMENT = [(f, "<u8") for f in ("x", "y", "symbol_first", "symbol_last", "sites", "column_first", "column_end")]
+
+
+def _ibs_call(ctx, fn, head, paths, min_sites, min_columns, max_segments):
+    """edsx_paths_ibs / edsx_eds_ibs behind their leading arguments -> (segments, pair_off, info); an EdsxError carries the
+    info dict, filled in as far as the call got, as its `info`"""
+    import numpy as np
+    ids = np.ascontiguousarray([] if paths is None else list(paths), dtype=np.uint64)
+    sg, po, info = _Buf(), _Buf(), IbsInfo()
+    rc = fn(*head, ids.ctypes.data if len(ids) else None, len(ids), int(min_sites), int(min_columns), int(max_segments),
+            ctypes.byref(sg), ctypes.byref(po), ctypes.byref(info))
+    try:
+        ctx._check(rc)
+    except EdsxError as ex:
+        ex.info = _fields(info)
+        raise
+    return (np.frombuffer(ctx._take(sg), dtype=IBS_SEGMENT), np.frombuffer(ctx._take(po), dtype=np.uint64), _fields(info))
 
 
 # the metrics of the path distances (EDSX_DIST_*)
@@ -788,6 +817,13 @@ class Context(_Handle):
         return _ld_call(self, self._lib.edsx_eds_ld, (self._h, eds, len(eds), sb, sn), paths, window, min_r2, min_count, all_strings,
                         max_pairs)
 
+    # ---- shared segments (edsparser-ibs)
+    def eds_ibs(self, eds, seds, paths=None, min_sites=1, min_columns=0, max_segments=0):
+        """One-shot edsx_eds_ibs: PathSession.ibs on a session opened and closed for this call."""
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        return _ibs_call(self, self._lib.edsx_eds_ibs, (self._h, eds, len(eds), sb, sn), paths, min_sites, min_columns, max_segments)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -1179,6 +1215,16 @@ class PathSession(_Handle):
         (LD_ALLELE), the allele frequency table of the panel; info: the dict of edsx_ld_info.  max_pairs (0: none):
         EdsxError when more pairs would be reported."""
         return _ld_call(self._ctx, self._lib.edsx_paths_ld, (self._h,), paths, window, min_r2, min_count, all_strings, max_pairs)
+
+    def ibs(self, paths=None, min_sites=1, min_columns=0, max_segments=0):
+        """(segments, pair_off, info): the segments every two of the paths `paths` share (None or empty: all paths 1..P;
+        duplicates allowed), pairs being request positions x < y (edsx_paths_ibs).  A segment is a maximal interval of
+        symbols at all of which the two paths take the same string; it is reported when it holds at least min_sites choice
+        symbols and min_columns alignment columns (0, 0: every segment).  segments: numpy structured array (IBS_SEGMENT) in
+        (x, y, symbol_first) order; pair_off: K (K - 1) / 2 + 1 offsets, the records of pair q = (x, y) in row-major
+        upper-triangle order are segments[pair_off[q]:pair_off[q + 1]]; info: the dict of edsx_ibs_info.  max_segments
+        (0: none): EdsxError when more segments would be reported."""
+        return _ibs_call(self._ctx, self._lib.edsx_paths_ibs, (self._h,), paths, min_sites, min_columns, max_segments)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

@@ -55,6 +55,7 @@ struct edsx_ctx {
     KernelTimes slice_times;                 // edsx_paths_slice, of every session of this context
     KernelTimes dist_times;                  // edsx_paths_distances, likewise
     KernelTimes ld_times;                    // edsx_paths_ld, likewise
+    KernelTimes ibs_times;                   // edsx_paths_ibs, likewise
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -424,6 +425,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->slice_times.set(enabled != 0);
     ctx->dist_times.set(enabled != 0);
     ctx->ld_times.set(enabled != 0);
+    ctx->ibs_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -434,7 +436,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     n += ctx->vcf_export.get_timing(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->ld_times.get(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->ld_times.get(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->ibs_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1252,6 +1255,43 @@ int edsx_eds_ld(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_ld(s, ids, n, opts, pairs, alleles, info); });
+}
+
+// ---- edsparser-ibs (ibs_device.hip, ibs_core.hpp)
+static_assert(sizeof(IbsInfo) == sizeof(edsx_ibs_info) && offsetof(IbsInfo, segments) == offsetof(edsx_ibs_info, segments), "edsx_ibs_info is IbsInfo");
+static_assert(sizeof(IbsSegment) == sizeof(edsx_ibs_segment) && offsetof(IbsSegment, column_end) == offsetof(edsx_ibs_segment, column_end),
+              "edsx_ibs_segment is IbsSegment");
+
+int edsx_paths_ibs(edsx_paths_session* s, const uint64_t* ids, size_t n, uint64_t min_sites, uint64_t min_columns, uint64_t max_segments,
+                   edsx_buf* segments, edsx_buf* pair_off, edsx_ibs_info* info)
+{
+    clear(segments, pair_off);
+    zero(info);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!segments || !pair_off || (n && !ids)) throw ParamError("null argument");
+        IbsInfo ii;
+        HostBytes sg, po;
+        try {
+            s->p.ibs(reinterpret_cast<const u64*>(ids), n, min_sites, min_columns, max_segments, sg, po, ii, &s->ctx->ibs_times, nullptr);
+        } catch (...) {                                          // as far as the call got
+            if (info) std::memcpy(info, &ii, sizeof(ii));
+            throw;
+        }
+        if (info) std::memcpy(info, &ii, sizeof(ii));
+        give(segments, sg);
+        give(pair_off, po);
+    });
+}
+
+int edsx_eds_ibs(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids, size_t n,
+                 uint64_t min_sites, uint64_t min_columns, uint64_t max_segments, edsx_buf* segments, edsx_buf* pair_off, edsx_ibs_info* info)
+{
+    clear(segments, pair_off);
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_ibs(s, ids, n, min_sites, min_columns, max_segments, segments, pair_off, info); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

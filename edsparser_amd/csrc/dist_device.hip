@@ -229,6 +229,36 @@ void PathPipeline::dist_classes(dist::Metric metric, TimedRuns& timed, hipStream
     c.ready = true;
 }
 
+// The class list of `metric` and the bit rows of ids[0..n) in dist_.rows, K x plan.row_words words: dist_open, dist_classes,
+// then fits(classes, plan) - the caller's info and its budget check, which throws -, then the batched tables() + k_dist_rows
+// loop.  missing (nullable): n entries.  Needs nc_ > 0.  distances() and ibs() (ibs_device.hip) both build their rows here.
+dist::Plan PathPipeline::dist_rows(const u64* ids, size_t n, dist::Metric m, u64* missing, TimedRuns& timed,
+                                   const std::function<void(const DistClasses&, const dist::Plan&)>& fits, hipStream_t st)
+{
+    dist_open(st);
+    dist_classes(m, timed, st);
+    const DistClasses& c = dist_.cls[m];
+    const dist::Plan pl = dist::plan(n, c.C);
+    fits(c, pl);
+    dist_.rows.ensure(std::max<u64>(8 * (u64)n * pl.row_words, 8));
+
+    const EdsView v = eds_.view();
+    const dist::DistTab t{v.sym.size, v.sym.ent_off, v.str_off, v.chars, cidx_.as<u64>(), dist_.ccol.as<u64>(), dist_.may_miss.as<uint8_t>(), nc_};
+    const u64 KT = table_batch(n);
+    std::vector<u64> len, miss;
+    for (size_t i0 = 0; i0 < n; i0 += KT) {
+        const u64 Kb = std::min<u64>(KT, n - i0);
+        tables(ids + i0, Kb, len, miss, st);
+        if (missing) std::memcpy(missing + i0, miss.data(), 8 * Kb);
+        if (!c.C) continue;
+        const RowArgs ra{t, m, c.desc.as<u64>(), c.C, pl.row_words, csid_.as<u64>(), Kb, dist_.rows.as<u64>() + i0 * pl.row_words};
+        timed.run("k_dist_rows", [&] {
+            hipLaunchKernelGGL(k_dist_rows, dim3(grid_for(Kb * pl.row_words, 16384)), dim3(DT), 0, st, ra);
+        }, &timing_.copy_ms);
+    }
+    return pl;
+}
+
 void PathPipeline::distances(const u64* ids, size_t n, int metric, u64 max_bytes, u64* matrix, u64* missing, DistInfo& info,
                              KernelTimes* times, hipStream_t st)
 {
@@ -254,37 +284,19 @@ void PathPipeline::distances(const u64* ids, size_t n, int metric, u64 max_bytes
     timing_.bytes_written = mat;
     if (nc_ == 0) return;                                        // no choice symbol: all paths are the same sequence
 
-    dist_open(st);
     TimedRuns timed(st, times);                                  // every run with a bucket, as slice()
-    dist_classes(m, timed, st);
-    const DistClasses& c = dist_.cls[m];
-    const dist::Plan pl = dist::plan(K, c.C);
-    info.variable_units = c.V; info.class_columns = c.C; info.chunk_columns = 64 * pl.chunk_words; info.chunks = pl.chunks;
-    const u128 rows128 = (u128)8 * K * pl.row_words;
     const u64 cap = budget(2);
-    if (rows128 + mat128 > cap)
-        throw LimitError("The distance rows (" + std::to_string((u64)std::min<u128>(rows128, ~0ull)) + " bytes) and the matrix (" +
-                         std::to_string(mat) + " bytes) do not fit the budget of " + std::to_string(cap) +
-                         " bytes; request fewer paths at a time");
-    const u64 row_bytes = (u64)rows128;
-    dist_.rows.ensure(std::max<u64>(row_bytes, 8));
+    const dist::Plan pl = dist_rows(ids, n, m, missing, timed, [&](const DistClasses& c, const dist::Plan& pl) {
+        info.variable_units = c.V; info.class_columns = c.C; info.chunk_columns = 64 * pl.chunk_words; info.chunks = pl.chunks;
+        const u128 rows128 = (u128)8 * K * pl.row_words;
+        if (rows128 + mat128 > cap)
+            throw LimitError("The distance rows (" + std::to_string((u64)std::min<u128>(rows128, ~0ull)) + " bytes) and the matrix (" +
+                             std::to_string(mat) + " bytes) do not fit the budget of " + std::to_string(cap) +
+                             " bytes; request fewer paths at a time");
+    }, st);
+    const DistClasses& c = dist_.cls[m];
     dist_.sums.ensure(mat);
     EDSX_HIP(hipMemsetAsync(dist_.sums.ptr, 0, mat, st));
-
-    const EdsView v = eds_.view();
-    const dist::DistTab t{v.sym.size, v.sym.ent_off, v.str_off, v.chars, cidx_.as<u64>(), dist_.ccol.as<u64>(), dist_.may_miss.as<uint8_t>(), nc_};
-    const u64 KT = table_batch(n);
-    std::vector<u64> len, miss;
-    for (size_t i0 = 0; i0 < n; i0 += KT) {
-        const u64 Kb = std::min<u64>(KT, n - i0);
-        tables(ids + i0, Kb, len, miss, st);
-        if (missing) std::memcpy(missing + i0, miss.data(), 8 * Kb);
-        if (!c.C) continue;
-        const RowArgs ra{t, m, c.desc.as<u64>(), c.C, pl.row_words, csid_.as<u64>(), Kb, dist_.rows.as<u64>() + i0 * pl.row_words};
-        timed.run("k_dist_rows", [&] {
-            hipLaunchKernelGGL(k_dist_rows, dim3(grid_for(Kb * pl.row_words, 16384)), dim3(DT), 0, st, ra);
-        }, &timing_.copy_ms);
-    }
     if (c.C) {
         const PairArgs pa{dist_.rows.as<u64>(), K, pl.row_words, pl.chunk_words, pl.tiles, dist_.sums.as<u64>()};
         timed.run("k_dist_pairs", [&] {

@@ -1,16 +1,19 @@
 // path_device.hpp — host driver of the path spelling kernels (see path_device.hip): the sequence of every path of an
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
 // The session's coordinate lift, region slice, path distances and linkage disequilibrium: lift_device.hip,
-// slice_device.hip, dist_device.hip, ld_device.hip (where an operation goes).
+// slice_device.hip, dist_device.hip, ld_device.hip; the segments two paths share: ibs_device.hip (where an
+// operation goes).
 #pragma once
 
 #include "dist_core.hpp"
 #include "eds_device.hpp"
+#include "ibs_core.hpp"
 #include "kernel_times.hpp"
 #include "ld_core.hpp"
 #include "lift_core.hpp"
 #include "path_records.hpp"
 
+#include <functional>
 #include <vector>
 
 namespace edsx {
@@ -47,6 +50,10 @@ struct LdOpts { u64 window; double min_r2; u64 min_count; int all_strings; u64 m
 struct LdInfo { u64 paths = 0, choice_symbols = 0, alleles = 0, candidate_pairs = 0, undefined_pairs = 0, pairs = 0, row_words = 0, tiles = 0; };
 struct LdPair { u64 symbol_a, string_a, symbol_b, string_b, n_ab, n_a, n_b, n; double r2; };
 struct LdAllele { u64 symbol, string, count, present; };
+
+// edsx_ibs_info, edsx_ibs_segment (include/edsx.h)
+struct IbsInfo { u64 paths = 0, choice_symbols = 0, class_columns = 0, chunk_columns = 0, chunks = 0, pairs = 0, candidate_segments = 0, segments = 0; };
+typedef ibs::Segment IbsSegment;
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -108,6 +115,15 @@ public:
     void ld(const u64* ids, size_t n, const LdOpts& opts, HostBytes& pairs, HostBytes* alleles, LdInfo& info, KernelTimes* times,
             hipStream_t st);
 
+    // The segments every two of the paths ids[0..n) share (n == 0: all paths; duplicates allowed), pairs are request
+    // positions x < y (ibs_core.hpp, ibs_device.hip): the maximal intervals of symbols at all of which the two
+    // paths take the same string, those with sites >= min_sites and columns >= min_columns, as IbsSegment in (x, y,
+    // symbol_first) order; pair_off: K (K - 1) / 2 + 1 u64, the CSR over the pairs.  More segments than max_segments
+    // (0: none): ParamError, from the counts and before the records are allocated.  The bit rows, the per-(pair, chunk)
+    // scratch and the records have to fit budget(2): LimitError.  info is filled in as far as the call got.
+    void ibs(const u64* ids, size_t n, u64 min_sites, u64 min_columns, u64 max_segments, HostBytes& segments, HostBytes& pair_off,
+             IbsInfo& info, KernelTimes* times, hipStream_t st);
+
 private:
     // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
     // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
@@ -136,6 +152,12 @@ private:
     // (trows, A x WP) and presence rows (urows), the alleles as they are returned (al) and their choice symbols (ar), the
     // column tiles per row tile, scanned (tstart), the reported pairs per (allele, column tile), scanned (cntx), the pairs
     struct LdState { bool ready = false; u64 S = 0; DevBuf soff, mask, cnt, pres, afirst, uidx, trows, urows, al, ar, tstart, cntx, pairs; };
+
+    // ibs: ready - the first ibs() of the session has made the columns (align_.col) its records name; the bit rows are
+    // dist_.rows under the STRINGS class list.  Per call and (pair, chunk) the reported interior segments (icnt) and the
+    // first and last differing rank (first, last); per (pair, chunk + 1) the segments of the slot, scanned (tot); pair_off
+    // and the records
+    struct IbsState { bool ready = false; DevBuf icnt, first, last, tot, pair_off, seg; };
 
     // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
@@ -167,6 +189,9 @@ private:
     // of its metric
     void dist_open(hipStream_t st);
     void dist_classes(dist::Metric metric, TimedRuns& timed, hipStream_t st);
+    // both, then the bit rows of ids[0..n) in dist_.rows; fits: the caller's budget check, run once the class list is known
+    dist::Plan dist_rows(const u64* ids, size_t n, dist::Metric m, u64* missing, TimedRuns& timed,
+                         const std::function<void(const DistClasses&, const dist::Plan&)>& fits, hipStream_t st);
     // ---- linkage disequilibrium (ld_device.hip): made by the first ld() of a session
     void ld_open(hipStream_t st);
 
@@ -181,6 +206,7 @@ private:
     SliceState slice_;
     DistState dist_;
     LdState ld_;
+    IbsState ibs_;
 };
 
 } // namespace edsx

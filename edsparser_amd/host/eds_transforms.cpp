@@ -171,6 +171,31 @@ PathLd path_ld(std::istream& eds_in, std::istream& seds_in, const std::vector<in
     return d;
 }
 
+PathIbs path_ibs(std::istream& eds_in, std::istream& seds_in, const std::vector<int>& paths, const IbsOptions& options)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> ids;
+    for (int p : paths) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    edsx_ctx* ctx = detail::context();
+    edsx_buf sb{nullptr, 0}, ob{nullptr, 0};
+    edsx_ibs_info ii;
+    const int rc = edsx_eds_ibs(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(), reinterpret_cast<const uint8_t*>(seds.data()),
+                                seds.size(), ids.data(), ids.size(), options.min_sites, options.min_columns, options.max_segments, &sb, &ob, &ii);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    PathIbs d;
+    static_assert(sizeof(IbsSegment) == sizeof(edsx_ibs_segment), "the records of edsx_paths_ibs");
+    try {
+        d.segments.resize(ii.segments);
+        d.pair_off.resize(ob.size / 8);
+    } catch (...) { edsx_buf_free(&sb); edsx_buf_free(&ob); throw; }
+    if (ii.segments) std::memcpy(d.segments.data(), sb.data, sizeof(IbsSegment) * ii.segments);
+    if (ob.size) std::memcpy(d.pair_off.data(), ob.data, ob.size);
+    edsx_buf_free(&sb);
+    edsx_buf_free(&ob);
+    d.paths = ii.paths; d.choice_symbols = ii.choice_symbols; d.candidate_segments = ii.candidate_segments;
+    return d;
+}
+
 void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
 {

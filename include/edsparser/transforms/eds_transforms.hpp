@@ -99,6 +99,24 @@ struct PathLd {
 };
 PathLd path_ld(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {}, const LdOptions& options = LdOptions());
 
+// edsparser-ibs: the segments every two of the given paths share (empty: all paths 1..P; duplicates allowed; pairs are
+// request positions x < y): the maximal intervals of symbols at all of which the two paths take the same string, those
+// with at least min_sites choice symbols and min_columns alignment columns, in (x, y, symbol_first) order (edsx_paths_ibs
+// states the rules in full).  pair_off: K (K - 1) / 2 + 1 offsets into segments, pairs in row-major upper-triangle order.
+// std::invalid_argument for a path outside 1..P and for more segments than max_segments.
+struct IbsOptions {
+    uint64_t min_sites = 1;
+    uint64_t min_columns = 0;
+    uint64_t max_segments = 0;                 // 0: no limit
+};
+struct IbsSegment { uint64_t x, y, symbol_first, symbol_last, sites, column_first, column_end; };
+struct PathIbs {
+    std::vector<IbsSegment> segments;
+    std::vector<uint64_t> pair_off;
+    size_t paths = 0, choice_symbols = 0, candidate_segments = 0;
+};
+PathIbs path_ibs(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {}, const IbsOptions& options = IbsOptions());
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

@@ -648,6 +648,46 @@ int edsx_paths_ld(edsx_paths_session* s, const uint64_t* ids, size_t n, const ed
 int edsx_eds_ld(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
                 size_t n, const edsx_ld_opts* opts, edsx_buf* pairs, edsx_buf* alleles, edsx_ld_info* info);
 
+/* ---- edsparser-ibs: the segments two paths of an EDS with sources share (ibs_device.hip, ibs_core.hpp) ----
+ * Input: a path session and n path ids in request order; n == 0 means all paths 1..P; duplicates are allowed, as in
+ * edsx_paths_distances; K is the number of requested paths.  An id of 0 or above P is EDSX_ERR_INVALID_PARAMETER, "Path id
+ * <p> out of range (1..<P>)".  Pairs are the request positions x < y, K (K - 1) / 2 of them.
+ *   Agreement.  chosen(p, i) is the session's rule: the first string of symbol i, in file order, whose source set holds p
+ *      or 0.  Two paths agree at symbol i iff they take the same string index there; two paths without a string agree.
+ *      Equal texts are not merged, the convention of the `strings` distances, eds2gfa and eds2vcf.  A symbol that is a
+ *      single universal string is fixed: all paths agree there.
+ *   Segment.  A segment of a pair is a maximal non-empty interval of symbols [symbol_first, symbol_last] at all of which
+ *      the two paths agree: it is bounded on each side by a symbol where they differ or by an end of the EDS.  Two
+ *      adjacent differing symbols have no segment between them.  A pair that never differs, and every pair of an EDS
+ *      without choice symbols, has the one segment [0, n - 1].
+ *   Record (edsx_ibs_segment).  x, y: the request positions; symbol_first, symbol_last; sites: the choice symbols
+ *      (n_choice_symbols of edsx_paths_info counts them) inside the interval, may be 0; column_first, column_end: the
+ *      interval's columns in the view of edsx_paths_align, col[symbol_first] and col[symbol_last + 1], may be equal.
+ *   Reporting rule.  A segment is reported iff sites >= min_sites and column_end - column_first >= min_columns; with
+ *      0, 0 every segment is reported (the tools and the Python call default to 1, 0).
+ *   Order.  By (x, y), then symbol_first.
+ *   Output.  segments: an edsx_buf of records, freed by edsx_buf_free.  pair_off: an edsx_buf of K (K - 1) / 2 + 1
+ *      uint64_t, a CSR over the pairs in row-major upper-triangle order ((0,1), (0,2), .., (1,2), ..): the records of pair
+ *      q are [pair_off[q], pair_off[q + 1]).  info (may be NULL), filled in as far as the call got, on errors too: paths
+ *      K, choice_symbols, class_columns and chunk_columns and chunks of the `strings` class list as edsx_dist_info names
+ *      them, pairs, candidate_segments (the segments before the thresholds), segments (the reported ones).
+ *   Limits.  max_segments (0: none) is held against the counted number of reported segments before the records are
+ *      allocated: EDSX_ERR_INVALID_PARAMETER, "IBS has <n> segments, above the limit of <max>".  The bit rows, the
+ *      per-(pair, chunk) scratch and the records must fit the session's budget: otherwise EDSX_ERR_BUILD_FAILED, with the
+ *      sizes and the budget in the text and "request fewer paths at a time".  K < 2 gives no record and pair_off = {0}.
+ *      Every error leaves the session usable.
+ * edsx_paths_last_timing: choose_ms the choice tables, scan_ms the class list, the stitch passes and the scan between
+ * them, copy_ms the bit rows and both scan passes, bytes_written the records and pair_off; under edsx_set_timing the
+ * kernels come back by name from edsx_get_timing. */
+typedef struct { uint64_t x, y, symbol_first, symbol_last, sites, column_first, column_end; } edsx_ibs_segment;
+typedef struct { uint64_t paths, choice_symbols, class_columns, chunk_columns, chunks, pairs, candidate_segments, segments; } edsx_ibs_info;
+int edsx_paths_ibs(edsx_paths_session* s, const uint64_t* ids, size_t n, uint64_t min_sites, uint64_t min_columns,
+                   uint64_t max_segments, edsx_buf* segments, edsx_buf* pair_off, edsx_ibs_info* info);
+/* open + ibs + close */
+int edsx_eds_ibs(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* ids,
+                 size_t n, uint64_t min_sites, uint64_t min_columns, uint64_t max_segments, edsx_buf* segments, edsx_buf* pair_off,
+                 edsx_ibs_info* info);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
