@@ -6,3 +6,4 @@ C++ `edsparser::` host shims in edsparser_amd/host/.  There is no CPU fallback: 
 anywhere, but creating a Context without a gfx950 GPU raises.
 """
 from ._capi import Context, EdsxError, MultiGpu, PathSession, VcfSession, bgzf_index, gz_probe, lib_path, load_library, synth_size  # noqa: F401
+from ._capi import MOSAIC_PRIVATE, MOSAIC_SEGMENT  # noqa: F401

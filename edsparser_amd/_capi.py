@@ -110,6 +110,11 @@ class IbsInfo(ctypes.Structure):
                                                 "candidate_segments", "segments")]
 
 
+class MosaicInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("targets", "donors", "choice_symbols", "class_columns", "segments", "private_segments",
+                                                "private_symbols", "switches")]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -316,6 +321,9 @@ def load_library():
     lib.edsx_paths_ibs.argtypes = [V, V, ctypes.c_size_t, U64, U64, U64, P(_Buf), P(_Buf), P(IbsInfo)]
     lib.edsx_eds_ibs.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, U64, U64, U64,
                                  P(_Buf), P(_Buf), P(IbsInfo)]
+    lib.edsx_paths_mosaic.argtypes = [V, V, ctypes.c_size_t, V, ctypes.c_size_t, U64, P(_Buf), P(_Buf), P(MosaicInfo)]
+    lib.edsx_eds_mosaic.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, V, ctypes.c_size_t,
+                                    U64, P(_Buf), P(_Buf), P(MosaicInfo)]
     _LIB = lib
     return lib
 
@@ -370,6 +378,28 @@ def _ibs_call(ctx, fn, head, paths, min_sites, min_columns, max_segments):
         ex.info = _fields(info)
         raise
     return (np.frombuffer(ctx._take(sg), dtype=IBS_SEGMENT), np.frombuffer(ctx._take(po), dtype=np.uint64), _fields(info))
+
+
+# edsx_mosaic_segment as a numpy structured type; donor MOSAIC_PRIVATE: a private segment
+MOSAIC_SEGMENT = [(f, "<u8") for f in ("target", "donor", "symbol_first", "symbol_last", "sites", "column_first", "column_end")]
+MOSAIC_PRIVATE = 2 ** 64 - 1
+
+
+def _mosaic_call(ctx, fn, head, targets, donors, max_segments):
+    """edsx_paths_mosaic / edsx_eds_mosaic behind their leading arguments -> (segments, target_off, info); an EdsxError
+    carries the info dict, filled in as far as the call got, as its `info`"""
+    import numpy as np
+    t = np.ascontiguousarray([] if targets is None else list(targets), dtype=np.uint64)
+    d = np.ascontiguousarray([] if donors is None else list(donors), dtype=np.uint64)
+    sg, to, info = _Buf(), _Buf(), MosaicInfo()
+    rc = fn(*head, t.ctypes.data if len(t) else None, len(t), d.ctypes.data if len(d) else None, len(d), int(max_segments),
+            ctypes.byref(sg), ctypes.byref(to), ctypes.byref(info))
+    try:
+        ctx._check(rc)
+    except EdsxError as ex:
+        ex.info = _fields(info)
+        raise
+    return (np.frombuffer(ctx._take(sg), dtype=MOSAIC_SEGMENT), np.frombuffer(ctx._take(to), dtype=np.uint64), _fields(info))
 
 
 # the metrics of the path distances (EDSX_DIST_*)
@@ -824,6 +854,13 @@ class Context(_Handle):
         sb, sn = _opt(seds)
         return _ibs_call(self, self._lib.edsx_eds_ibs, (self._h, eds, len(eds), sb, sn), paths, min_sites, min_columns, max_segments)
 
+    # ---- mosaics (edsparser-mosaic)
+    def eds_mosaic(self, eds, seds, targets=None, donors=None, max_segments=0):
+        """One-shot edsx_eds_mosaic: PathSession.mosaic on a session opened and closed for this call."""
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        return _mosaic_call(self, self._lib.edsx_eds_mosaic, (self._h, eds, len(eds), sb, sn), targets, donors, max_segments)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -1225,6 +1262,17 @@ class PathSession(_Handle):
         upper-triangle order are segments[pair_off[q]:pair_off[q + 1]]; info: the dict of edsx_ibs_info.  max_segments
         (0: none): EdsxError when more segments would be reported."""
         return _ibs_call(self._ctx, self._lib.edsx_paths_ibs, (self._h,), paths, min_sites, min_columns, max_segments)
+
+    def mosaic(self, targets=None, donors=None, max_segments=0):
+        """(segments, target_off, info): every path of `targets` written as the fewest copies from the paths of `donors`
+        (each None or empty: all paths 1..P; duplicates allowed; a donor naming the target's own path is skipped), both
+        named by request position (edsx_paths_mosaic).  A copied segment is an interval of symbols over which the target
+        and its donor take the same strings, chosen to reach as far as any donor does (then the smallest position); a
+        private segment (donor MOSAIC_PRIVATE) holds symbols no eligible donor shares.  segments: numpy structured array
+        (MOSAIC_SEGMENT) in (target, symbol_first) order, the segments of a target tile [0, n - 1]; target_off: T + 1
+        offsets, the records of target x are segments[target_off[x]:target_off[x + 1]]; info: the dict of
+        edsx_mosaic_info.  max_segments (0: none): EdsxError when there are more segments."""
+        return _mosaic_call(self._ctx, self._lib.edsx_paths_mosaic, (self._h,), targets, donors, max_segments)
 
     def gfa_walks(self, paths=None, names=None, prefix=None):
         """(lines, missing, steps): the GFA P lines of the requested paths in request order (None or empty: all paths

@@ -56,6 +56,7 @@ struct edsx_ctx {
     KernelTimes dist_times;                  // edsx_paths_distances, likewise
     KernelTimes ld_times;                    // edsx_paths_ld, likewise
     KernelTimes ibs_times;                   // edsx_paths_ibs, likewise
+    KernelTimes mosaic_times;                // edsx_paths_mosaic, likewise
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -426,6 +427,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->dist_times.set(enabled != 0);
     ctx->ld_times.set(enabled != 0);
     ctx->ibs_times.set(enabled != 0);
+    ctx->mosaic_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -437,7 +439,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     n += ctx->slice_times.get(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->ld_times.get(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->ibs_times.get(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->ibs_times.get(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->mosaic_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1292,6 +1295,46 @@ int edsx_eds_ibs(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_ibs(s, ids, n, min_sites, min_columns, max_segments, segments, pair_off, info); });
+}
+
+// ---- edsparser-mosaic (mosaic_device.hip, mosaic_core.hpp)
+static_assert(sizeof(MosaicInfo) == sizeof(edsx_mosaic_info) && offsetof(MosaicInfo, switches) == offsetof(edsx_mosaic_info, switches),
+              "edsx_mosaic_info is MosaicInfo");
+static_assert(sizeof(MosaicSegment) == sizeof(edsx_mosaic_segment) && offsetof(MosaicSegment, column_end) == offsetof(edsx_mosaic_segment, column_end),
+              "edsx_mosaic_segment is MosaicSegment");
+
+int edsx_paths_mosaic(edsx_paths_session* s, const uint64_t* targets, size_t nt, const uint64_t* donors, size_t nd, uint64_t max_segments,
+                      edsx_buf* segments, edsx_buf* target_off, edsx_mosaic_info* info)
+{
+    clear(segments, target_off);
+    zero(info);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!segments || !target_off || (nt && !targets) || (nd && !donors)) throw ParamError("null argument");
+        MosaicInfo mi;
+        HostBytes sg, to;
+        try {
+            s->p.mosaic(reinterpret_cast<const u64*>(targets), nt, reinterpret_cast<const u64*>(donors), nd, max_segments, sg, to, mi,
+                        &s->ctx->mosaic_times, nullptr);
+        } catch (...) {                                          // as far as the call got
+            if (info) std::memcpy(info, &mi, sizeof(mi));
+            throw;
+        }
+        if (info) std::memcpy(info, &mi, sizeof(mi));
+        give(segments, sg);
+        give(target_off, to);
+    });
+}
+
+int edsx_eds_mosaic(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* targets,
+                    size_t nt, const uint64_t* donors, size_t nd, uint64_t max_segments, edsx_buf* segments, edsx_buf* target_off,
+                    edsx_mosaic_info* info)
+{
+    clear(segments, target_off);
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_mosaic(s, targets, nt, donors, nd, max_segments, segments, target_off, info); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

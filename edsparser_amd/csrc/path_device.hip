@@ -43,8 +43,8 @@
 //
 // spell, align and walks write records - a header text and a body - through one driver, emit_records: the arithmetic of
 // the records and of their batches is path_records.hpp; each of the three brings its tables and its body kernel.  The
-// coordinate lift, the region slice, the path distances, the linkage disequilibrium and the shared segments of the
-// session: lift_device.hip, slice_device.hip, dist_device.hip, ld_device.hip, ibs_device.hip.
+// coordinate lift, the region slice, the path distances, the linkage disequilibrium, the shared segments and the mosaics
+// of the session: lift_device.hip, slice_device.hip, dist_device.hip, ld_device.hip, ibs_device.hip, mosaic_device.hip.
 #include "path_device.hpp"
 #include "gfa_device.hpp"
 
@@ -550,7 +550,7 @@ void PathPipeline::open(const uint8_t* eds, size_t eds_n, const uint8_t* seds, s
     if (!seds) throw ParamError("Path spelling needs sources (.seds)");
     info_ = PathInfo{};
     timing_ = PathTiming{};
-    walk_.ready = align_.ready = lift_.ready = slice_.ready = dist_.ready = dist_.cls[0].ready = dist_.cls[1].ready = ld_.ready = ibs_.ready = false;
+    walk_.ready = align_.ready = lift_.ready = slice_.ready = dist_.ready = dist_.cls[0].ready = dist_.cls[1].ready = ld_.ready = ibs_.ready = mosaic_.ready = false;
     const auto t0 = std::chrono::steady_clock::now();
     eds_.load(eds, eds_n, seds, seds_n, true, st);
     eds_.drop_scratch();                                                      // the session may live long

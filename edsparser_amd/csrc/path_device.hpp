@@ -1,8 +1,8 @@
 // path_device.hpp — host driver of the path spelling kernels (see path_device.hip): the sequence of every path of an
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
 // The session's coordinate lift, region slice, path distances and linkage disequilibrium: lift_device.hip,
-// slice_device.hip, dist_device.hip, ld_device.hip; the segments two paths share: ibs_device.hip (where an
-// operation goes).
+// slice_device.hip, dist_device.hip, ld_device.hip; the segments two paths share: ibs_device.hip; a path as a mosaic of
+// other paths: mosaic_device.hip (where an operation goes).
 #pragma once
 
 #include "dist_core.hpp"
@@ -11,6 +11,7 @@
 #include "kernel_times.hpp"
 #include "ld_core.hpp"
 #include "lift_core.hpp"
+#include "mosaic_core.hpp"
 #include "path_records.hpp"
 
 #include <functional>
@@ -54,6 +55,10 @@ struct LdAllele { u64 symbol, string, count, present; };
 // edsx_ibs_info, edsx_ibs_segment (include/edsx.h)
 struct IbsInfo { u64 paths = 0, choice_symbols = 0, class_columns = 0, chunk_columns = 0, chunks = 0, pairs = 0, candidate_segments = 0, segments = 0; };
 typedef ibs::Segment IbsSegment;
+
+// edsx_mosaic_info, edsx_mosaic_segment (include/edsx.h)
+struct MosaicInfo { u64 targets = 0, donors = 0, choice_symbols = 0, class_columns = 0, segments = 0, private_segments = 0, private_symbols = 0, switches = 0; };
+typedef mosaic::Segment MosaicSegment;
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -124,6 +129,16 @@ public:
     void ibs(const u64* ids, size_t n, u64 min_sites, u64 min_columns, u64 max_segments, HostBytes& segments, HostBytes& pair_off,
              IbsInfo& info, KernelTimes* times, hipStream_t st);
 
+    // Every target path as a minimal mosaic of the donor paths (mosaic_core.hpp, mosaic_device.hip): targets
+    // [0..nt) and donors[0..nd) in request order, duplicates allowed, a count of 0: all paths; a donor position is eligible
+    // for a target unless it names the target's own path.  The fewest segments that tile [0, n - 1], each a copy from one
+    // donor (the furthest-reaching one, then the smallest request position) or private (donor NONE), as MosaicSegment in
+    // (target, symbol_first) order; target_off: nt + 1 u64, the CSR over the targets.  More segments than max_segments
+    // (0: none): ParamError, from the counts and before the records are allocated.  The bit rows of the distinct paths, the
+    // donor scratch and the records have to fit budget(2): LimitError.  info is filled in as far as the call got.
+    void mosaic(const u64* targets, size_t nt, const u64* donors, size_t nd, u64 max_segments, HostBytes& segments,
+                HostBytes& target_off, MosaicInfo& info, KernelTimes* times, hipStream_t st);
+
 private:
     // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
     // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
@@ -158,6 +173,11 @@ private:
     // first and last differing rank (first, last); per (pair, chunk + 1) the segments of the slot, scanned (tot); pair_off
     // and the records
     struct IbsState { bool ready = false; DevBuf icnt, first, last, tot, pair_off, seg; };
+
+    // mosaic: ready - as ibs, the columns its records name; the bit rows are dist_.rows.  Per call the row of every target
+    // and donor (rowof), the donor rows word-major in request order (rt), the alive bits per (target, lane) (alive), the
+    // segments per target, scanned: target_off (cnt), and the records
+    struct MosaicState { bool ready = false; DevBuf rowof, rt, alive, cnt, seg; };
 
     // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
@@ -207,6 +227,7 @@ private:
     DistState dist_;
     LdState ld_;
     IbsState ibs_;
+    MosaicState mosaic_;
 };
 
 } // namespace edsx

@@ -196,6 +196,34 @@ PathIbs path_ibs(std::istream& eds_in, std::istream& seds_in, const std::vector<
     return d;
 }
 
+PathMosaic path_mosaic(std::istream& eds_in, std::istream& seds_in, const std::vector<int>& targets, const std::vector<int>& donors,
+                       const MosaicOptions& options)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> tids, dids;
+    for (int p : targets) tids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+    for (int p : donors) dids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));
+    edsx_ctx* ctx = detail::context();
+    edsx_buf sb{nullptr, 0}, ob{nullptr, 0};
+    edsx_mosaic_info mi;
+    const int rc = edsx_eds_mosaic(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(), reinterpret_cast<const uint8_t*>(seds.data()),
+                                   seds.size(), tids.data(), tids.size(), dids.data(), dids.size(), options.max_segments, &sb, &ob, &mi);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    PathMosaic d;
+    static_assert(sizeof(MosaicSegment) == sizeof(edsx_mosaic_segment), "the records of edsx_paths_mosaic");
+    try {
+        d.segments.resize(mi.segments);
+        d.target_off.resize(ob.size / 8);
+    } catch (...) { edsx_buf_free(&sb); edsx_buf_free(&ob); throw; }
+    if (mi.segments) std::memcpy(d.segments.data(), sb.data, sizeof(MosaicSegment) * mi.segments);
+    if (ob.size) std::memcpy(d.target_off.data(), ob.data, ob.size);
+    edsx_buf_free(&sb);
+    edsx_buf_free(&ob);
+    d.targets = mi.targets; d.donors = mi.donors; d.choice_symbols = mi.choice_symbols;
+    d.private_segments = mi.private_segments; d.private_symbols = mi.private_symbols; d.switches = mi.switches;
+    return d;
+}
+
 void eds_subset(std::istream& eds_in, std::istream& seds_in, std::ostream& eds_out, std::ostream& seds_out,
                 const std::vector<int>& paths, bool keep_ids, SubsetInfo* info)
 {

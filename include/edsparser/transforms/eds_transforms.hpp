@@ -117,6 +117,25 @@ struct PathIbs {
 };
 PathIbs path_ibs(std::istream& eds, std::istream& seds, const std::vector<int>& paths = {}, const IbsOptions& options = IbsOptions());
 
+// edsparser-mosaic: every target path written as the fewest copies from the donor paths (each list empty: all paths 1..P;
+// duplicates allowed; both are named by request position; a donor that names the target's own path is skipped for it).
+// A copied segment reaches as far as any donor does, of equals the smallest position; a private segment (donor
+// MOSAIC_PRIVATE) holds the symbols no donor shares; the segments of a target tile [0, n - 1], in (target, symbol_first)
+// order (edsx_paths_mosaic states the rules in full).  target_off: T + 1 offsets into segments.  std::invalid_argument for
+// a path outside 1..P and for more segments than max_segments.
+constexpr uint64_t MOSAIC_PRIVATE = ~0ull;
+struct MosaicOptions {
+    uint64_t max_segments = 0;                 // 0: no limit
+};
+struct MosaicSegment { uint64_t target, donor, symbol_first, symbol_last, sites, column_first, column_end; };
+struct PathMosaic {
+    std::vector<MosaicSegment> segments;
+    std::vector<uint64_t> target_off;
+    size_t targets = 0, donors = 0, choice_symbols = 0, private_segments = 0, private_symbols = 0, switches = 0;
+};
+PathMosaic path_mosaic(std::istream& eds, std::istream& seds, const std::vector<int>& targets = {}, const std::vector<int>& donors = {},
+                       const MosaicOptions& options = MosaicOptions());
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

@@ -688,6 +688,46 @@ int edsx_eds_ibs(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8
                  size_t n, uint64_t min_sites, uint64_t min_columns, uint64_t max_segments, edsx_buf* segments, edsx_buf* pair_off,
                  edsx_ibs_info* info);
 
+/* ---- edsparser-mosaic: a path of an EDS with sources as a minimal mosaic of other paths (mosaic_device.hip, mosaic_core.hpp) ----
+ * Input: a path session and two id lists.  targets: nt path ids in request order, duplicates allowed; nt == 0 means all
+ * paths 1..P; T is the number of requested targets.  donors: nd ids likewise, nd == 0 means all paths 1..P; D is the number
+ * of requested donors.  An id of 0 or above P in either list is EDSX_ERR_INVALID_PARAMETER, "Path id <p> out of range
+ * (1..<P>)".  Targets and donors are named by their request positions x and y.
+ *   Agreement.  chosen(p, i) and "agree at symbol i" are those of edsx_paths_ibs: two paths agree iff they take the same
+ *      string index; two paths without a string agree; equal texts are not merged; at a fixed symbol all paths agree.
+ *   Eligibility.  For the target position x with path id t a donor position y is eligible iff donors[y] != t (leave one
+ *      out: with both lists empty every path is written in terms of all the others).
+ *   Mosaic of a target, n the number of symbols.  Start at s = 0 and repeat while s < n.  For every eligible y let e(y) be
+ *      the first symbol i >= s at which t and donors[y] differ, n without one, and best = max e(y).  If an eligible donor
+ *      exists and best > s: a copied segment [s, best - 1] whose donor is the smallest eligible y with e(y) = best; s =
+ *      best.  Otherwise a private segment [s, j - 1], j the first symbol > s at which some eligible donor agrees with t,
+ *      or n; its donor is UINT64_MAX; s = j.  Without an eligible donor the whole EDS is one private segment; n = 0 gives
+ *      no record.  The segments of a target tile [0, n - 1] without gaps or overlaps, and no way of writing t as copies
+ *      from single donors plus the symbols no donor shares has fewer pieces: reaching furthest is optimal.
+ *   Record (edsx_mosaic_segment).  target: x; donor: y or UINT64_MAX; symbol_first, symbol_last; sites, column_first,
+ *      column_end as in edsx_ibs_segment: the choice symbols inside, col[symbol_first] and col[symbol_last + 1].
+ *   Order.  By target, then symbol_first.
+ *   Output.  segments: an edsx_buf of records, freed by edsx_buf_free.  target_off: an edsx_buf of T + 1 uint64_t, the CSR
+ *      over the targets.  info (may be NULL), filled in as far as the call got, on errors too: targets T, donors D,
+ *      choice_symbols, class_columns of the `strings` class list, segments, private_segments, private_symbols (the
+ *      symbols inside private segments), switches (the sum over the targets of segments - 1).
+ *   Limits.  max_segments (0: none) is held against the counted number of segments before the records are allocated:
+ *      EDSX_ERR_INVALID_PARAMETER, "Mosaic has <n> segments, above the limit of <max>".  The bit rows of the distinct
+ *      requested paths, the donor scratch and the records must fit the session's budget: otherwise EDSX_ERR_BUILD_FAILED,
+ *      with the sizes and the budget in the text and "request fewer paths at a time".  Every error leaves the session
+ *      usable.
+ * edsx_paths_last_timing: choose_ms the choice tables, scan_ms the class list and the scan of the counts, copy_ms the bit
+ * rows, the donor transpose and both passes of the march, bytes_written the records and target_off; under edsx_set_timing
+ * the kernels come back by name from edsx_get_timing. */
+typedef struct { uint64_t target, donor, symbol_first, symbol_last, sites, column_first, column_end; } edsx_mosaic_segment;
+typedef struct { uint64_t targets, donors, choice_symbols, class_columns, segments, private_segments, private_symbols, switches; } edsx_mosaic_info;
+int edsx_paths_mosaic(edsx_paths_session* s, const uint64_t* targets, size_t nt, const uint64_t* donors, size_t nd,
+                      uint64_t max_segments, edsx_buf* segments, edsx_buf* target_off, edsx_mosaic_info* info);
+/* open + mosaic + close */
+int edsx_eds_mosaic(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* targets,
+                    size_t nt, const uint64_t* donors, size_t nd, uint64_t max_segments, edsx_buf* segments, edsx_buf* target_off,
+                    edsx_mosaic_info* info);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
