@@ -1,8 +1,8 @@
 """Build libedsx.so (HIP kernels + C ABI) for gfx950 with hipcc, in-tree.
 
-One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link; two more
-libraries for the tests only (libedsx_smallstacks.so, libedsx_guard.so) relink the same objects with one source each
-compiled with other flags.
+One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link; three more
+libraries for the tests only (libedsx_smallstacks.so, libedsx_guard.so, libedsx_weakhash.so) relink the same objects
+with one source each compiled with other flags.
 """
 import os
 import subprocess
@@ -27,6 +27,11 @@ TEST_FLAGS = {"merge_device.hip": ["-DEDSX_EXPERIMENTS", "-DEDSX_FW_STACK=256", 
 # call (csrc/dev_alloc.hip with -DEDSX_GUARD, tests/test_guard_gpu.py).  Never loaded by the product.
 GUARD_LIB = os.path.join(HERE, "libedsx_guard.so")
 GUARD_FLAGS = {"dev_alloc.hip": ["-DEDSX_GUARD"]}
+# A fourth one, also for the tests only: the MSA grouping with every hash of its hash-then-compare sites cut to ONE bit
+# (msa_hash() in csrc/msa_wave.hpp), so that of any three distinct strings two share a hash and the byte compares behind
+# the hashes decide over real collisions (tests/test_msa_weakhash_gpu.py).  Never loaded by the product.
+WEAKHASH_LIB = os.path.join(HERE, "libedsx_weakhash.so")
+WEAKHASH_FLAGS = {"msa_device.hip": ["-DEDSX_MSA_HASH_BITS=1"]}
 
 
 def _headers():
@@ -74,13 +79,14 @@ def build(force=False, verbose=False):
             list(ex.map(lambda j: _compile(j[0], j[1], j[2], verbose), jobs))
     if force or _newer(LIB, objs):
         _link(objs, LIB, verbose)
-    for lib, tag, flags in ((TEST_LIB, "smallstacks", TEST_FLAGS), (GUARD_LIB, "guard", GUARD_FLAGS)):
+    for lib, tag, flags in ((TEST_LIB, "smallstacks", TEST_FLAGS), (GUARD_LIB, "guard", GUARD_FLAGS),
+                           (WEAKHASH_LIB, "weakhash", WEAKHASH_FLAGS)):
         tobjs = list(objs)
         for name, extra in flags.items():
             src, obj = os.path.join(CSRC, name), os.path.join(OBJ, name.replace(".hip", ".%s.o" % tag))
             tobjs[tobjs.index(os.path.join(OBJ, name.replace(".hip", ".o")))] = obj
             if force or _newer(obj, [src] + hdrs):
-                _compile(src, obj, extra, verbose)
+                _compile(src, obj, EXTRA_FLAGS.get(name, []) + extra, verbose)
         if force or _newer(lib, tobjs):
             _link(tobjs, lib, verbose)
     return LIB

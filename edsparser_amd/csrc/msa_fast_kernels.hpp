@@ -14,8 +14,8 @@ namespace edsx {
 //   Grouping (k_seg_group): rows are grouped by RAW equality over the segment's columns ('-' and '\n'
 //   normalised), which needs no per-row gap stripping; the gap-stripped string of each raw group is then
 //   built once from its first row, and raw groups spelling the same string are joined.  Every path is exact
-//   (msa_transforms.cpp:262-293); what the wave cannot decide exactly (NUL bytes, long strings whose hashed
-//   keys meet, more than KCAP strings) goes to the generic workgroup-per-segment kernels.
+//   (msa_transforms.cpp:262-293); what the wave does not do (NUL bytes, more than KCAP strings or raw
+//   groups; strings whose hashes meet are compared in place) goes to the generic workgroup-per-segment kernels.
 //   The result is a grouping RECORD per segment: group id of every row (2 bits when there are at most 4
 //   strings, else 4 bits; natural row order, lane l's rows in dword(s) l), number of strings, first rows.
 //   Text (k_emit_fast): ids of rows 0..127 are placed one row per lane (mixed token lengths), ids 129.. by
@@ -256,7 +256,7 @@ __device__ __forceinline__ int refine_groups(LoadCol load_col, Cell cell, u32 nc
         if (keep) strs[r * 64u + mbcnt(nz)] = (uint8_t)c;
         // the same string as an earlier root?  Candidates by length and a hash of the letters in their columns (one
         // ballot instead of a walk over the roots: wide segments of an l-EDS have tens of raw groups), then the letters.
-        const u32 hsh = wave_xor_all(keep ? (c + 1u) * (0x9e3779b1u + 0x85ebca77u * mbcnt(nz)) : 0u);
+        const u32 hsh = msa_hash(wave_xor_all(keep ? (c + 1u) * (0x9e3779b1u + 0x85ebca77u * mbcnt(nz)) : 0u));
         u32 fin = nroot;
         for (u64 cand = ballot64(lane < nroot && root_len_l == len && root_hash_l == hsh); cand; cand &= cand - 1) {
             const u32 tt = (u32)__builtin_ctzll(cand);
@@ -281,12 +281,16 @@ __device__ __forceinline__ int refine_groups(LoadCol load_col, Cell cell, u32 nc
 // order of first appearance).  Returns false when the segment must take the generic path.
 //   one column : DNA table lookups, else exact SWAR byte compares.
 //   2..20 cols over {A,C,G,T,N,-}: exact 3-bit-per-column keys.
-//   otherwise  : every row gets a 96-bit additive signature of its raw column bytes (gaps normalised
-//                to 0; v_mad_u32_u24 = full rate); rows with equal signatures are PROPOSED as a raw
-//                group and then compared with the group's first row byte for byte (phase B), so the
-//                grouping is exact; raw groups that spell the same string are joined by their
-//                stripped string (verbatim key up to 12 letters; longer strings that hash alike send
-//                the segment to the generic kernels).  NUL bytes (msa_transforms.cpp:282) -> generic.
+//   otherwise, up to 64 rows and no common column inside: one row per lane.  The lane spells its gap-stripped
+//                string into 64 zeroed bytes of LDS; rows with the first remaining row's length and 32-bit
+//                FNV hash are PROPOSED as its group and then compared with its string in place, dword by
+//                dword (the zero padding makes the last partial dword comparable), so the grouping is exact.
+//   otherwise  : refine_groups - raw groups by refining the partition column by column (exact for every
+//                byte), the stripped string of each raw group's first row built once in LDS; an earlier
+//                root of the same length and 32-bit hash is PROPOSED and its letters compared in place,
+//                candidate after candidate, so the join is exact as well.  More than 64 raw groups, or a
+//                NUL byte (msa_transforms.cpp:282) -> generic.
+//   Both hashes go through msa_hash() (msa_wave.hpp): full width here, one bit in the tests' weak-hash library.
 // HEAVY false: one column, or 2..10 columns over the DNA alphabet; everything else returns 2 (= try the heavy
 // instantiation, which needs twice the registers).  1 = grouped, 0 = generic kernels.
 template <bool CHECK_NL, bool HEAVY>
@@ -398,6 +402,7 @@ __device__ __forceinline__ int fast_group(const MsaView& mv, u64 seg_a, u64 cmet
                 nl |= isnl ? 1u : 0u;
                 if (ch != '-' && !isnl) { strs[lane * 64u + len] = (uint8_t)ch; hsh = (hsh ^ ch) * 16777619u; len++; }
             }
+            hsh = msa_hash(hsh);
             if (ballot64(act && nul)) return 0;                   // '\0' ends a row's string (msa_transforms.cpp:282): generic kernels
             if (CHECK_NL && ballot64(act && nl)) saw_nl = 1;
             u32 mygid = 0, rep = 0, k = 0, sum = 0;

@@ -220,7 +220,7 @@ __device__ u32 group_segment(const MsaView& mv, u64 a, u64 b, SegLdsT<BIG>& lds,
             for (int i = 0; i < R; i++) {
                 const u32 r = r0 + (u32)i * GT;
                 if (r < S) {
-                    lds.key[r] = exact ? key[i] : (key[i] ^ len[i]) * 0x100000001b3ull;
+                    lds.key[r] = exact ? key[i] : msa_hash((key[i] ^ len[i]) * 0x100000001b3ull);
                     lds.gid[r] = GID_NONE;
                 }
             }

@@ -107,12 +107,30 @@ __device__ __forceinline__ uint4 normalise_col(const uint4& c, const uint4& vmas
     return make_uint4(c.x & ~gap.x, c.y & ~gap.y, c.z & ~gap.z, c.w & ~gap.w);
 }
 
+// Hash-then-compare sites of the grouping (the one-row-per-lane branch of fast_group, the root join of refine_groups,
+// the hashed keys of group_segment): the hash proposes, a byte compare decides.  EDSX_MSA_HASH_BITS keeps only that
+// many low bits of every such hash, so that the compares meet strings that differ (libedsx_weakhash.so: one bit, for
+// the tests only).  Undefined - the product - the hashes keep their full width and msa_hash() is the identity.
+#ifdef EDSX_MSA_HASH_BITS
+constexpr u32 MSA_HASH_BITS = EDSX_MSA_HASH_BITS;
+static_assert(MSA_HASH_BITS >= 1 && MSA_HASH_BITS <= 64, "EDSX_MSA_HASH_BITS: 1..64");
+#else
+constexpr u32 MSA_HASH_BITS = 64;
+#endif
+template <class T> __device__ __forceinline__ T msa_hash(T h)
+{
+    if constexpr (MSA_HASH_BITS >= 8 * sizeof(T)) return h;
+    else return h & (T)(((T)1 << MSA_HASH_BITS) - 1);
+}
+
 struct FastGroups {
     uint4 gid;            // byte i = group of row 16*lane+i (0xFF: no such row)
     u32 k;                // number of distinct strings (wave-uniform)
     u32 sumlen;           // sum of their lengths
     // lane g holds the state of group g
-    u64 key_lo, key_hi;   // the group's gap-stripped string (packed) or its hash, + length
+    u64 key_lo, key_hi;   // the group's gap-stripped string itself: one letter, or the 3-bit class codes of the exact DNA
+                          // keys (never a hash); 0 where the strings are compared in place in LDS and no key is kept
+                          // (the one-row-per-lane branch of fast_group, refine_groups)
     u32 rep;              // representative row (first row of the group in row order)
     u32 len;              // length of the group's string
 };
