@@ -1,4 +1,4 @@
-// cli_util.hpp — minimal command-line option parser for the three tools.  The reference uses
+// cli_util.hpp — minimal command-line option parser of the tools.  The reference uses
 // Boost.program_options (absent in this image); this accepts the same spellings:
 //   --name value | --name=value | -n value | -nvalue | boolean switches, and reports errors with
 //   Boost's wording so scripts that grep the messages keep working.

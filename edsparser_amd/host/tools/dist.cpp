@@ -7,30 +7,16 @@
 //   phylip   "K", then per row the name and the K values separated by single blanks
 // Rows are named <prefix><id - 1>, as eds2msa names them, or by line id of --names.  Banner, "[Performance]" line and exit
 // codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <cstdio>
 #include <vector>
 
 using namespace edsparser;
 
-namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Pairwise distances between the paths of an EDS with sources");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -52,65 +38,32 @@ int main(int argc, char** argv)
                          "EXAMPLES:\n"
                          "  edsparser-dist -i in.eds                                  # in.seds -> in.dist, all paths, tsv\n"
                          "  edsparser-dist -i in.eds -p 1-32 --normalize --format phylip -o tree.phy\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".dist");
+        const tool::Files f = tool::files(opts, ".dist");
         const unsigned long max_mb = opts.get_unsigned("max-mb", 0);
-        const std::string prefix = opts.get("prefix", "s"), metric_text = opts.get("metric", "columns"), format = opts.get("format", "tsv");
+        const std::string metric_text = opts.get("metric", "columns"), format = opts.get("format", "tsv");
         const bool normalize = opts.has("normalize");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
         if (metric_text != "columns" && metric_text != "strings")
-            return fail("the argument ('" + metric_text + "') for option '--metric' is invalid");
-        if (format != "tsv" && format != "phylip") return fail("the argument ('" + format + "') for option '--format' is invalid");
+            tool::fail("the argument ('" + metric_text + "') for option '--metric' is invalid");
+        if (format != "tsv" && format != "phylip") tool::fail("the argument ('" + format + "') for option '--format' is invalid");
         const int metric = metric_text == "columns" ? EDSX_DIST_COLUMNS : EDSX_DIST_STRINGS;
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
-        std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
+        tool::need_files(f);
+        std::vector<uint64_t> ids = tool::path_list(opts, "paths");
 
         std::cout << "EDS path distances\n";
-        std::cout << "  Input: " << input_file << "\n";
-        std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
         std::cout << "  Metric: " << metric_text << (normalize ? ", normalized" : "") << ", format: " << format << "\n";
 
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
-        }
-        edsx_paths_info_t pi;
-        edsx_paths_info(ses.s, &pi);
-        if (!opts.has("paths")) for (uint64_t p = 1; p <= pi.num_paths; p++) ids.push_back(p);
-        for (uint64_t p : ids)                                   // before the output file is created
-            if (p == 0 || p > pi.num_paths)
-                return fail("Path id " + std::to_string(p) + " out of range (1.." + std::to_string(pi.num_paths) + ")");
+        tool::Session ses(f);
+        const edsx_paths_info_t& pi = ses.info;
+        tool::resolve_paths(ids, pi.num_paths);                  // before the output file is created
         const size_t K = ids.size();
 
-        std::vector<std::string> all_names;
-        if (opts.has("names")) {
-            std::ifstream nf(opts.get("names"));
-            if (!nf) return fail("Cannot open names file: " + opts.get("names"));
-            for (std::string line; std::getline(nf, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                all_names.push_back(line);
-            }
-        }
-        std::vector<std::string> name;
-        for (uint64_t p : ids) {
-            if (!opts.has("names")) name.push_back(prefix + std::to_string(p - 1));
-            else if (p > all_names.size()) return fail("The names file has no name for path " + std::to_string(p));
-            else name.push_back(all_names[p - 1]);
-            if (name.back().empty() || name.back().find_first_of("\t \n") != std::string::npos)
-                return fail("The name of path " + std::to_string(p) + " is empty or holds a tab, blank or line feed");
-        }
+        const std::vector<std::string> name = tool::Names(opts, "s").names_of(ids, true);
 
         uint64_t bytes = 0;
         const bool wraps = __builtin_mul_overflow(static_cast<uint64_t>(K), static_cast<uint64_t>(K), &bytes) ||
@@ -118,12 +71,11 @@ int main(int argc, char** argv)
         if (wraps) bytes = ~0ull;
         const uint64_t cap = static_cast<uint64_t>(max_mb) << 20;
         if (wraps || (cap && bytes > cap))
-            return fail("Distance matrix has " + std::string(wraps ? "more than " : "") + std::to_string(bytes >> 20) +
+            tool::fail("Distance matrix has " + std::string(wraps ? "more than " : "") + std::to_string(bytes >> 20) +
                         " megabytes, above the limit of " + std::to_string(max_mb) + " (--max-mb)");
         std::vector<uint64_t> matrix(K * K), miss(K);
         edsx_dist_info di;
-        if (K && edsx_paths_distances(ses.s, ids.data(), K, metric, cap, matrix.data(), miss.data(), &di) != EDSX_OK)
-            return fail(edsx_last_error(ctx));
+        if (K) ses.check(edsx_paths_distances(ses.s, ids.data(), K, metric, cap, matrix.data(), miss.data(), &di));
         if (!K) di = edsx_dist_info{0, 0, 0, 0, 0};
         for (size_t k = 0; k < K; k++)
             if (miss[k]) std::cerr << "Warning: path " << ids[k] << " has no string in " << miss[k] << " symbols\n";
@@ -147,17 +99,11 @@ int main(int argc, char** argv)
             }
             text += '\n';
         }
-        tool::write_bytes(output_file, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
+        tool::write_bytes(f.output, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
         edsx_paths_timing t;
         edsx_paths_last_timing(ses.s, &t);
         std::cout << "  Device: tables " << t.choose_ms << " ms, class list " << t.scan_ms << " ms, rows and pairs " << t.copy_ms << " ms\n";
         std::cout << "  Matrix written: " << K << " x " << K << ", " << text.size() << " bytes\n";
         std::cout << "Distances complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

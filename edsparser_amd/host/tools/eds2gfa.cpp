@@ -3,30 +3,15 @@
 // linked (across symbols that hold an empty string), every path becomes a P line: the way from msa2eds / vcf2eds to graph
 // viewers, vg-style toolchains and graph aligners.  Banner, "[Performance]" line and exit codes in the style of the other
 // tools.  The graph is written first; the walks are appended in batches (--batch-mb), so host memory stays bounded.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <algorithm>
-#include <vector>
 
 using namespace edsparser;
 
-namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Write an EDS and its paths as a GFA 1.0 graph");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -48,51 +33,40 @@ int main(int argc, char** argv)
                          "  eds2gfa -i in.eds                       # in.seds, if there, -> in.gfa with one P line per path\n"
                          "  eds2gfa -i in.eds --no-paths -o graph.gfa\n"
                          "  eds2gfa -i in.eds -p 1,5,7-9 --names samples.txt\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        const bool sources_given = !sources_file.empty(), no_paths = opts.has("no-paths");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".gfa");
+        const tool::Files f = tool::files(opts, ".gfa");
+        const bool no_paths = opts.has("no-paths");
         const unsigned long batch_mb = opts.get_unsigned("batch-mb", 4096);
         const unsigned long long max_links = opts.get_unsigned("max-links", 0);
-        const std::string prefix = opts.get("prefix", "path");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (batch_mb == 0) return fail("--batch-mb must be > 0");
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (no_paths && (sources_given || opts.has("paths") || opts.has("names"))) return fail("--no-paths does not go with --sources, --paths or --names");
-        const bool with_paths = !no_paths && std::filesystem::exists(sources_file);
-        if (!no_paths && !with_paths && sources_given) return fail("Sources file does not exist: " + sources_file.string());
-        if (!with_paths && (opts.has("paths") || opts.has("names"))) return fail("--paths and --names need sources (.seds): " + sources_file.string() + " does not exist");
-        std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
+        if (batch_mb == 0) tool::fail("--batch-mb must be > 0");
+        tool::need_input(f);
+        if (no_paths && (f.sources_given || opts.has("paths") || opts.has("names"))) tool::fail("--no-paths does not go with --sources, --paths or --names");
+        const bool with_paths = !no_paths && std::filesystem::exists(f.sources);
+        if (!no_paths && !with_paths && f.sources_given) tool::fail("Sources file does not exist: " + f.sources.string());
+        if (!with_paths && (opts.has("paths") || opts.has("names"))) tool::fail("--paths and --names need sources (.seds): " + f.sources.string() + " does not exist");
+        std::vector<uint64_t> ids = tool::path_list(opts, "paths");
 
         std::cout << "EDS → GFA export\n";
-        std::cout << "  Input: " << input_file << "\n";
-        if (with_paths) std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        if (with_paths) std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
 
         edsx_ctx* ctx = detail::context();
-        const tool::MappedFile eds(input_file, "input");
-        Session ses;
-        if (with_paths) {                                        // first: a text that does not match its sources writes nothing
-            const tool::MappedFile seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
-        }
+        const tool::MappedFile eds(f.input, "input");
+        tool::Session ses;
+        if (with_paths) ses.open(eds, f.sources);                // first: a text that does not match its sources writes nothing
         std::ofstream out;
         uint64_t total = 0;
         edsx_gfa_info info;
         {
             detail::Buf graph;
-            if (edsx_eds_gfa_graph(ctx, eds.data(), eds.size(), max_links, &graph.b, &info) != EDSX_OK) return fail(edsx_last_error(ctx));
-            out.open(output_file, std::ios::binary);
-            if (!out) return fail("Cannot open output file: " + output_file.string());
+            tool::check(ctx, edsx_eds_gfa_graph(ctx, eds.data(), eds.size(), max_links, &graph.b, &info));
+            out.open(f.output, std::ios::binary);
+            if (!out) tool::fail("Cannot open output file: " + f.output.string());
             out.write(reinterpret_cast<const char*>(graph.b.data), static_cast<std::streamsize>(graph.b.size));
-            if (!out) return fail("Cannot write output file: " + output_file.string());
+            if (!out) tool::fail("Cannot write output file: " + f.output.string());
             total = graph.b.size;
         }
         std::cout << "  Symbols: " << info.n_symbols << " (" << info.n_open_symbols << " with an empty string), strings: " << info.n_strings
@@ -100,38 +74,22 @@ int main(int argc, char** argv)
 
         uint64_t lines = 0, batches = 0, off_graph = 0;
         if (with_paths) {
-            edsx_paths_info_t pi;
-            edsx_paths_info(ses.s, &pi);
-            if (!opts.has("paths")) for (uint64_t p = 1; p <= pi.num_paths; p++) ids.push_back(p);
-            std::vector<std::string> all_names;
-            if (opts.has("names")) {
-                std::ifstream nf(opts.get("names"));
-                if (!nf) return fail("Cannot open names file: " + opts.get("names"));
-                for (std::string line; std::getline(nf, line);) {
-                    if (!line.empty() && line.back() == '\r') line.pop_back();
-                    all_names.push_back(line);
-                }
-            }
-            std::vector<const char*> names;
-            if (opts.has("names")) {
-                for (uint64_t p : ids) {
-                    if (p == 0 || p > all_names.size() || all_names[p - 1].empty())
-                        return fail("The names file has no name for path " + std::to_string(p));
-                    names.push_back(all_names[p - 1].c_str());
-                }
-            }
+            if (ids.empty()) ids = tool::all_paths(ses.info.num_paths);
+            const tool::Names table(opts, "path");
+            std::vector<std::string> name_text;
+            if (table.given) name_text = table.names_of(ids);
+            const std::vector<const char*> names = tool::c_strs(name_text);
             // a line has at most 12 bytes per symbol ("<ten digits>+,") behind its name
-            const uint64_t per_path = 12 * pi.n_symbols + 256, budget = static_cast<uint64_t>(batch_mb) << 20;
+            const uint64_t per_path = 12 * ses.info.n_symbols + 256, budget = static_cast<uint64_t>(batch_mb) << 20;
             const size_t per_batch = static_cast<size_t>(std::max<uint64_t>(1, budget / per_path));
             std::vector<uint64_t> miss(ids.size()), steps(ids.size());
             for (size_t k0 = 0; k0 < ids.size(); k0 += per_batch) {
                 const size_t k1 = std::min(ids.size(), k0 + per_batch);
                 detail::Buf text;
-                if (edsx_paths_gfa_walks(ses.s, ids.data() + k0, k1 - k0, names.empty() ? nullptr : names.data() + k0, prefix.c_str(),
-                                         &text.b, miss.data() + k0, steps.data() + k0) != EDSX_OK)
-                    return fail(edsx_last_error(ctx));
+                ses.check(edsx_paths_gfa_walks(ses.s, ids.data() + k0, k1 - k0, names.empty() ? nullptr : names.data() + k0, table.prefix.c_str(),
+                                               &text.b, miss.data() + k0, steps.data() + k0));
                 out.write(reinterpret_cast<const char*>(text.b.data), static_cast<std::streamsize>(text.b.size));
-                if (!out) return fail("Cannot write output file: " + output_file.string());
+                if (!out) tool::fail("Cannot write output file: " + f.output.string());
                 total += text.b.size;
                 batches++;
             }
@@ -147,11 +105,5 @@ int main(int argc, char** argv)
         }
         std::cout << "  Bytes written: " << total << "\n";
         std::cout << "Export complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

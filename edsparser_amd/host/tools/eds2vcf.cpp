@@ -2,20 +2,13 @@
 // its positions refer to, on the GPU (edsx_eds_vcf).  Every symbol with two strings or more becomes a record, every path a
 // sample column: the way from msa2eds / vcf2eds / edsparser-subset back to bcftools, association pipelines and IGV.
 // Banner, "[Performance]" line and exit codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
-
-#include <vector>
+#include "tool_front.hpp"
 
 using namespace edsparser;
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Write an EDS and its sources as a VCF plus reference FASTA");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -41,61 +34,49 @@ int main(int argc, char** argv)
                          "  eds2vcf -i in.eds                       # in.seds, if there, -> in.vcf and in.ref.fa\n"
                          "  eds2vcf -i in.eds --no-samples -o sites.vcf\n"
                          "  eds2vcf -i in.eds --ref-path 1 --chrom chr21 --names samples.txt\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output"), ref_file = opts.get("ref-out");
-        const bool sources_given = !sources_file.empty(), no_samples = opts.has("no-samples");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".vcf");
-        if (ref_file.empty()) ref_file = input_file.parent_path() / (input_file.stem().string() + ".ref.fa");
-        const std::string chrom = opts.get("chrom", "eds"), prefix = opts.get("prefix", "path");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (no_samples && (sources_given || opts.has("names") || opts.has("ref-path")))
-            return fail("--no-samples does not go with --sources, --names or --ref-path");
-        const bool with_samples = !no_samples && std::filesystem::exists(sources_file);
-        if (!no_samples && !with_samples && sources_given) return fail("Sources file does not exist: " + sources_file.string());
-        if (!with_samples && opts.has("names")) return fail("--names needs sources (.seds): " + sources_file.string() + " does not exist");
+        const tool::Files f = tool::files(opts, ".vcf");
+        std::filesystem::path ref_file = opts.get("ref-out");
+        if (ref_file.empty()) ref_file = tool::beside(f.input, ".ref.fa");
+        const bool no_samples = opts.has("no-samples");
+        const std::string chrom = opts.get("chrom", "eds");
+        tool::need_input(f);
+        if (no_samples && (f.sources_given || opts.has("names") || opts.has("ref-path")))
+            tool::fail("--no-samples does not go with --sources, --names or --ref-path");
+        const bool with_samples = !no_samples && std::filesystem::exists(f.sources);
+        if (!no_samples && !with_samples && f.sources_given) tool::fail("Sources file does not exist: " + f.sources.string());
+        if (!with_samples && opts.has("names")) tool::fail("--names needs sources (.seds): " + f.sources.string() + " does not exist");
 
-        std::vector<std::string> all_names;
-        std::vector<const char*> names;
-        if (opts.has("names")) {
-            std::ifstream nf(opts.get("names"));
-            if (!nf) return fail("Cannot open names file: " + opts.get("names"));
-            for (std::string line; std::getline(nf, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                all_names.push_back(line);
-            }
-            for (const std::string& s : all_names) names.push_back(s.c_str());
-        }
+        // every line of the names file goes to the library as it is: it names the samples and checks the names itself
+        const tool::Names table(opts, "path");
+        const std::vector<const char*> names = tool::c_strs(table.lines);
 
         std::cout << "EDS → VCF export\n";
-        std::cout << "  Input: " << input_file << "\n";
-        if (with_samples) std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        if (with_samples) std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
         std::cout << "  Reference: " << ref_file << "\n";
 
         edsx_ctx* ctx = detail::context();
-        const tool::MappedFile eds(input_file, "input");
+        const tool::MappedFile eds(f.input, "input");
         edsx_vcf_export_opts o{};
-        o.chrom = chrom.c_str(); o.prefix = prefix.c_str();
+        o.chrom = chrom.c_str(); o.prefix = table.prefix.c_str();
         o.ref_path = opts.get_unsigned("ref-path", 0);
         o.line_width = opts.get_unsigned("line-width", 60);
         o.max_bytes = opts.get_unsigned("max-bytes", 0);
         static const char* const none[1] = {nullptr};
-        if (opts.has("names")) { o.names = names.empty() ? none : names.data(); o.n_names = names.size(); }
+        if (table.given) { o.names = names.empty() ? none : names.data(); o.n_names = names.size(); }
         edsx_vcf_export_info info;
         detail::Buf vcf, fa;
         int rc;
         if (with_samples) {
-            const tool::MappedFile seds(sources_file, "sources");
+            const tool::MappedFile seds(f.sources, "sources");
             rc = edsx_eds_vcf(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &o, &vcf.b, &fa.b, &info);
         } else rc = edsx_eds_vcf(ctx, eds.data(), eds.size(), nullptr, 0, &o, &vcf.b, &fa.b, &info);
-        if (rc != EDSX_OK) return fail(edsx_last_error(ctx));
-        tool::write_bytes(output_file, vcf.b.data, vcf.b.size, "output");
+        tool::check(ctx, rc);
+        tool::write_bytes(f.output, vcf.b.data, vcf.b.size, "output");
         tool::write_bytes(ref_file, fa.b.data, fa.b.size, "reference");
 
         std::cout << "  Symbols: " << info.symbols << ", strings: " << info.strings << "\n";
@@ -107,11 +88,5 @@ int main(int argc, char** argv)
                       << " the record before: anchored next to another degenerate symbol\n";
         std::cout << "  Bytes written: " << vcf.b.size + fa.b.size << "\n";
         std::cout << "Export complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

@@ -2,10 +2,7 @@
 // Flags, defaults, validation messages and the progress lines on stderr follow the reference tool
 // (src/cpp/tools/genrandomeds.cpp:383-405 options, :423-462 validation, :231-246 and :497-516 messages); the text
 // itself comes from edsx_genrandomeds (counter-based generator in HBM: same shape, not the reference's mt19937 bytes).
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <random>
 
@@ -13,9 +10,7 @@ using namespace edsparser;
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Generate random EDS file with controlled variability");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("output", 'o', true, true, "Output EDS file (.eds or .leds)");
@@ -34,8 +29,7 @@ int main(int argc, char** argv)
                       << "  genrandomeds --ref-size-mb 100 --variability 0.10 -o random.eds\n"
                       << "  genrandomeds --ref-size-mb 50 --variability 0.05 --min-context 50 -o random.leds\n"
                       << "\nNote: Sources file (.seds) is automatically generated alongside the EDS file.\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
         auto real = [&](const char* name, double def) {
@@ -54,17 +48,16 @@ int main(int argc, char** argv)
         const unsigned long var_len_max = opts.get_unsigned("variant-length-max", 10), min_context = opts.get_unsigned("min-context", 0);
         const std::string alphabet = opts.get("alphabet", "ACGT");
         const unsigned long seed = opts.has("seed") ? opts.get_unsigned("seed", 0) : std::random_device{}();
-        auto fail = [&](const char* msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (ref_size_mb == 0) return fail("Reference size must be greater than 0 MB");
-        if (!(variability >= 0.0 && variability <= 1.0)) return fail("Variability must be between 0.0 and 1.0");
-        if (min_alt < 2) return fail("Minimum alternatives must be at least 2");
+        if (ref_size_mb == 0) tool::fail("Reference size must be greater than 0 MB");
+        if (!(variability >= 0.0 && variability <= 1.0)) tool::fail("Variability must be between 0.0 and 1.0");
+        if (min_alt < 2) tool::fail("Minimum alternatives must be at least 2");
         // (range checks before the values are narrowed to the library's 32-bit parameters)
-        if (min_alt > 0xffffffffUL || max_alt > 0xffffffffUL) return fail("Maximum alternatives above 16 are not supported by this build");
-        if (var_len_max > 0xffffffffUL) return fail("Variant length max above 63 is not supported by this build");
-        if (max_alt < min_alt) return fail("Maximum alternatives must be >= minimum alternatives");
-        if (var_len_max == 0) return fail("Variant length max must be greater than 0");
-        if (!(snp_ratio >= 0.0 && snp_ratio <= 1.0)) return fail("SNP ratio must be between 0.0 and 1.0");
-        if (alphabet.empty()) return fail("Alphabet cannot be empty");
+        if (min_alt > 0xffffffffUL || max_alt > 0xffffffffUL) tool::fail("Maximum alternatives above 16 are not supported by this build");
+        if (var_len_max > 0xffffffffUL) tool::fail("Variant length max above 63 is not supported by this build");
+        if (max_alt < min_alt) tool::fail("Maximum alternatives must be >= minimum alternatives");
+        if (var_len_max == 0) tool::fail("Variant length max must be greater than 0");
+        if (!(snp_ratio >= 0.0 && snp_ratio <= 1.0)) tool::fail("SNP ratio must be between 0.0 and 1.0");
+        if (alphabet.empty()) tool::fail("Alphabet cannot be empty");
 
         const uint64_t total_bp = (uint64_t)ref_size_mb * 1000000ull;
         std::cerr << "Generating random EDS:\n";
@@ -88,7 +81,7 @@ int main(int argc, char** argv)
         std::cerr << "Writing to file: " << output_file << "\n";
         {
             std::ofstream out(output_file, std::ios::binary);
-            if (!out) return fail(("Cannot open output file: \"" + output_file.string() + "\"").c_str());
+            if (!out) tool::fail("Cannot open output file: \"" + output_file.string() + "\"");
             out.write(reinterpret_cast<const char*>(eds.b.data), (std::streamsize)eds.b.size);
         }
         std::filesystem::path seds_path = output_file;
@@ -102,11 +95,5 @@ int main(int argc, char** argv)
         std::cerr << "Successfully generated random EDS with sources\n";
         std::cerr << "Output written to: " << output_file << "\n";
         std::cerr << "Sources written to: " << seds_path << "\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

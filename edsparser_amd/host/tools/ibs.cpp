@@ -6,34 +6,15 @@
 //   record order; columns = column_end - column_first, ready for edsparser-slice --columns.
 // Paths are named <prefix><id - 1>, as eds2msa names them, or by line id of --names.  Banner, "[Performance]" line and exit
 // codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <vector>
 
 using namespace edsparser;
 
-namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-
-struct Buf {
-    edsx_buf b{nullptr, 0};
-    ~Buf() { edsx_buf_free(&b); }
-};
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Segments that two paths of an EDS with sources share");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -55,66 +36,31 @@ int main(int argc, char** argv)
                          "EXAMPLES:\n"
                          "  edsparser-ibs -i in.eds                                   # in.seds -> in.ibs, all pairs of paths\n"
                          "  edsparser-ibs -i in.eds -p 1-32 --min-sites 50 --min-columns 10000 -o tracts.tsv\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".ibs");
+        const tool::Files f = tool::files(opts, ".ibs");
         const unsigned long min_sites = opts.get_unsigned("min-sites", 1), min_columns = opts.get_unsigned("min-columns", 0),
                             max_segments = opts.get_unsigned("max-segments", 0);
-        const std::string prefix = opts.get("prefix", "s");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
-        std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
+        tool::need_files(f);
+        std::vector<uint64_t> ids = tool::path_list(opts, "paths");
 
         std::cout << "EDS shared segments\n";
-        std::cout << "  Input: " << input_file << "\n";
-        std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
         std::cout << "  Minimum: " << min_sites << " sites, " << min_columns << " columns\n";
 
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
-        }
-        edsx_paths_info_t pi;
-        edsx_paths_info(ses.s, &pi);
-        if (!opts.has("paths")) for (uint64_t p = 1; p <= pi.num_paths; p++) ids.push_back(p);
-        for (uint64_t p : ids)                                   // before the output file is created
-            if (p == 0 || p > pi.num_paths)
-                return fail("Path id " + std::to_string(p) + " out of range (1.." + std::to_string(pi.num_paths) + ")");
+        tool::Session ses(f);
+        const edsx_paths_info_t& pi = ses.info;
+        tool::resolve_paths(ids, pi.num_paths);                  // before the output file is created
         const size_t K = ids.size();
 
-        std::vector<std::string> all_names;
-        if (opts.has("names")) {
-            std::ifstream nf(opts.get("names"));
-            if (!nf) return fail("Cannot open names file: " + opts.get("names"));
-            for (std::string line; std::getline(nf, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                all_names.push_back(line);
-            }
-        }
-        std::vector<std::string> name;
-        for (uint64_t p : ids) {
-            if (!opts.has("names")) name.push_back(prefix + std::to_string(p - 1));
-            else if (p > all_names.size()) return fail("The names file has no name for path " + std::to_string(p));
-            else name.push_back(all_names[p - 1]);
-            if (name.back().empty() || name.back().find_first_of("\t \n") != std::string::npos)
-                return fail("The name of path " + std::to_string(p) + " is empty or holds a tab, blank or line feed");
-        }
+        const std::vector<std::string> name = tool::Names(opts, "s").names_of(ids, true);
 
-        Buf segs, off;
+        detail::Buf segs, off;
         edsx_ibs_info ii{0, 0, 0, 0, 0, 0, 0, 0};
-        if (K && edsx_paths_ibs(ses.s, ids.data(), K, min_sites, min_columns, max_segments, &segs.b, &off.b, &ii) != EDSX_OK)
-            return fail(edsx_last_error(ctx));
+        if (K) ses.check(edsx_paths_ibs(ses.s, ids.data(), K, min_sites, min_columns, max_segments, &segs.b, &off.b, &ii));
         std::cout << "  Paths: " << K << " of " << pi.num_paths << ", pairs: " << ii.pairs << ", choice symbols: " << ii.choice_symbols
                   << ", class columns: " << ii.class_columns << " in " << ii.chunks << (ii.chunks == 1 ? " chunk" : " chunks") << "\n";
 
@@ -129,18 +75,12 @@ int main(int argc, char** argv)
             }
             text += '\n';
         }
-        tool::write_bytes(output_file, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
+        tool::write_bytes(f.output, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
         edsx_paths_timing t;
         edsx_paths_last_timing(ses.s, &t);
         std::cout << "  Device: tables " << t.choose_ms << " ms, class list, stitch and scan " << t.scan_ms << " ms, rows and segment scan "
                   << t.copy_ms << " ms\n";
         std::cout << "  Segments written: " << ii.segments << " of " << ii.candidate_segments << ", " << text.size() << " bytes\n";
         std::cout << "IBS complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

@@ -6,10 +6,7 @@
 //   pairs    "symbol_a string_a symbol_b string_b n_ab n_a n_b n r2", tab separated, r2 as %.6g, the pairs with r2 >= --min-r2
 //   --freq   "symbol string count present freq": the listed alleles, the allele frequency table of the panel
 // Banner, "[Performance]" line and exit codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -17,24 +14,9 @@
 
 using namespace edsparser;
 
-namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-struct Buf {
-    edsx_buf b{nullptr, 0};
-    ~Buf() { edsx_buf_free(&b); }
-};
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Linkage disequilibrium between the alleles of an EDS with sources");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -56,51 +38,38 @@ int main(int argc, char** argv)
                          "EXAMPLES:\n"
                          "  edsparser-ld -i in.eds                                    # in.seds -> in.ld, window 100, r2 >= 0.2\n"
                          "  edsparser-ld -i in.eds --window 1000 --min-r2 0.8 --min-count 5 --freq in.frq -o pruned.ld\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".ld");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
+        const tool::Files f = tool::files(opts, ".ld");
         edsx_ld_opts lo;
         lo.window = opts.get_unsigned("window", 100);
         lo.min_count = opts.get_unsigned("min-count", 1);
         lo.max_pairs = opts.get_unsigned("max-pairs", 0);
         lo.all_strings = opts.has("all-strings") ? 1 : 0;
         lo.min_r2 = 0.2;
-        if (lo.window == 0) return fail("the argument ('0') for option '--window' is invalid");
+        if (lo.window == 0) tool::fail("the argument ('0') for option '--window' is invalid");
         if (opts.has("min-r2")) {
             const std::string t = opts.get("min-r2");
             size_t used = 0;
             try { lo.min_r2 = std::stod(t, &used); } catch (...) { used = 0; }
             if (used != t.size() || t.empty() || !(lo.min_r2 >= 0.0 && lo.min_r2 <= 1.0))
-                return fail("the argument ('" + t + "') for option '--min-r2' is invalid");
+                tool::fail("the argument ('" + t + "') for option '--min-r2' is invalid");
         }
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
-        std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
+        tool::need_files(f);
+        const std::vector<uint64_t> ids = tool::path_list(opts, "paths");   // none: all paths, and the library checks the ids
 
         std::cout << "EDS linkage disequilibrium\n";
-        std::cout << "  Input: " << input_file << "\n";
-        std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
         std::cout << "  Window: " << lo.window << " choice symbols, r2 >= " << lo.min_r2 << ", min count: " << lo.min_count
                   << (lo.all_strings ? ", all strings" : "") << "\n";
 
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
-        }
-        Buf pairs, alleles;
+        tool::Session ses(f);
+        detail::Buf pairs, alleles;
         edsx_ld_info li;
-        if (edsx_paths_ld(ses.s, ids.data(), ids.size(), &lo, &pairs.b, &alleles.b, &li) != EDSX_OK) return fail(edsx_last_error(ctx));
+        ses.check(edsx_paths_ld(ses.s, ids.data(), ids.size(), &lo, &pairs.b, &alleles.b, &li));
         std::cout << "  Paths: " << li.paths << ", choice symbols: " << li.choice_symbols << ", alleles: " << li.alleles << "\n";
         std::cout << "  Candidate pairs: " << li.candidate_pairs << " in " << li.tiles << (li.tiles == 1 ? " tile" : " tiles") << ", undefined: "
                   << li.undefined_pairs << ", reported: " << li.pairs << "\n";
@@ -115,7 +84,7 @@ int main(int argc, char** argv)
                           p[k].r2);
             text += line;
         }
-        tool::write_bytes(output_file, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
+        tool::write_bytes(f.output, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
         if (opts.has("freq")) {
             std::string ft = "symbol\tstring\tcount\tpresent\tfreq\n";
             const edsx_ld_allele* a = reinterpret_cast<const edsx_ld_allele*>(alleles.b.data);
@@ -132,11 +101,5 @@ int main(int argc, char** argv)
         std::cout << "  Device: allele and tile lists " << t.scan_ms << " ms, rows and pairs " << t.copy_ms << " ms\n";
         std::cout << "  Pairs written: " << li.pairs << ", " << text.size() << " bytes\n";
         std::cout << "LD complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

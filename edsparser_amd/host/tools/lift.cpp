@@ -12,21 +12,13 @@
 // OK or RANGE.  common_pos is "." inside a degenerate symbol.  An interval [s, e) is lifted by its first and last
 // character: start = pos(s), end = pos(e - 1), plus one when that character is there (SAME or ALIGNED); an interval that
 // comes out empty is written, not dropped.  Argument and query-file errors are reported before a context is created.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <sstream>
 
 using namespace edsparser;
 
 namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
 
 const char* const STATUS[] = {"SAME", "ALIGNED", "GAP", "MISSING", "RANGE"};
 
@@ -51,9 +43,7 @@ bool parse_path(const std::string& t, const std::string& prefix, uint64_t& v)
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Translate positions between the paths of an EDS");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -73,29 +63,25 @@ int main(int argc, char** argv)
                          "  edsparser-lift -i in.eds -q pos.tsv --sites          # symbol, string, offset, column\n"
                          "  cut -f3-5 hits.tsv | sed 's/$/\\t2/' | edsparser-lift -i in.eds --from-eds   # locate hits onto path 2\n"
                          "  edsparser-lift -i in.eds -q genes.bed --bed --to 7   # annotations of column 1's paths on path 7\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input"), query_file = opts.get("queries");
+        const tool::Files io = tool::files(opts);
+        const std::filesystem::path query_file = opts.get("queries");
         const bool from_stdin = !opts.has("queries");
-        std::filesystem::path sources_file = opts.get("sources");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
         const std::string prefix = opts.get("prefix", "path");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
         const bool sites = opts.has("sites"), from_eds = opts.has("from-eds"), bed = opts.has("bed"), has_to = opts.has("to");
-        if (sites + from_eds + bed > 1) return fail("--sites, --from-eds and --bed exclude each other");
-        if (bed && !has_to) return fail("--bed needs --to");
-        if (has_to && (sites || from_eds)) return fail("--to does not go with --sites or --from-eds");
+        if (sites + from_eds + bed > 1) tool::fail("--sites, --from-eds and --bed exclude each other");
+        if (bed && !has_to) tool::fail("--bed needs --to");
+        if (has_to && (sites || from_eds)) tool::fail("--to does not go with --sites or --from-eds");
         uint64_t to = 0;
         std::string to_text;
         if (has_to) {
             to_text = opts.get("to");
-            if (!parse_path(to_text, prefix, to)) return fail("the argument ('" + to_text + "') for option '--to' is invalid");
+            if (!parse_path(to_text, prefix, to)) tool::fail("the argument ('" + to_text + "') for option '--to' is invalid");
         }
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: \"" + input_file.string() + "\"");
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
-        if (!from_stdin && !std::filesystem::exists(query_file)) return fail("Query file does not exist: \"" + query_file.string() + "\"");
+        tool::need_files(io, true);
+        if (!from_stdin && !std::filesystem::exists(query_file)) tool::fail("Query file does not exist: \"" + query_file.string() + "\"");
 
         // the queries: a trailing '\r' is dropped, a missing final newline is fine
         std::vector<std::vector<std::string>> rows;              // the fields of every query line
@@ -104,7 +90,7 @@ int main(int argc, char** argv)
             std::ifstream file;
             if (!from_stdin) {
                 file.open(query_file, std::ios::binary);
-                if (!file) return fail("Cannot open query file: \"" + query_file.string() + "\"");
+                if (!file) tool::fail("Cannot open query file: \"" + query_file.string() + "\"");
             }
             std::istream& in = from_stdin ? std::cin : file;
             size_t line_no = 0;
@@ -120,19 +106,19 @@ int main(int argc, char** argv)
                     std::istringstream ls(line);
                     for (std::string t; ls >> t;) f.push_back(t);
                 }
-                auto bad = [&] { return fail("Query file line " + std::to_string(line_no) + " is malformed: \"" + line + "\""); };
+                auto bad = [&] { tool::fail("Query file line " + std::to_string(line_no) + " is malformed: \"" + line + "\""); };
                 uint64_t v[4] = {0, 0, 0, 0};
                 if (bed) {
                     if (f.size() < 3 || !parse_path(f[0], prefix, v[0]) || !parse_u64(f[1], v[1]) || !parse_u64(f[2], v[2]) || v[1] >= v[2])
-                        return bad();
+                        bad();
                 } else if (from_eds) {
                     if (f.size() != 4 || !parse_u64(f[0], v[0]) || !parse_u64(f[1], v[1]) || !parse_u64(f[2], v[2]) || !parse_path(f[3], prefix, v[3]))
-                        return bad();
+                        bad();
                 } else {
                     const size_t want = sites || has_to ? 2 : 3;
                     if (f.size() != want || !parse_path(f[0], prefix, v[0]) || !parse_u64(f[1], v[1]) ||
                         (want == 3 && !parse_path(f[2], prefix, v[2])))
-                        return bad();
+                        bad();
                     if (has_to) v[2] = to;
                 }
                 a.push_back(v[0]); b.push_back(v[1]); c.push_back(v[2]); d.push_back(v[3]);
@@ -141,39 +127,30 @@ int main(int argc, char** argv)
         }
         const size_t n = rows.size();
 
-        std::cerr << "Loading EDS file: " << input_file << "\n";
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK) return fail(edsx_last_error(ctx));
-        }
-        edsx_paths_info_t info;
-        edsx_paths_info(ses.s, &info);
-        std::cerr << "Loaded EDS with " << info.n_symbols << " symbols, " << info.num_paths << " paths\n";
+        std::cerr << "Loading EDS file: " << io.input << "\n";
+        tool::Session ses(io);
+        std::cerr << "Loaded EDS with " << ses.info.n_symbols << " symbols, " << ses.info.num_paths << " paths\n";
         std::cerr << "Lifting " << n << (bed ? " intervals" : " positions") << "...\n";
 
         std::string text;
         if (sites) {
             std::vector<edsx_lift_site> site(n);
             std::vector<uint8_t> st(n);
-            if (edsx_paths_lift_sites(ses.s, n, a.data(), b.data(), site.data(), st.data()) != EDSX_OK) return fail(edsx_last_error(ctx));
+            ses.check(edsx_paths_lift_sites(ses.s, n, a.data(), b.data(), site.data(), st.data()));
             for (size_t q = 0; q < n; q++)
                 text += rows[q][0] + "\t" + rows[q][1] + "\t" + num(site[q].symbol) + "\t" + num(site[q].string) + "\t" + num(site[q].offset) +
                         "\t" + num(site[q].column) + "\t" + num(site[q].common_pos) + "\t" + (st[q] ? "RANGE" : "OK") + "\n";
         } else if (from_eds) {
             std::vector<uint64_t> pos(n);
             std::vector<uint8_t> st(n);
-            if (edsx_paths_lift_place(ses.s, n, a.data(), b.data(), c.data(), d.data(), pos.data(), st.data()) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
+            ses.check(edsx_paths_lift_place(ses.s, n, a.data(), b.data(), c.data(), d.data(), pos.data(), st.data()));
             for (size_t q = 0; q < n; q++)
                 text += rows[q][0] + "\t" + rows[q][1] + "\t" + rows[q][2] + "\t" + rows[q][3] + "\t" + num(pos[q]) + "\t" + STATUS[st[q]] + "\n";
         } else if (bed) {                                        // both ends of every interval in one call
             std::vector<uint64_t> src(2 * n), at(2 * n), dst(2 * n, to), pos(2 * n);
             std::vector<uint8_t> st(2 * n);
             for (size_t q = 0; q < n; q++) { src[2 * q] = src[2 * q + 1] = a[q]; at[2 * q] = b[q]; at[2 * q + 1] = c[q] - 1; }
-            if (edsx_paths_lift(ses.s, 2 * n, src.data(), at.data(), dst.data(), pos.data(), st.data(), nullptr) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
+            ses.check(edsx_paths_lift(ses.s, 2 * n, src.data(), at.data(), dst.data(), pos.data(), st.data(), nullptr));
             for (size_t q = 0; q < n; q++) {
                 const uint8_t s0 = st[2 * q], s1 = st[2 * q + 1];
                 const bool there = s0 != EDSX_LIFT_RANGE && s1 != EDSX_LIFT_RANGE;
@@ -185,8 +162,7 @@ int main(int argc, char** argv)
         } else {
             std::vector<uint64_t> pos(n);
             std::vector<uint8_t> st(n);
-            if (edsx_paths_lift(ses.s, n, a.data(), b.data(), c.data(), pos.data(), st.data(), nullptr) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
+            ses.check(edsx_paths_lift(ses.s, n, a.data(), b.data(), c.data(), pos.data(), st.data(), nullptr));
             for (size_t q = 0; q < n; q++)
                 text += rows[q][0] + "\t" + rows[q][1] + "\t" + (has_to ? to_text : rows[q][2]) + "\t" + num(pos[q]) + "\t" + STATUS[st[q]] + "\n";
         }
@@ -196,11 +172,5 @@ int main(int argc, char** argv)
         edsx_paths_last_timing(ses.s, &t);
         std::cerr << "Device: tables " << t.choose_ms + t.scan_ms << " ms, search and place " << t.copy_ms << " ms\n";
         if (opts.has("output")) std::cerr << "Output written to: " << opts.get("output") << "\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

@@ -5,18 +5,13 @@
 // comma-separated: columns 2 and 6 of a common-start line are a --witness line of edsparser-genpatterns, and what
 // EDS::check_position takes.  --count-only writes "pattern  total  flags" instead (flags: 1 hits left out, 2 a walk cut
 // at its 65th choice).  Argument and pattern-file errors are reported before a context is created.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 using namespace edsparser;
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Locate patterns in EDS");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file");
@@ -29,8 +24,7 @@ int main(int argc, char** argv)
         opts.parse(argc, argv);
         if (opts.has("help")) {
             std::cout << opts.usage() << "\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
         const std::filesystem::path input_file = opts.get("input"), pattern_file = opts.get("patterns"), output_file = opts.get("output");
@@ -41,19 +35,18 @@ int main(int argc, char** argv)
             try { max_hits = std::stoull(v, &used); } catch (...) { used = 0; }
             if (used != v.size() || v[0] == '-') throw std::runtime_error("the argument ('" + v + "') for option '--max-hits' is invalid");
         }
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (max_hits == 0) return fail("--max-hits must be at least 1");
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: \"" + input_file.string() + "\"");
+        if (max_hits == 0) tool::fail("--max-hits must be at least 1");
+        if (!std::filesystem::exists(input_file)) tool::fail("Input file does not exist: \"" + input_file.string() + "\"");
         if (opts.has("sources") && !std::filesystem::exists(opts.get("sources")))
-            return fail("Sources file does not exist: \"" + opts.get("sources") + "\"");
-        if (!std::filesystem::exists(pattern_file)) return fail("Pattern file does not exist: \"" + pattern_file.string() + "\"");
+            tool::fail("Sources file does not exist: \"" + opts.get("sources") + "\"");
+        if (!std::filesystem::exists(pattern_file)) tool::fail("Pattern file does not exist: \"" + pattern_file.string() + "\"");
 
         // the patterns as CSR: a trailing '\r' is dropped, a missing final newline is fine, an empty line is an error
         std::string text;
         std::vector<uint64_t> off(1, 0);
         {
             std::ifstream in(pattern_file, std::ios::binary);
-            if (!in) return fail("Cannot open pattern file: \"" + pattern_file.string() + "\"");
+            if (!in) tool::fail("Cannot open pattern file: \"" + pattern_file.string() + "\"");
             const std::string raw = detail::slurp(in);
             size_t line = 1;
             for (size_t b = 0; b < raw.size(); line++) {
@@ -61,7 +54,7 @@ int main(int argc, char** argv)
                 if (e == std::string::npos) e = raw.size();
                 size_t len = e - b;
                 if (len && raw[b + len - 1] == '\r') len--;
-                if (len == 0) return fail("Pattern file line " + std::to_string(line) + " is empty");
+                if (len == 0) tool::fail("Pattern file line " + std::to_string(line) + " is empty");
                 text.append(raw, b, len);
                 off.push_back(text.size());
                 b = e + 1;
@@ -80,7 +73,7 @@ int main(int argc, char** argv)
                                        reinterpret_cast<const uint8_t*>(text.data()), max_hits,
                                        opts.has("common-only") ? EDSX_LOCATE_COMMON_ONLY : 0u, &hoff.b, &hits.b, &coff.b, &ch.b,
                                        &totals.b, &flags.b);
-        if (rc != EDSX_OK) return fail(edsx_last_error(ctx));
+        tool::check(ctx, rc);
         edsx_query_info info;
         edsx_query_last_info(ctx, &info);
         std::cerr << "Loaded EDS with " << info.n_symbols << " symbols, " << info.n_strings << " strings\n";
@@ -94,7 +87,7 @@ int main(int argc, char** argv)
         for (size_t q = 0; q < n; q++) truncated += fl[q] != 0;
         {
             std::ofstream out(output_file, std::ios::binary);
-            if (!out) return fail("Cannot open output file: \"" + output_file.string() + "\"");
+            if (!out) tool::fail("Cannot open output file: \"" + output_file.string() + "\"");
             std::string buf;
             for (size_t q = 0; q < n; q++) {
                 if (opts.has("count-only")) {
@@ -119,11 +112,5 @@ int main(int argc, char** argv)
         std::cerr << "Device: tokenise " << info.tokenise_ms << " ms, tables " << info.tables_ms << " ms, kernels " << info.kernel_ms
                   << " ms, download " << info.download_ms << " ms\n";
         std::cerr << "Output written to: " << output_file << "\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

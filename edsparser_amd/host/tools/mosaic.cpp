@@ -9,41 +9,15 @@
 //   changes: the symbol and the column at which the new segment starts.
 // Paths are named <prefix><id - 1>, as eds2msa names them, or by line id of --names.  Banner, "[Performance]" line and exit
 // codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <vector>
 
 using namespace edsparser;
 
-namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-
-struct Buf {
-    edsx_buf b{nullptr, 0};
-    ~Buf() { edsx_buf_free(&b); }
-};
-
-// tool::parse_paths under the name of the option it reads
-std::vector<uint64_t> parse_list(const std::string& text, const std::string& option)
-{
-    try { return tool::parse_paths(text); }
-    catch (const std::runtime_error&) { throw std::runtime_error("the argument ('" + text + "') for option '--" + option + "' is invalid"); }
-}
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Paths of an EDS with sources as minimal mosaics of other paths");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -67,69 +41,32 @@ int main(int argc, char** argv)
                          "EXAMPLES:\n"
                          "  edsparser-mosaic -i in.eds                               # in.seds -> in.mosaic, every path by the others\n"
                          "  edsparser-mosaic -i in.eds -t 7 -d 1-6 --breakpoints -o breaks.tsv\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + ".mosaic");
+        const tool::Files f = tool::files(opts, ".mosaic");
         const unsigned long max_segments = opts.get_unsigned("max-segments", 0);
         const bool breakpoints = opts.has("breakpoints");
-        const std::string prefix = opts.get("prefix", "s");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
-        std::vector<uint64_t> targets, donors;
-        if (opts.has("targets")) targets = parse_list(opts.get("targets"), "targets");
-        if (opts.has("donors")) donors = parse_list(opts.get("donors"), "donors");
+        tool::need_files(f);
+        std::vector<uint64_t> targets = tool::path_list(opts, "targets"), donors = tool::path_list(opts, "donors");
 
         std::cout << "EDS path mosaics\n";
-        std::cout << "  Input: " << input_file << "\n";
-        std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << (breakpoints ? " (breakpoints)\n" : "\n");
+        std::cout << "  Input: " << f.input << "\n";
+        std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << (breakpoints ? " (breakpoints)\n" : "\n");
 
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK)
-                return fail(edsx_last_error(ctx));
-        }
-        edsx_paths_info_t pi;
-        edsx_paths_info(ses.s, &pi);
-        if (!opts.has("targets")) for (uint64_t p = 1; p <= pi.num_paths; p++) targets.push_back(p);
-        if (!opts.has("donors")) for (uint64_t p = 1; p <= pi.num_paths; p++) donors.push_back(p);
-        for (const auto* ids : {&targets, &donors})                // before the output file is created
-            for (uint64_t p : *ids)
-                if (p == 0 || p > pi.num_paths)
-                    return fail("Path id " + std::to_string(p) + " out of range (1.." + std::to_string(pi.num_paths) + ")");
+        tool::Session ses(f);
+        const edsx_paths_info_t& pi = ses.info;
+        tool::resolve_paths(targets, pi.num_paths);              // before the output file is created
+        tool::resolve_paths(donors, pi.num_paths);
 
-        std::vector<std::string> all_names;
-        if (opts.has("names")) {
-            std::ifstream nf(opts.get("names"));
-            if (!nf) return fail("Cannot open names file: " + opts.get("names"));
-            for (std::string line; std::getline(nf, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                all_names.push_back(line);
-            }
-        }
-        std::vector<std::string> tname, dname;
-        for (const auto& [ids, name] : {std::make_pair(&targets, &tname), std::make_pair(&donors, &dname)})
-            for (uint64_t p : *ids) {
-                if (!opts.has("names")) name->push_back(prefix + std::to_string(p - 1));
-                else if (p > all_names.size()) return fail("The names file has no name for path " + std::to_string(p));
-                else name->push_back(all_names[p - 1]);
-                if (name->back().empty() || name->back().find_first_of("\t \n") != std::string::npos)
-                    return fail("The name of path " + std::to_string(p) + " is empty or holds a tab, blank or line feed");
-            }
+        const tool::Names table(opts, "s");
+        const std::vector<std::string> tname = table.names_of(targets, true), dname = table.names_of(donors, true);
 
-        Buf segs, off;
+        detail::Buf segs, off;
         edsx_mosaic_info mi{0, 0, 0, 0, 0, 0, 0, 0};
-        if (!targets.empty() && edsx_paths_mosaic(ses.s, targets.data(), targets.size(), donors.data(), donors.size(), max_segments, &segs.b,
-                                                  &off.b, &mi) != EDSX_OK)
-            return fail(edsx_last_error(ctx));
+        if (!targets.empty())
+            ses.check(edsx_paths_mosaic(ses.s, targets.data(), targets.size(), donors.data(), donors.size(), max_segments, &segs.b, &off.b, &mi));
         std::cout << "  Targets: " << targets.size() << ", donors: " << donors.size() << " of " << pi.num_paths << " paths, choice symbols: "
                   << mi.choice_symbols << ", class columns: " << mi.class_columns << "\n";
 
@@ -159,18 +96,12 @@ int main(int argc, char** argv)
             }
             lines = mi.segments;
         }
-        tool::write_bytes(output_file, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
+        tool::write_bytes(f.output, reinterpret_cast<const uint8_t*>(text.data()), text.size(), "output");
         edsx_paths_timing t;
         edsx_paths_last_timing(ses.s, &t);
         std::cout << "  Device: tables " << t.choose_ms << " ms, class list and scan " << t.scan_ms << " ms, rows and march " << t.copy_ms << " ms\n";
         std::cout << "  Segments: " << mi.segments << " (" << mi.private_segments << " private over " << mi.private_symbols << " symbols), switches: "
                   << mi.switches << "; lines written: " << lines << ", " << text.size() << " bytes\n";
         std::cout << "Mosaic complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

@@ -9,25 +9,12 @@
 //                     name symbol_first symbol_last cut_first cut_end column_first column_end strings chars eds_bytes seds_bytes status
 // A region that is empty or leaves its path is RANGE: it writes no file and is reported on standard error; the exit status
 // is non-zero only when the call fails.  Argument and BED errors are reported before a context is created.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
 #include "slice_args.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 using namespace edsparser;
 
 namespace {
-
-struct Session {
-    edsx_paths_session* s = nullptr;
-    ~Session() { edsx_paths_close(s); }
-};
-
-struct Buf {
-    edsx_buf b{nullptr, 0};
-    ~Buf() { edsx_buf_free(&b); }
-};
 
 std::string num(uint64_t v) { return v == UINT64_MAX ? std::string(".") : std::to_string(v); }
 
@@ -35,9 +22,7 @@ std::string num(uint64_t v) { return v == UINT64_MAX ? std::string(".") : std::t
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Cut regions out of an EDS by path or column coordinates");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -57,69 +42,56 @@ int main(int argc, char** argv)
                          "  edsparser-slice -i in.eds -r 7:10200000-10300000 -o region.eds    # of path 7, with all variation there\n"
                          "  edsparser-slice -i in.eds --columns 0-5000 --columns 5000-10000 --output-dir parts\n"
                          "  edsparser-slice -i in.eds --bed genes.bed --output-dir genes --table > genes.tsv\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
+        const tool::Files f = tool::files(opts);
         const std::string prefix = opts.get("prefix", "path");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
         uint64_t max_bytes = 0;
         if (opts.has("max-bytes") && !slice_args::parse_u64(opts.get("max-bytes"), max_bytes))
-            return fail("the argument ('" + opts.get("max-bytes") + "') for option '--max-bytes' is invalid");
+            tool::fail("the argument ('" + opts.get("max-bytes") + "') for option '--max-bytes' is invalid");
 
         // the regions, in command-line order
         std::vector<slice_args::Region> regions;
         for (const auto& g : opts.given()) {
             slice_args::Region r;
             if (g.first == "region") {
-                if (!slice_args::parse_region(g.second, prefix, r)) return fail("the argument ('" + g.second + "') for option '--region' is invalid");
+                if (!slice_args::parse_region(g.second, prefix, r)) tool::fail("the argument ('" + g.second + "') for option '--region' is invalid");
                 regions.push_back(r);
             } else if (g.first == "columns") {
-                if (!slice_args::parse_columns(g.second, r)) return fail("the argument ('" + g.second + "') for option '--columns' is invalid");
+                if (!slice_args::parse_columns(g.second, r)) tool::fail("the argument ('" + g.second + "') for option '--columns' is invalid");
                 regions.push_back(r);
             } else if (g.first == "bed") {
                 std::ifstream file(g.second, std::ios::binary);
-                if (!file) return fail("Cannot open BED file: \"" + g.second + "\"");
+                if (!file) tool::fail("Cannot open BED file: \"" + g.second + "\"");
                 size_t line_no = 0;
                 for (std::string line; std::getline(file, line);) {
                     line_no++;
                     const int rc = slice_args::parse_bed_line(line, prefix, r);
-                    if (rc < 0) return fail("BED file line " + std::to_string(line_no) + " is malformed: \"" + line + "\"");
+                    if (rc < 0) tool::fail("BED file line " + std::to_string(line_no) + " is malformed: \"" + line + "\"");
                     if (rc > 0) regions.push_back(r);
                 }
             }
         }
         const size_t n = regions.size();
-        if (n == 0) return fail("No region given (-r, --columns or --bed)");
+        if (n == 0) tool::fail("No region given (-r, --columns or --bed)");
         const bool to_file = opts.has("output"), to_dir = opts.has("output-dir");
-        if (to_file && to_dir) return fail("--output and --output-dir exclude each other");
-        if (to_file && n != 1) return fail("--output takes one region; use --output-dir for " + std::to_string(n));
-        if (!to_file && !to_dir && !opts.has("table")) return fail("Nothing to do: give --output, --output-dir or --table");
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: \"" + input_file.string() + "\"");
-        if (!std::filesystem::exists(sources_file)) return fail("Path spelling needs sources (.seds): " + sources_file.string() + " does not exist");
+        if (to_file && to_dir) tool::fail("--output and --output-dir exclude each other");
+        if (to_file && n != 1) tool::fail("--output takes one region; use --output-dir for " + std::to_string(n));
+        if (!to_file && !to_dir && !opts.has("table")) tool::fail("Nothing to do: give --output, --output-dir or --table");
+        tool::need_files(f, true);
 
-        std::cerr << "Loading EDS file: " << input_file << "\n";
-        edsx_ctx* ctx = detail::context();
-        Session ses;
-        {
-            const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
-            if (edsx_paths_open(ctx, eds.data(), eds.size(), seds.data(), seds.size(), &ses.s) != EDSX_OK) return fail(edsx_last_error(ctx));
-        }
-        edsx_paths_info_t info;
-        edsx_paths_info(ses.s, &info);
-        std::cerr << "Loaded EDS with " << info.n_symbols << " symbols, " << info.num_paths << " paths\n";
+        std::cerr << "Loading EDS file: " << f.input << "\n";
+        tool::Session ses(f);
+        std::cerr << "Loaded EDS with " << ses.info.n_symbols << " symbols, " << ses.info.num_paths << " paths\n";
         std::cerr << "Slicing " << n << " regions...\n";
 
         std::vector<uint64_t> path(n), start(n), end(n);
         for (size_t r = 0; r < n; r++) { path[r] = regions[r].path; start[r] = regions[r].start; end[r] = regions[r].end; }
         std::vector<edsx_slice_region> reg(n);
         std::vector<uint8_t> st(n);
-        Buf eds, seds;
-        if (edsx_paths_slice(ses.s, n, path.data(), start.data(), end.data(), max_bytes, &eds.b, &seds.b, reg.data(), st.data()) != EDSX_OK)
-            return fail(edsx_last_error(ctx));
+        detail::Buf eds, seds;
+        ses.check(edsx_paths_slice(ses.s, n, path.data(), start.data(), end.data(), max_bytes, &eds.b, &seds.b, reg.data(), st.data()));
 
         if (to_dir) std::filesystem::create_directories(opts.get("output-dir"));
         std::string table;
@@ -148,11 +120,5 @@ int main(int argc, char** argv)
         edsx_paths_last_timing(ses.s, &t);
         std::cerr << "Device: resolve, count and scan " << t.choose_ms + t.scan_ms << " ms, fill " << t.copy_ms << " ms, " << t.bytes_written << " bytes\n";
         if (to_file || to_dir) std::cerr << "Slices written: " << written << " of " << n << "\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

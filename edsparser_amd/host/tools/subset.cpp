@@ -2,37 +2,15 @@
 // The result is again an .eds (FULL form) + .seds: one population out of a panel, a training / held-out split, "these 20
 // assemblies only".  Every kept path spells the sequence it spelled before (eds2fasta).  Banner, "[Performance]" line and
 // exit codes in the style of the other tools.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
-#include "tool_common.hpp"
+#include "tool_front.hpp"
 
 #include <algorithm>
-#include <vector>
 
 using namespace edsparser;
 
-namespace {
-
-std::vector<std::string> read_lines(const std::string& path, const char* what)
-{
-    std::ifstream in(path);
-    if (!in) throw std::runtime_error(std::string("Cannot open ") + what + " file: " + path);
-    std::vector<std::string> lines;
-    for (std::string line; std::getline(in, line);) {
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        lines.push_back(line);
-    }
-    return lines;
-}
-
-} // namespace
-
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Restrict an EDS with sources to a set of paths");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input EDS file (.eds / .leds)");
@@ -53,47 +31,40 @@ int main(int argc, char** argv)
                          "EXAMPLES:\n"
                          "  edsparser-subset -i in.eds -p 1,5,7-9          # in.seds -> in_subset.eds + in_subset.seds\n"
                          "  edsparser-subset -i in.eds --paths-file held_out.txt --exclude -o train.eds\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
-        const std::filesystem::path input_file = opts.get("input");
-        std::filesystem::path sources_file = opts.get("sources"), output_file = opts.get("output");
-        if (sources_file.empty()) { sources_file = input_file; sources_file.replace_extension(".seds"); }
-        if (output_file.empty()) output_file = input_file.parent_path() / (input_file.stem().string() + "_subset.eds");
-        std::filesystem::path sources_out = output_file;
+        const tool::Files f = tool::files(opts, "_subset.eds");
+        std::filesystem::path sources_out = f.output;
         sources_out.replace_extension(".seds");
         const bool exclude = opts.has("exclude"), keep_ids = opts.has("keep-ids");
-        auto fail = [&](const std::string& msg) { std::cerr << "Error: " << msg << "\n"; tool::print_performance(timer); return 1; };
-        if (!std::filesystem::exists(input_file)) return fail("Input file does not exist: " + input_file.string());
-        if (!std::filesystem::exists(sources_file)) return fail("Path subsetting needs sources (.seds): " + sources_file.string() + " does not exist");
-        if (opts.has("paths") && opts.has("paths-file")) return fail("--paths and --paths-file exclude each other");
-        if (!opts.has("paths") && !opts.has("paths-file")) return fail("One of --paths and --paths-file is required");
-        if (opts.has("names") != opts.has("names-out")) return fail("--names and --names-out go together");
-        if (opts.has("names") && keep_ids) return fail("--names-out lists the names in new-id order: it does not go with --keep-ids");
-        std::vector<uint64_t> ids;
-        if (opts.has("paths")) ids = tool::parse_paths(opts.get("paths"));
-        else {
+        tool::need_files(f, false, "Path subsetting");
+        if (opts.has("paths") && opts.has("paths-file")) tool::fail("--paths and --paths-file exclude each other");
+        if (!opts.has("paths") && !opts.has("paths-file")) tool::fail("One of --paths and --paths-file is required");
+        if (opts.has("names") != opts.has("names-out")) tool::fail("--names and --names-out go together");
+        if (opts.has("names") && keep_ids) tool::fail("--names-out lists the names in new-id order: it does not go with --keep-ids");
+        std::vector<uint64_t> ids = tool::path_list(opts, "paths");
+        if (!opts.has("paths")) {
             size_t no = 0;
-            for (const std::string& line : read_lines(opts.get("paths-file"), "paths")) {
+            for (const std::string& line : tool::read_lines(opts.get("paths-file"), "Cannot open paths file")) {
                 no++;
                 if (line.empty()) continue;
                 size_t used = 0;
                 unsigned long long v = 0;
                 if (line[0] >= '0' && line[0] <= '9') { try { v = std::stoull(line, &used); } catch (...) { used = 0; } }
-                if (used != line.size()) return fail("Paths file line " + std::to_string(no) + " is not a path id");
+                if (used != line.size()) tool::fail("Paths file line " + std::to_string(no) + " is not a path id");
                 ids.push_back(v);
             }
         }
 
         std::cout << "EDS path subsetting\n";
-        std::cout << "  Input: " << input_file << "\n";
-        std::cout << "  Sources: " << sources_file << "\n";
-        std::cout << "  Output: " << output_file << "\n";
+        std::cout << "  Input: " << f.input << "\n";
+        std::cout << "  Sources: " << f.sources << "\n";
+        std::cout << "  Output: " << f.output << "\n";
         std::cout << "  Output sources: " << sources_out << "\n";
 
         edsx_ctx* ctx = detail::context();
-        const tool::MappedFile eds(input_file, "input"), seds(sources_file, "sources");
+        const tool::MappedFile eds(f.input, "input"), seds(f.sources, "sources");
         if (exclude) {                                           // the complement within 1..P; P, the largest id of the
             uint64_t P = 0, cur = 0;                             // .seds, is read off the text (the library checks the text)
             for (size_t k = 0; k <= seds.size(); k++) {
@@ -101,11 +72,11 @@ int main(int argc, char** argv)
                 if (c >= '0' && c <= '9') cur = cur > (1ull << 40) ? cur : cur * 10 + (c - '0');
                 else { P = std::max(P, cur); cur = 0; }
             }
-            if (P > (1ull << 31)) return fail("The sources name a path id above 2^31");
+            if (P > (1ull << 31)) tool::fail("The sources name a path id above 2^31");
             std::vector<bool> drop(P + 1, false);
-            for (uint64_t p : ids) {
-                if (p == 0 || p > P) return fail("Path id " + std::to_string(p) + " out of range (1.." + std::to_string(P) + ")");
-                if (drop[p]) return fail("Path id " + std::to_string(p) + " given twice");
+            for (uint64_t p : ids) {                             // (not tool::resolve_paths: per id, this check comes before the next one)
+                if (p == 0 || p > P) tool::fail("Path id " + std::to_string(p) + " out of range (1.." + std::to_string(P) + ")");
+                if (drop[p]) tool::fail("Path id " + std::to_string(p) + " given twice");
                 drop[p] = true;
             }
             ids.clear();
@@ -113,31 +84,20 @@ int main(int argc, char** argv)
         }
         detail::Buf e, s;
         edsx_subset_info info;
-        if (edsx_eds_subset(ctx, eds.data(), eds.size(), seds.data(), seds.size(), ids.data(), ids.size(), keep_ids ? 1 : 0, &e.b, &s.b,
-                            &info) != EDSX_OK)
-            return fail(edsx_last_error(ctx));
-        tool::write_bytes(output_file, e.b.data, e.b.size, "output");
+        tool::check(ctx, edsx_eds_subset(ctx, eds.data(), eds.size(), seds.data(), seds.size(), ids.data(), ids.size(), keep_ids ? 1 : 0, &e.b, &s.b, &info));
+        tool::write_bytes(f.output, e.b.data, e.b.size, "output");
         tool::write_bytes(sources_out, s.b.data, s.b.size, "output sources");
         if (opts.has("names")) {
-            const std::vector<std::string> names = read_lines(opts.get("names"), "names");
+            const tool::Names table(opts, "");
             std::vector<uint64_t> kept(ids);
             std::sort(kept.begin(), kept.end());                 // new id = rank in ascending order
             std::string text;
-            for (uint64_t p : kept) {
-                if (p > names.size() || names[p - 1].empty()) return fail("The names file has no name for path " + std::to_string(p));
-                text += names[p - 1] + "\n";
-            }
+            for (uint64_t p : kept) text += table.name_of(p) + "\n";
             tool::write_file(opts.get("names-out"), text, "names output");
         }
         std::cout << "  Paths: " << info.paths_in << " -> " << info.paths_out << ", symbols: " << info.symbols_in << " -> " << info.symbols_out
                   << " (" << info.symbols_removed << " removed, " << info.common_runs_merged << " common runs merged), strings: "
                   << info.strings_in << " -> " << info.strings_out << ", characters: " << info.chars_in << " -> " << info.chars_out << "\n";
         std::cout << "Subsetting complete!\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }

@@ -1,5 +1,6 @@
-// shared by the three tools: the "[Performance]" line the reference prints to stderr
-// (e.g. src/cpp/tools/msa2eds.cpp:18-27) and small file helpers.
+// shared by every tool: the "[Performance]" line the reference prints to stderr
+// (e.g. src/cpp/tools/msa2eds.cpp:18-27), small file helpers and the path list grammar.  The front end of the tools that
+// work on an EDS and its sources is tool_front.hpp.
 #pragma once
 #include "edsparser/common.hpp"
 
@@ -75,11 +76,11 @@ inline void write_bytes(const std::filesystem::path& path, const uint8_t* data, 
     out.write(reinterpret_cast<const char*>(data), static_cast<std::streamsize>(n));
 }
 
-// "1,5,7-9" -> 1 5 7 8 9 (the -p / --paths grammar of eds2fasta and edsparser-subset)
-inline std::vector<uint64_t> parse_paths(const std::string& text)
+// "1,5,7-9" -> 1 5 7 8 9 (the grammar of -p / --paths and of every other path list option; option: its long name)
+inline std::vector<uint64_t> parse_paths(const std::string& text, const std::string& option)
 {
     std::vector<uint64_t> ids;
-    auto bad = [&] { return std::runtime_error("the argument ('" + text + "') for option '--paths' is invalid"); };
+    auto bad = [&] { return std::runtime_error("the argument ('" + text + "') for option '--" + option + "' is invalid"); };
     auto number = [&](const std::string& t) {
         size_t used = 0;
         unsigned long long v = 0;

@@ -37,9 +37,9 @@ VCFStats to_stats(const edsx_vcf_stats& c)
     return s;
 }
 
-struct Session {                                   // edsx_vcf_session, closed on every way out
+struct VcfSession {                                // edsx_vcf_session, closed on every way out
     edsx_vcf_session* h = nullptr;
-    ~Session() { edsx_vcf_session_close(h); }
+    ~VcfSession() { edsx_vcf_session_close(h); }
 };
 
 // --all-chroms: one session, one pair of files per FASTA record that the VCF has record lines for.  false: a contig failed.
@@ -47,7 +47,7 @@ bool transform_all_contigs(const tool::GzInput& vcf_in, const tool::GzInput& fas
                            const std::filesystem::path& out_dir, Length context_length)
 {
     edsx_ctx* ctx = detail::context();
-    Session ses;
+    VcfSession ses;
     int rc = compressed ? edsx_vcf_session_open_z(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size, &ses.h)
                         : edsx_vcf_session_open(ctx, vcf_in.data, vcf_in.size, fasta_in.data, fasta_in.size, &ses.h);
     if (rc != EDSX_OK) detail::throw_status(rc, ctx);

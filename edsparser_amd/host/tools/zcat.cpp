@@ -1,16 +1,12 @@
 // edsx-zcat — inflate a gzip / BGZF file (BGZF blocks on the GPU), or print the block table of a BGZF file.
-#include "edsx.h"
-#include "../cli_util.hpp"
-#include "../device.hpp"
 #include "gz_input.hpp"
+#include "tool_front.hpp"
 
 using namespace edsparser;
 
 int main(int argc, char** argv)
 {
-    Timer timer;
-    timer.start();
-    try {
+    return tool::run([&] {
         cli::Parser opts("Inflate a gzip / BGZF file on the GPU");
         opts.add("help", 'h', false, false, "Show help message");
         opts.add("input", 'i', true, true, "Input file (.gz / .bgz, or plain: copied)");
@@ -23,8 +19,7 @@ int main(int argc, char** argv)
                          "  BGZF (bgzip) files are inflated on the GPU, one wave per block, and every block's\n"
                          "  CRC-32 is checked there.  Any other gzip file is inflated on the host, on one thread.\n"
                          "  --index needs no GPU: it reads the headers and trailers of the blocks only.\n\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         opts.notify();
         const std::filesystem::path input_file = opts.get("input");
@@ -37,8 +32,7 @@ int main(int argc, char** argv)
             std::cout << "#comp_off\tout_off\tcomp_len\tisize\n";
             for (size_t i = 0; i < blocks.b.size / sizeof(edsx_bgzf_block); i++)
                 std::cout << b[i].comp_off << "\t" << b[i].out_off << "\t" << b[i].comp_len << "\t" << b[i].isize << "\n";
-            tool::print_performance(timer);
-            return 0;
+            return;
         }
         tool::GzInput z(in, "input", false);
         detail::Buf text;
@@ -53,11 +47,5 @@ int main(int argc, char** argv)
         if (opts.has("output")) tool::write_bytes(opts.get("output"), out, n, "output");
         else std::cout.write(reinterpret_cast<const char*>(out), static_cast<std::streamsize>(n));
         std::cerr << "  Compression: " << z.describe() << "\n";
-        tool::print_performance(timer);
-        return 0;
-    } catch (const std::exception& e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        tool::print_performance(timer);
-        return 1;
-    }
+    });
 }
