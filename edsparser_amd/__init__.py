@@ -7,3 +7,4 @@ anywhere, but creating a Context without a gfx950 GPU raises.
 """
 from ._capi import Context, EdsxError, MultiGpu, PathSession, VcfSession, bgzf_index, gz_probe, lib_path, load_library, synth_size  # noqa: F401
 from ._capi import MOSAIC_PRIVATE, MOSAIC_SEGMENT  # noqa: F401
+from ._capi import DIV_GROUP, DIV_MAX_GROUPS, DIV_PAIR, DIV_UNITS, DIV_WINDOW  # noqa: F401

@@ -115,6 +115,14 @@ class MosaicInfo(ctypes.Structure):
                                                 "private_symbols", "switches")]
 
 
+class DivInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("groups", "paths", "choice_symbols", "windows", "pairs", "row_words", "extent")]
+
+
+class DivOpts(ctypes.Structure):
+    _fields_ = [("unit", ctypes.c_int), ("size", ctypes.c_uint64), ("step", ctypes.c_uint64), ("max_windows", ctypes.c_uint64)]
+
+
 class SubsetInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("symbols_in", "symbols_out", "strings_in", "strings_out", "chars_in", "chars_out",
                                                 "paths_in", "paths_out", "symbols_removed", "common_runs_merged")]
@@ -324,6 +332,9 @@ def load_library():
     lib.edsx_paths_mosaic.argtypes = [V, V, ctypes.c_size_t, V, ctypes.c_size_t, U64, P(_Buf), P(_Buf), P(MosaicInfo)]
     lib.edsx_eds_mosaic.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, ctypes.c_size_t, V, ctypes.c_size_t,
                                     U64, P(_Buf), P(_Buf), P(MosaicInfo)]
+    lib.edsx_paths_diversity.argtypes = [V, V, V, ctypes.c_size_t, P(DivOpts), P(_Buf), P(_Buf), P(_Buf), P(_Buf), P(DivInfo)]
+    lib.edsx_eds_diversity.argtypes = [V, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, V, V, ctypes.c_size_t, P(DivOpts),
+                                       P(_Buf), P(_Buf), P(_Buf), P(_Buf), P(DivInfo)]
     _LIB = lib
     return lib
 
@@ -400,6 +411,51 @@ def _mosaic_call(ctx, fn, head, targets, donors, max_segments):
         ex.info = _fields(info)
         raise
     return (np.frombuffer(ctx._take(sg), dtype=MOSAIC_SEGMENT), np.frombuffer(ctx._take(to), dtype=np.uint64), _fields(info))
+
+
+# edsx_div_window, edsx_div_group and edsx_div_pair as numpy structured types; the window units (EDSX_DIV_*)
+DIV_WINDOW = [(f, "<u8") for f in ("start", "end", "rank_first", "rank_end")]
+DIV_GROUP = [(f, "<u8") for f in ("segregating", "present")]
+DIV_PAIR = [(f, "<u8") for f in ("diff", "comp")]
+DIV_UNITS = {"symbols": 0, "columns": 1}
+DIV_MAX_GROUPS = 16
+
+
+def _div_call(ctx, fn, head, groups, unit, size, step, max_windows, sfs):
+    """edsx_paths_diversity / edsx_eds_diversity behind their leading arguments -> (windows, groups, pairs, sfs, info):
+    windows (NW,) DIV_WINDOW, groups (NW, G) DIV_GROUP, pairs (NW, G (G + 1) / 2) DIV_PAIR with (g, h), g <= h, row-major,
+    sfs a list of G uint64 arrays of K_g + 1 bins (None unless asked for); an EdsxError carries the info dict, filled in as
+    far as the call got, as its `info`"""
+    import numpy as np
+    if isinstance(unit, str):
+        if unit not in DIV_UNITS:
+            raise ValueError("the unit is one of %s" % ", ".join(sorted(DIV_UNITS)))
+        unit = DIV_UNITS[unit]
+    groups = [list(g) for g in groups] if groups is not None else []
+    off = np.zeros(len(groups) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64) if groups else []
+    ids = np.ascontiguousarray([p for g in groups for p in g], dtype=np.uint64)
+    opts = DivOpts(int(unit), int(size), int(step), int(max_windows))
+    w, g, p, f, info = _Buf(), _Buf(), _Buf(), _Buf(), DivInfo()
+    rc = fn(*head, off.ctypes.data if groups else None, ids.ctypes.data if len(ids) else None, len(groups), ctypes.byref(opts),
+            ctypes.byref(w), ctypes.byref(g), ctypes.byref(p), ctypes.byref(f) if sfs else None, ctypes.byref(info))
+    try:
+        ctx._check(rc)
+    except EdsxError as ex:
+        ex.info = _fields(info)
+        raise
+    info = _fields(info)
+    G, NP = max(info["groups"], 1), max(info["pairs"], 1)
+    spectra = None
+    if sfs:
+        flat = np.frombuffer(ctx._take(f), dtype=np.uint64)
+        sizes = [len(set(x)) + 1 for x in groups] if groups else [info["paths"] + 1]
+        spectra, at = [], 0
+        for n in sizes:
+            spectra.append(flat[at:at + n])
+            at += n
+    return (np.frombuffer(ctx._take(w), dtype=DIV_WINDOW), np.frombuffer(ctx._take(g), dtype=DIV_GROUP).reshape(-1, G),
+            np.frombuffer(ctx._take(p), dtype=DIV_PAIR).reshape(-1, NP), spectra, info)
 
 
 # the metrics of the path distances (EDSX_DIST_*)
@@ -861,6 +917,13 @@ class Context(_Handle):
         sb, sn = _opt(seds)
         return _mosaic_call(self, self._lib.edsx_eds_mosaic, (self._h, eds, len(eds), sb, sn), targets, donors, max_segments)
 
+    # ---- diversity (edsparser-diversity)
+    def eds_diversity(self, eds, seds, groups=None, unit="symbols", size=0, step=0, max_windows=0, sfs=False):
+        """One-shot edsx_eds_diversity: PathSession.diversity on a session opened and closed for this call."""
+        eds = bytes(eds)
+        sb, sn = _opt(seds)
+        return _div_call(self, self._lib.edsx_eds_diversity, (self._h, eds, len(eds), sb, sn), groups, unit, size, step, max_windows, sfs)
+
     # ---- path subsetting (edsparser-subset)
     def eds_subset(self, eds, seds, paths, keep_ids=False):
         """The .eds + .seds restricted to the paths `paths` (ids of 1..P, each once) -> (eds bytes, seds bytes, info dict):
@@ -1262,6 +1325,17 @@ class PathSession(_Handle):
         upper-triangle order are segments[pair_off[q]:pair_off[q + 1]]; info: the dict of edsx_ibs_info.  max_segments
         (0: none): EdsxError when more segments would be reported."""
         return _ibs_call(self._ctx, self._lib.edsx_paths_ibs, (self._h,), paths, min_sites, min_columns, max_segments)
+
+    def diversity(self, groups=None, unit="symbols", size=0, step=0, max_windows=0, sfs=False):
+        """-> (windows, groups, pairs, sfs, info): per window along the EDS the diversity within and between groups of paths
+        (edsx_paths_diversity).  groups: lists of path ids, at most DIV_MAX_GROUPS, disjoint (None: one group of all paths).
+        unit "symbols": windows of `size` choice symbols every `step` (0: size; size 0: one window); "columns": of columns of
+        the alignment view.  windows: (NW,) DIV_WINDOW; groups: (NW, G) DIV_GROUP - segregating sites and present paths summed
+        over the window; pairs: (NW, G (G + 1) / 2) DIV_PAIR for (g, h), g <= h, row-major - the path pairs that both have a
+        string (comp) and those that differ (diff), summed: pi = diff / comp on the diagonal, d_xy off it.  sfs=True: per
+        group the unfolded site frequency spectrum over all complete choice symbols, K_g + 1 bins.  info: the dict of
+        edsx_div_info.  max_windows (0: none): EdsxError when there are more windows."""
+        return _div_call(self._ctx, self._lib.edsx_paths_diversity, (self._h,), groups, unit, size, step, max_windows, sfs)
 
     def mosaic(self, targets=None, donors=None, max_segments=0):
         """(segments, target_off, info): every path of `targets` written as the fewest copies from the paths of `donors`

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libedsx.so")
-SOURCES = ["dev_alloc.hip", "msa_device.hip", "msa_scan.hip", "eds_device.hip", "merge_device.hip", "merge_scan.hip", "vcf_device.hip", "vcf_contig.hip", "bgzf_device.hip", "synth.hip", "genrandom.hip", "genvcf.hip", "multi_gpu.hip", "vcf_multi.hip", "merge_multi.hip", "query_device.hip", "locate_device.hip", "path_device.hip", "lift_device.hip", "subset_device.hip", "slice_device.hip", "dist_device.hip", "ld_device.hip", "ibs_device.hip", "mosaic_device.hip", "gfa_device.hip", "vcf_export_device.hip", "capi.hip"]
+SOURCES = ["dev_alloc.hip", "msa_device.hip", "msa_scan.hip", "eds_device.hip", "merge_device.hip", "merge_scan.hip", "vcf_device.hip", "vcf_contig.hip", "bgzf_device.hip", "synth.hip", "genrandom.hip", "genvcf.hip", "multi_gpu.hip", "vcf_multi.hip", "merge_multi.hip", "query_device.hip", "locate_device.hip", "path_device.hip", "lift_device.hip", "subset_device.hip", "slice_device.hip", "dist_device.hip", "ld_device.hip", "ibs_device.hip", "mosaic_device.hip", "div_device.hip", "gfa_device.hip", "vcf_export_device.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # per-source flags.  msa_scan.hip: machine scheduler off - the column scan's loads stay in source order (bench shape: scan
 # 26.5 instead of 26.9 ms; the same flag on msa_device.hip costs its emitters 0.2 ms: alternating A/B runs, EXPERIMENTS.md)

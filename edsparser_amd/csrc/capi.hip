@@ -57,6 +57,7 @@ struct edsx_ctx {
     KernelTimes ld_times;                    // edsx_paths_ld, likewise
     KernelTimes ibs_times;                   // edsx_paths_ibs, likewise
     KernelTimes mosaic_times;                // edsx_paths_mosaic, likewise
+    KernelTimes div_times;                   // edsx_paths_diversity, likewise
     VcfPipeline vcf;
     GenPipeline gen;
     GenVcfPipeline genvcf;
@@ -428,6 +429,7 @@ void edsx_set_timing(edsx_ctx* ctx, int enabled)
     ctx->ld_times.set(enabled != 0);
     ctx->ibs_times.set(enabled != 0);
     ctx->mosaic_times.set(enabled != 0);
+    ctx->div_times.set(enabled != 0);
 }
 int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* launches, int cap)
 {
@@ -440,7 +442,8 @@ int edsx_get_timing(edsx_ctx* ctx, const char** names, float* total_ms, int* lau
     n += ctx->dist_times.get(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->ld_times.get(names + n, total_ms + n, launches + n, cap - n);
     n += ctx->ibs_times.get(names + n, total_ms + n, launches + n, cap - n);
-    return n + ctx->mosaic_times.get(names + n, total_ms + n, launches + n, cap - n);
+    n += ctx->mosaic_times.get(names + n, total_ms + n, launches + n, cap - n);
+    return n + ctx->div_times.get(names + n, total_ms + n, launches + n, cap - n);
 }
 
 int edsx_msa_transform(edsx_ctx* ctx, const uint8_t* msa, size_t msa_size, uint32_t context_len,
@@ -1335,6 +1338,57 @@ int edsx_eds_mosaic(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
     edsx_paths_session* s = nullptr;
     return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
                       [&] { return edsx_paths_mosaic(s, targets, nt, donors, nd, max_segments, segments, target_off, info); });
+}
+
+// ---- edsparser-diversity (div_device.hip, div_core.hpp)
+static_assert(sizeof(DivInfo) == sizeof(edsx_div_info) && offsetof(DivInfo, extent) == offsetof(edsx_div_info, extent), "edsx_div_info is DivInfo");
+static_assert(sizeof(DivOpts) == sizeof(edsx_div_opts) && offsetof(DivOpts, max_windows) == offsetof(edsx_div_opts, max_windows),
+              "edsx_div_opts is DivOpts");
+static_assert(sizeof(DivWindow) == sizeof(edsx_div_window) && offsetof(DivWindow, rank_end) == offsetof(edsx_div_window, rank_end),
+              "edsx_div_window is DivWindow");
+static_assert(sizeof(DivGroup) == sizeof(edsx_div_group) && offsetof(DivGroup, present) == offsetof(edsx_div_group, present),
+              "edsx_div_group is DivGroup");
+static_assert(sizeof(DivPair) == sizeof(edsx_div_pair) && offsetof(DivPair, comp) == offsetof(edsx_div_pair, comp), "edsx_div_pair is DivPair");
+static_assert(EDSX_DIV_SYMBOLS == diversity::SYMBOLS && EDSX_DIV_COLUMNS == diversity::COLUMNS && EDSX_DIV_MAX_GROUPS == diversity::MAX_GROUPS,
+              "EDSX_DIV_*");
+
+int edsx_paths_diversity(edsx_paths_session* s, const uint64_t* group_off, const uint64_t* group_ids, size_t n_groups, const edsx_div_opts* opts,
+                         edsx_buf* windows, edsx_buf* groups, edsx_buf* pairs, edsx_buf* sfs, edsx_div_info* info)
+{
+    clear(windows, groups, pairs, sfs);
+    zero(info);
+    if (!s) return EDSX_ERR_INVALID_PARAMETER;
+    return guarded(s->ctx, [&] {
+        if (!windows || !groups || !pairs || !opts || (n_groups && (!group_off || (group_off[n_groups] && !group_ids))))
+            throw ParamError("null argument");
+        DivOpts o;
+        std::memcpy(&o, opts, sizeof(o));
+        DivInfo di;
+        HostBytes w, g, p, f;
+        try {
+            s->p.diversity(reinterpret_cast<const u64*>(group_off), reinterpret_cast<const u64*>(group_ids), n_groups, o, w, g, p, sfs ? &f : nullptr,
+                           di, &s->ctx->div_times, nullptr);
+        } catch (...) {                                          // as far as the call got
+            if (info) std::memcpy(info, &di, sizeof(di));
+            throw;
+        }
+        if (info) std::memcpy(info, &di, sizeof(di));
+        give(windows, w);
+        give(groups, g);
+        give(pairs, p);
+        if (sfs) give(sfs, f);
+    });
+}
+
+int edsx_eds_diversity(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size, const uint64_t* group_off,
+                       const uint64_t* group_ids, size_t n_groups, const edsx_div_opts* opts, edsx_buf* windows, edsx_buf* groups,
+                       edsx_buf* pairs, edsx_buf* sfs, edsx_div_info* info)
+{
+    clear(windows, groups, pairs, sfs);
+    zero(info);
+    edsx_paths_session* s = nullptr;
+    return in_session(edsx_paths_open(ctx, eds, eds_size, seds, seds_size, &s), s, edsx_paths_close,
+                      [&] { return edsx_paths_diversity(s, group_off, group_ids, n_groups, opts, windows, groups, pairs, sfs, info); });
 }
 
 // ---- eds2vcf (vcf_export_device.hip)

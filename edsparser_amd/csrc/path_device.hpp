@@ -2,10 +2,12 @@
 // EDS with sources, as FASTA.  The inverse of the transforms: path s + 1 of msa2eds(A) is row s of A without its gaps.
 // The session's coordinate lift, region slice, path distances and linkage disequilibrium: lift_device.hip,
 // slice_device.hip, dist_device.hip, ld_device.hip; the segments two paths share: ibs_device.hip; a path as a mosaic of
-// other paths: mosaic_device.hip (where an operation goes).
+// other paths: mosaic_device.hip; windowed diversity between groups of paths: div_device.hip (where an operation
+// goes).
 #pragma once
 
 #include "dist_core.hpp"
+#include "div_core.hpp"
 #include "eds_device.hpp"
 #include "ibs_core.hpp"
 #include "kernel_times.hpp"
@@ -59,6 +61,13 @@ typedef ibs::Segment IbsSegment;
 // edsx_mosaic_info, edsx_mosaic_segment (include/edsx.h)
 struct MosaicInfo { u64 targets = 0, donors = 0, choice_symbols = 0, class_columns = 0, segments = 0, private_segments = 0, private_symbols = 0, switches = 0; };
 typedef mosaic::Segment MosaicSegment;
+
+// edsx_div_opts, edsx_div_info, edsx_div_window, edsx_div_group, edsx_div_pair (include/edsx.h)
+struct DivOpts { int unit; u64 size, step, max_windows; };
+struct DivInfo { u64 groups = 0, paths = 0, choice_symbols = 0, windows = 0, pairs = 0, row_words = 0, extent = 0; };
+struct DivWindow { u64 start, end, rank_first, rank_end; };
+struct DivGroup { u64 segregating, present; };
+struct DivPair { u64 diff, comp; };
 
 // One EDS + sEDS kept tokenised in HBM in a DeviceEds of its own (other calls on the context do not touch it).
 class PathPipeline {
@@ -139,6 +148,17 @@ public:
     void mosaic(const u64* targets, size_t nt, const u64* donors, size_t nd, u64 max_segments, HostBytes& segments,
                 HostBytes& target_off, MosaicInfo& info, KernelTimes* times, hipStream_t st);
 
+    // Windowed diversity within and between groups of paths (div_core.hpp, div_device.hip).  The groups as a CSR
+    // over path ids (group_off: n_groups + 1 entries); n_groups == 0: one group of all paths; a duplicate inside a group counts
+    // once.  More than diversity::MAX_GROUPS groups, an id outside 1..P, an empty group, an id in two groups, a unit that is
+    // neither SYMBOLS nor COLUMNS, or more windows than opts.max_windows (0: none; from the counts, before anything is
+    // allocated): ParamError.  windows: NW DivWindow; groups: NW x G DivGroup; pairs: NW x G (G + 1) / 2 DivPair, (g, h) with
+    // g <= h row-major; sfs (nullable): sum (K_g + 1) u64, the unfolded spectrum of every group over all choice symbols.  The
+    // per-symbol sums and the records have to fit budget(2), and nc max K_g^2 has to stay below 2^63: LimitError.  info is
+    // filled in as far as the call got.
+    void diversity(const u64* group_off, const u64* group_ids, size_t n_groups, const DivOpts& opts, HostBytes& windows, HostBytes& groups,
+                   HostBytes& pairs, HostBytes* sfs, DivInfo& info, KernelTimes* times, hipStream_t st);
+
 private:
     // what a feature keeps with the session from its first call until the session closes (`ready`), and its buffers
     // walks: seg_rank (segment_ranks, m + 1); the token bytes of the fixed symbols, scanned (cum_tok, n + 1), their sum and
@@ -178,6 +198,10 @@ private:
     // and donor (rowof), the donor rows word-major in request order (rt), the alive bits per (target, lane) (alive), the
     // segments per target, scanned: target_off (cnt), and the records
     struct MosaicState { bool ready = false; DevBuf rowof, rt, alive, cnt, seg; };
+
+    // diversity: per call the rows of the groups (masks, G x WP), per choice symbol the NA sums, array-major and scanned
+    // (arr), the walk rows of the lane groups when a row does not fit the registers (seen), the spectrum and the records
+    struct DivState { DevBuf masks, arr, seen, sfs, win, grp, pr; };
 
     // ---- session and choice tables
     void check_ids(const u64* ids, size_t n) const;
@@ -228,6 +252,7 @@ private:
     LdState ld_;
     IbsState ibs_;
     MosaicState mosaic_;
+    DivState div_;
 };
 
 } // namespace edsx

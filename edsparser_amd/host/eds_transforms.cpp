@@ -3,6 +3,7 @@
 #include "edsparser/transforms/eds_transforms.hpp"
 #include "device.hpp"
 
+#include <algorithm>
 #include <cstring>
 
 namespace edsparser {
@@ -221,6 +222,50 @@ PathMosaic path_mosaic(std::istream& eds_in, std::istream& seds_in, const std::v
     edsx_buf_free(&ob);
     d.targets = mi.targets; d.donors = mi.donors; d.choice_symbols = mi.choice_symbols;
     d.private_segments = mi.private_segments; d.private_symbols = mi.private_symbols; d.switches = mi.switches;
+    return d;
+}
+
+PathDiversity path_diversity(std::istream& eds_in, std::istream& seds_in, const std::vector<std::vector<int>>& groups, const DiversityOptions& options)
+{
+    const std::string eds = detail::slurp(eds_in), seds = detail::slurp(seds_in);
+    std::vector<uint64_t> off(1, 0), ids;
+    for (const auto& g : groups) {
+        for (int p : g) ids.push_back(p < 0 ? 0 : static_cast<uint64_t>(p));      // (0 is out of range as well)
+        off.push_back(ids.size());
+    }
+    edsx_ctx* ctx = detail::context();
+    edsx_div_opts o;
+    o.unit = static_cast<int>(options.unit); o.size = options.size; o.step = options.step; o.max_windows = options.max_windows;
+    detail::Buf wb, gb, pb, fb;
+    edsx_div_info di;
+    const int rc = edsx_eds_diversity(ctx, reinterpret_cast<const uint8_t*>(eds.data()), eds.size(), reinterpret_cast<const uint8_t*>(seds.data()),
+                                      seds.size(), off.data(), ids.data(), groups.size(), &o, &wb.b, &gb.b, &pb.b, options.sfs ? &fb.b : nullptr, &di);
+    if (rc != EDSX_OK) detail::throw_status(rc, ctx);
+    PathDiversity d;
+    static_assert(sizeof(DiversityWindow) == sizeof(edsx_div_window) && sizeof(DiversityGroup) == sizeof(edsx_div_group) &&
+                  sizeof(DiversityPair) == sizeof(edsx_div_pair), "the records of edsx_paths_diversity");
+    d.windows.resize(wb.b.size / sizeof(DiversityWindow));
+    d.groups.resize(gb.b.size / sizeof(DiversityGroup));
+    d.pairs.resize(pb.b.size / sizeof(DiversityPair));
+    if (wb.b.size) std::memcpy(d.windows.data(), wb.b.data, wb.b.size);
+    if (gb.b.size) std::memcpy(d.groups.data(), gb.b.data, gb.b.size);
+    if (pb.b.size) std::memcpy(d.pairs.data(), pb.b.data, pb.b.size);
+    d.n_groups = di.groups; d.paths = di.paths; d.choice_symbols = di.choice_symbols; d.n_pairs = di.pairs; d.extent = di.extent;
+    for (const auto& g : groups) {                               // K_g: the distinct ids
+        std::vector<int> u(g);
+        std::sort(u.begin(), u.end());
+        d.group_paths.push_back(static_cast<uint64_t>(std::unique(u.begin(), u.end()) - u.begin()));
+    }
+    if (groups.empty()) d.group_paths.push_back(di.paths);
+    if (options.sfs) {
+        const uint64_t* f = reinterpret_cast<const uint64_t*>(fb.b.data);
+        size_t at = 0;
+        for (uint64_t K : d.group_paths) {
+            const size_t n = fb.b.size ? K + 1 : 0;
+            d.sfs.emplace_back(f + at, f + at + n);
+            at += n;
+        }
+    }
     return d;
 }
 

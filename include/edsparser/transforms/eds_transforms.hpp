@@ -136,6 +136,37 @@ struct PathMosaic {
 PathMosaic path_mosaic(std::istream& eds, std::istream& seds, const std::vector<int>& targets = {}, const std::vector<int>& donors = {},
                        const MosaicOptions& options = MosaicOptions());
 
+// edsparser-diversity: per window along the EDS the diversity within and between groups of paths (no group: one group of
+// all paths 1..P; a duplicate inside a group counts once; at most 16 disjoint groups).  Windows of `size` coordinates every
+// `step` (0: size; size 0: one window), coordinates being choice symbols or columns of the alignment view.  Per (window,
+// group): the segregating choice symbols and the paths present, summed; per (window, g <= h), row-major: the path pairs that
+// both have a string (comp) and those whose strings differ (diff), summed - pi = diff / comp on the diagonal, d_xy off it
+// (edsx_paths_diversity states the rules in full; edsparser_amd/host/div_stats.hpp derives pi, d_xy, F_ST, theta_W and
+// Tajima's D from the integers).  sfs: per group K_g + 1 bins of the unfolded spectrum over all complete choice symbols.
+// std::invalid_argument for a path outside 1..P, an empty group, a path in two groups, more than 16 groups and more
+// windows than max_windows.
+enum class DiversityUnit { SYMBOLS = 0, COLUMNS = 1 };
+struct DiversityOptions {
+    DiversityUnit unit = DiversityUnit::SYMBOLS;
+    uint64_t size = 0, step = 0;
+    uint64_t max_windows = 0;                  // 0: no limit
+    bool sfs = false;
+};
+struct DiversityWindow { uint64_t start, end, rank_first, rank_end; };
+struct DiversityGroup { uint64_t segregating, present; };
+struct DiversityPair { uint64_t diff, comp; };
+struct PathDiversity {
+    std::vector<DiversityWindow> windows;      // NW
+    std::vector<DiversityGroup> groups;        // NW x G
+    std::vector<DiversityPair> pairs;          // NW x G (G + 1) / 2
+    std::vector<std::vector<uint64_t>> sfs;    // G spectra, with options.sfs
+    std::vector<uint64_t> group_paths;         // K_g
+    size_t n_groups = 0, paths = 0, choice_symbols = 0, n_pairs = 0, extent = 0;
+    static size_t pair_index(size_t G, size_t g, size_t h) { return g * G - g * (g + 1) / 2 + h; }     // g <= h
+};
+PathDiversity path_diversity(std::istream& eds, std::istream& seds, const std::vector<std::vector<int>>& groups = {},
+                             const DiversityOptions& options = DiversityOptions());
+
 // edsparser-subset: the EDS with sources restricted to the given paths (ids of 1..P, each once), as FULL .eds text and
 // .seds text, each with a trailing line feed.  A string is kept when its set holds 0 or one of the paths; symbols without
 // a kept string go, a symbol whose only kept string is universal or holds every kept path becomes common, and runs of

@@ -728,6 +728,57 @@ int edsx_eds_mosaic(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const ui
                     size_t nt, const uint64_t* donors, size_t nd, uint64_t max_segments, edsx_buf* segments, edsx_buf* target_off,
                     edsx_mosaic_info* info);
 
+/* ---- edsparser-diversity: windowed diversity within and between groups of paths (div_device.hip, div_core.hpp) ----
+ * Input: a path session and G >= 1 groups of path ids as a CSR: group g holds group_ids[group_off[g] .. group_off[g + 1]);
+ * n_groups == 0 means one group of all paths 1..P.  A duplicate id inside a group counts once; M_g is the set of group g and
+ * K_g = |M_g|.  All of the following are EDSX_ERR_INVALID_PARAMETER: an id of 0 or above P, "Path id <p> out of range
+ * (1..<P>)"; an empty group, "Group <g> is empty"; an id in two groups, "Path id <p> is in groups <a> and <b>", for the
+ * lowest such p and its two lowest groups; more than EDSX_DIV_MAX_GROUPS groups.  Group pairs are (g, h) with g <= h in
+ * row-major order, NP = G (G + 1) / 2 of them.
+ *   Per choice symbol.  The choice symbols r = 0..nc-1 and the carrier rule are those of edsx_paths_ld: T(r, j) is the set
+ *      of paths that take string j of r, the first string in file order whose source set holds the path or 0; equal texts
+ *      are not merged.  c_g(r, j) = |T(r, j) & M_g| and n_g(r) = sum_j c_g(r, j).
+ *      comp_gh(r): the pairs (p in M_g, q in M_h) that both take a string at r; unordered with p != q when g == h.
+ *      diff_gh(r): those of them whose string indices differ.
+ *      seg_g(r) = 1 iff at least two strings of r have a carrier in M_g.  present_g(r) = n_g(r).
+ *      (Closed forms: between groups comp = n_g n_h and diff = n_g n_h - sum_j c_gj c_hj; within a group comp =
+ *      n_g (n_g - 1) / 2 and diff = (n_g^2 - sum_j c_gj^2) / 2.)
+ *   Windows.  unit EDSX_DIV_SYMBOLS: the coordinate of r is r and the extent E = nc.  EDSX_DIV_COLUMNS: the coordinate is
+ *      min(col[i], E - 1), i the symbol index of r, col the first column of a symbol in the view of edsx_paths_align, W its
+ *      number of columns and E = max(W, 1).  Window k covers the coordinates [k step, min(k step + size, E)) for every k
+ *      with k step < E; step == 0 means step = size; size == 0 means the one window [0, E).  A window without a choice
+ *      symbol is still a record, with zero sums.  nc = 0 gives empty buffers and status 0.  max_windows (0: none) is held
+ *      against the window count before anything is allocated: "Diversity has <n> windows, above the limit of <max>".
+ *   Output, all edsx_buf, sized exactly, freed by edsx_buf_free.  windows: NW edsx_div_window, rank_first and rank_end the
+ *      choice symbols [rank_first, rank_end) of the window.  groups: NW x G edsx_div_group.  pairs: NW x NP edsx_div_pair.
+ *      Every field is the sum over the window's choice symbols.  sfs (may be NULL): sum over g of (K_g + 1) uint64_t, group
+ *      after group; sfs[g][c] is the number of (r, j >= 1) over ALL choice symbols with n_g(r) = K_g and c_g(r, j) = c: the
+ *      unfolded spectrum against string 0 on complete sites, bin 0 kept.  info (may be NULL), filled in as far as the call
+ *      got, on errors too: groups G, paths sum K_g, choice_symbols nc, windows NW, pairs NP, row_words ceil(P / 64), extent E.
+ *   Limits.  The NA = 2 G + 2 NP sums the device keeps per choice symbol (8 NA (nc + 1) bytes), the records and, above
+ *      8192 paths, the walk rows must fit the session's budget: otherwise EDSX_ERR_BUILD_FAILED, with the sizes and the
+ *      budget in the text; slabs of the symbol range are not built.  nc max_g K_g^2 >= 2^63 is refused the same way: the
+ *      sums are 64-bit.  Every error leaves the session usable.
+ *   Derived statistics (pi, d_xy, F_ST, Watterson's theta, Tajima's D) are host arithmetic over these integers:
+ *      edsparser_amd/host/div_stats.hpp.
+ * edsx_paths_last_timing: copy_ms the k_div_sites launches, scan_ms the scans and the window kernel, bytes_written the
+ * records and the spectrum; under edsx_set_timing the kernels come back by name from edsx_get_timing. */
+#define EDSX_DIV_SYMBOLS 0
+#define EDSX_DIV_COLUMNS 1
+#define EDSX_DIV_MAX_GROUPS 16
+typedef struct { int unit; uint64_t size, step, max_windows; } edsx_div_opts;
+typedef struct { uint64_t groups, paths, choice_symbols, windows, pairs, row_words, extent; } edsx_div_info;
+typedef struct { uint64_t start, end, rank_first, rank_end; } edsx_div_window;
+typedef struct { uint64_t segregating, present; } edsx_div_group;
+typedef struct { uint64_t diff, comp; } edsx_div_pair;
+int edsx_paths_diversity(edsx_paths_session* s, const uint64_t* group_off, const uint64_t* group_ids, size_t n_groups,
+                         const edsx_div_opts* opts, edsx_buf* windows, edsx_buf* groups, edsx_buf* pairs, edsx_buf* sfs,
+                         edsx_div_info* info);
+/* open + diversity + close */
+int edsx_eds_diversity(edsx_ctx* ctx, const uint8_t* eds, size_t eds_size, const uint8_t* seds, size_t seds_size,
+                       const uint64_t* group_off, const uint64_t* group_ids, size_t n_groups, const edsx_div_opts* opts,
+                       edsx_buf* windows, edsx_buf* groups, edsx_buf* pairs, edsx_buf* sfs, edsx_div_info* info);
+
 /* ---- edsparser-subset: an EDS with sources restricted to a keep set K of its paths (subset_device.hip) ----
  * Input: an .eds + .seds, parsed exactly as edsx_paths_open parses them (same tokenisers, statuses and error texts), and
  * n path ids, the keep set K.  P is the largest path id in the .seds.
