@@ -2,7 +2,7 @@
 
 One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link; three more
 libraries for the tests only (libedsx_smallstacks.so, libedsx_guard.so, libedsx_weakhash.so) relink the same objects
-with one source each compiled with other flags.
+with one source each compiled with other flags, and a fifth (libedsx_primitives.so) is one translation unit of the tests' own.
 """
 import os
 import subprocess
@@ -32,6 +32,11 @@ GUARD_FLAGS = {"dev_alloc.hip": ["-DEDSX_GUARD"]}
 # the hashes decide over real collisions (tests/test_msa_weakhash_gpu.py).  Never loaded by the product.
 WEAKHASH_LIB = os.path.join(HERE, "libedsx_weakhash.so")
 WEAKHASH_FLAGS = {"msa_device.hip": ["-DEDSX_MSA_HASH_BITS=1"]}
+# A fifth one, also for the tests only: plain C launchers around the shared device primitives of csrc/dev_util.hpp and
+# csrc/byte_ops.hpp (scans, set-id text, bisection, 16-byte and wave helpers, the pinned download), one translation unit
+# linked on its own (tests/hip/primitives_harness.hip, tests/test_primitives_gpu.py).  Never loaded by the product.
+PRIM_LIB = os.path.join(HERE, "libedsx_primitives.so")
+PRIM_SRC = os.path.join(HERE, "..", "tests", "hip", "primitives_harness.hip")
 
 
 def _headers():
@@ -89,6 +94,12 @@ def build(force=False, verbose=False):
                 _compile(src, obj, EXTRA_FLAGS.get(name, []) + extra, verbose)
         if force or _newer(lib, tobjs):
             _link(tobjs, lib, verbose)
+    if os.path.exists(PRIM_SRC) and (force or _newer(PRIM_LIB, [PRIM_SRC] + [h for h in hdrs if h.endswith(".hpp")])):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cmd = [hipcc] + FLAGS + ["-I", CSRC, "-shared", PRIM_SRC, "-o", PRIM_LIB, "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
     return LIB
 
 

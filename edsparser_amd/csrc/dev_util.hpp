@@ -223,7 +223,9 @@ __device__ __forceinline__ u32 byte_of(const uint4& v, int i)
 // ---- device-wide scans on u64 arrays, element count read from device memory -----------------
 // OP 0: exclusive sum (out[i] = sum(in[0..i)), *total = sum of all)
 // OP 1: inclusive max (out[i] = max(in[0..i]),  *total = max of all)
-// in/out may alias (they are not __restrict__: callers scan in place).  Three grid-stride kernels; tmp holds one u64 per SCAN_TILE elements.
+// in/out may alias (they are not __restrict__: callers scan in place).  Three grid-stride kernels.  tmp: exactly
+// ceil(n / SCAN_TILE) u64, one sum per tile; nothing behind them is read or written, and n = 0 touches none
+// (tests/test_primitives_gpu.py gives the scans this much and no more).
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;   // 2048
@@ -345,7 +347,9 @@ inline void exclusive_scan_u64(const u64* in, u64* out, const u64* d_n, u64* d_t
 }
 
 // ---- N exclusive sums over arrays of the same length in ONE pass of the three kernels (the MSA planner scans two or
-// three size / flag arrays per step: a third of the launches and of the tail latencies).  tmp: N * (n / SCAN_TILE + 2) u64.
+// three size / flag arrays per step: a third of the launches and of the tail latencies).  in[k] / out[k] may alias.
+// tmp: exactly N * (ceil(n / SCAN_TILE) + 1) u64: the tile sums of array k begin at k * (ceil(n / SCAN_TILE) + 1), and the last
+// slot of each stretch is never touched (N * (n / SCAN_TILE + 2), the callers' form, is at least this much).
 template <int N> struct ScanSet { const u64* in[N]; u64* out[N]; u64* total[N]; };
 
 template <int N>
