@@ -208,9 +208,9 @@ bool msa_transform_in_batches(edsx_ctx* ctx, const uint8_t* msa, const MsaLayout
                               edsx_buf* eds, edsx_buf* seds)
 {
     if (!ctx->mini) ctx->mini.reset(new MsaPipeline());
-    const BatchResources R{&ctx->msa, ctx->mini.get(), &ctx->d_in, &ctx->d_eds, &ctx->d_seds, &ctx->d_mini, &ctx->host_tmp};
+    const SlabWorker w{&ctx->msa, ctx->mini.get(), &ctx->d_in, &ctx->d_eds, &ctx->d_seds, &ctx->d_mini, &ctx->host_tmp};
     HostBytes e, q;
-    if (!msa_transform_batched(R, msa, lay, context_len, K, e, q, nullptr)) return false;
+    if (!msa_transform_batched(w, msa, lay, context_len, K, e, q, nullptr)) return false;
     give(eds, e);
     give(seds, q);
     return true;

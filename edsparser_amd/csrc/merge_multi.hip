@@ -144,11 +144,8 @@ void MultiMsa::run_rank_merge(int r, MergeShared& sh)
                 if (!g3[3 * k + 2]) why = 5;
             if (!why) {
                 // ---- 5. rank 0 allocates, every rank copies its piece to its offset
-                u64 eoff = 0, soff = 0, etot = 0, stot = 0;
-                for (int k = 0; k < N; k++) {
-                    if (k < r) { eoff += g3[3 * k]; soff += g3[3 * k + 1]; }
-                    etot += g3[3 * k]; stot += g3[3 * k + 1];
-                }
+                u64 eoff, soff, etot, stot;
+                piece_offsets(g3, 3, r, eoff, soff, etot, stot);
                 if (!phase([&] {
                         if (r != 0) return;
                         sh.leds->take(etot); sh.sout->take(stot);

@@ -7,12 +7,16 @@
 // (SURVEY §8(e)): an all-gather of twelve numbers per rank (the edge descriptors), and - only when a VARIANT run
 // crosses a boundary - an all-gather of the raw boundary columns, from which the left-most rank recomputes that
 // segment.  With a context length l > 0 every boundary is recomputed between the nearest standalone common runs of at
-// least l columns on either side (run_rank_leds in multi_gpu.hip).  The exchanges are ncclAllGather calls on one communicator per rank (RcclExchange); LocalExchange moves the
-// same bytes between the rank threads directly and exists so that the whole path can be tested with several contexts
-// sharing ONE GPU (RCCL does not run two ranks on one device).
+// least l columns on either side (the anchors).  What is decided on the host - the geometry of the image, the cuts, the
+// descriptors and which bytes and boundaries follow from them (SlabStitch) - is msa_slabs.hpp, without a HIP include
+// and tested on the CPU; MultiMsa::run_rank (one rank, either context length) and msa_transform_batched (the same slabs
+// one after the other on one GPU) in multi_gpu.hip run on it.  The exchanges are ncclAllGather calls on one
+// communicator per rank (RcclExchange); LocalExchange moves the same bytes between the rank threads directly and exists
+// so that the whole path can be tested with several contexts sharing ONE GPU (RCCL does not run two ranks on one device).
 #pragma once
 
 #include "msa_device.hpp"
+#include "msa_slabs.hpp"
 #include "rank_barrier.hpp"
 #include "merge_device.hpp"
 #include "merge_scan.hpp"
@@ -27,23 +31,6 @@
 
 namespace edsx {
 
-struct SlabEdges {              // twelve u64, exchanged as they are
-    u64 n_segments, cols, eds_bytes, seds_bytes;
-    u64 first_is_variant, first_cols, first_eds_bytes, first_seds_bytes;
-    u64 last_is_variant, last_cols, last_eds_bytes, last_seds_bytes;
-};
-struct SlabChain { int first, last; bool variant; };      // a run of one type over slabs first .. last
-struct SlabAction {             // what a rank does to its slab text: bytes dropped at both ends, chains it recomputes
-    u64 front_eds = 0, front_seds = 0, back_eds = 0, back_seds = 0;
-    std::vector<int> owns;
-};
-struct StitchPlan { std::vector<SlabChain> chains; std::vector<SlabAction> actions; };
-StitchPlan plan_stitch(const std::vector<SlabEdges>& edges);               // pure host logic, the same on every rank
-
-// geometry of a plain uniform FASTA alignment image; ok == false: not partitioned (the unpartitioned transform words the error)
-struct MsaLayout { bool ok = false; std::vector<u64> start; u64 draw = 0, lw = 0, L = 0; };
-MsaLayout msa_layout(const uint8_t* f, size_t n);
-
 // columns [c0, c1) of every row as a one-line-per-row image in HBM, every row on a multiple of 128 bytes (see multi_gpu.hip)
 struct RowImage { u64 rows = 0, cols = 0, hdr0 = 0, hdr = 0, bytes = 0; };
 RowImage upload_row_image(const uint8_t* fasta, const MsaLayout& lay, u64 c0, u64 c1, DevBuf& d_img, std::vector<uint8_t>& host_tmp,
@@ -54,11 +41,14 @@ void msa_image_to_text(MsaPipeline& p, const DevBuf& d_img, size_t n, uint32_t l
 void msa_transform_plain(MsaPipeline& p, const uint8_t* msa, size_t n, uint32_t l, DevBuf& d_img, DevBuf& d_eds, DevBuf& d_seds,
                          HostBytes& eds, HostBytes& seds, hipStream_t st);
 
+// What transforms slabs on one device, the owner's members: the slab's pipeline and a second one through which boundary
+// segments are recomputed (the slab's plan stays), the slab image, its text, the mini alignment, and host scratch
+struct SlabWorker { MsaPipeline* slab; MsaPipeline* mini; DevBuf* d_img; DevBuf* d_eds; DevBuf* d_seds; DevBuf* d_mini; std::vector<uint8_t>* host; };
+
 // msa2eds in K column batches on one GPU (working set of one slab; see multi_gpu.hip).  false: not batched - the image is
 // not a plain uniform alignment, the batches would be too narrow, or (l > 0) a slab has no standalone common runs to
 // anchor the stitch on; nothing has been written to eds / seds then.
-struct BatchResources { MsaPipeline* slab; MsaPipeline* mini; DevBuf* d_img; DevBuf* d_eds; DevBuf* d_seds; DevBuf* d_mini; std::vector<uint8_t>* host_tmp; };
-bool msa_transform_batched(const BatchResources& R, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, int K,
+bool msa_transform_batched(const SlabWorker& w, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, int K,
                            HostBytes& eds, HostBytes& seds, hipStream_t st);
 
 // all ranks call with `bytes` bytes each; `all` receives world * bytes bytes in rank order
@@ -113,8 +103,7 @@ private:
     struct Rank;
     struct VcfShared;
     struct MergeShared;
-    void run_rank(int r, const uint8_t* fasta, size_t n, const MsaLayout& lay, HostBytes& eds, HostBytes& seds);
-    void run_rank_leds(int r, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, HostBytes& eds, HostBytes& seds);
+    void run_rank(int r, const uint8_t* fasta, const MsaLayout& lay, uint32_t l, HostBytes& eds, HostBytes& seds);
     void run_rank_vcf(int r, VcfShared& sh);
     void run_rank_merge(int r, MergeShared& sh);
     // one_rank(r) on a thread per rank (multi_gpu.hip); throws what the failed rank threw (errors[rank]) or a DeviceError
@@ -126,8 +115,6 @@ private:
     bool partitioned_ = false;
     bool no_anchor_ = false;             // l > 0: some slab has no standalone common runs to anchor the stitch on
     int chains_ = 0;
-    // shared between the rank threads of one call
-    std::vector<u64> piece_e_, piece_s_;
     VcfMultiInfo vcf_info_;
     MergeMultiInfo merge_info_;
 };
@@ -136,7 +123,8 @@ struct MultiMsa::Rank {
     int device = 0;
     MsaPipeline slab, mini;              // the slab's pipeline; boundary segments are recomputed through a second one
     DevBuf d_img, d_eds, d_seds, d_mini;
-    std::vector<uint8_t> host_img;       // wrapped rows: the slab image is put together on the host
+    std::vector<uint8_t> host_img;       // wrapped rows: the slab image is put together on the host; mini alignments
+    SlabWorker worker() { return SlabWorker{&slab, &mini, &d_img, &d_eds, &d_seds, &d_mini, &host_img}; }
     std::string error;
     std::unique_ptr<VcfPipeline> vcf;    // vcf_transform: created on first use
     std::unique_ptr<MergePipeline> merge;   // (rank 0, context length > 0; every rank in leds_merge_multi)

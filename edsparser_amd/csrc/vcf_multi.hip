@@ -218,11 +218,8 @@ void MultiMsa::run_rank_vcf(int r, VcfShared& sh)
     const u64 my[5] = {pe.size, ps.size, rc.variant_groups, moved, h2d};
     std::vector<u64> piece(5 * (size_t)N);
     if (!phase([&] { xch_->all_gather(r, my, sizeof(my), piece.data()); })) return;
-    u64 eoff = 0, soff = 0, etot = 0, stot = 0;
-    for (int k = 0; k < N; k++) {
-        if (k < r) { eoff += piece[5 * k]; soff += piece[5 * k + 1]; }
-        etot += piece[5 * k]; stot += piece[5 * k + 1];
-    }
+    u64 eoff, soff, etot, stot;
+    piece_offsets(piece, 5, r, eoff, soff, etot, stot);
     if (!phase([&] {
             if (r != 0) return;
             sh.eds->take(etot); sh.seds->take(stot);

@@ -471,6 +471,12 @@ def test_column_batches_equal_the_single_call(ctx, K):
         else:
             assert ctx.msa_info()["n_cols"] > 0
     assert cut >= 25
+    # chains over more than two batches, through batches that are a single run: one common run, then one variant run,
+    # over all four (the alignments of test_multi_cpp_gpu.py::test_long_runs_make_chains_over_several_slabs)
+    for rows in ([b"ACGT" * 50] * 3, [b"A" * 200, b"C" * 200, b"A" * 100 + b"G" * 100]):
+        msa = b"".join(b">s%d\n%s\n" % (i, r) for i, r in enumerate(rows))
+        e, s, used = ctx.msa_transform_batched(msa, 0, 4)
+        assert (e, s) == o.msa(msa, 0) and used == 4
     # not an alignment the geometry walk accepts: one piece, the transform words the error
     import edsparser_amd
     with pytest.raises(edsparser_amd.EdsxError) as ei:

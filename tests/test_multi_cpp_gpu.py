@@ -65,7 +65,7 @@ def test_odd_files_and_short_leds_slabs_are_not_partitioned():
 @pytest.mark.parametrize("n", [2, 3, 5])
 def test_leds_slabs_stitched_between_standalone_runs(n):
     """Context length > 0: every slab boundary is recomputed between the nearest common runs of at least l columns on
-    either side (run_rank_leds).  Random alignments with sparse and dense variation, one-line and wrapped rows; cases
+    either side (run_rank, stitch_from_anchors).  Random alignments with sparse and dense variation, one-line and wrapped rows; cases
     whose slabs have no such runs fall back to one GPU - both kinds must occur and both equal the oracle."""
     m = _multi(n)
     rng = random.Random(300 + n)
