@@ -2,7 +2,8 @@
 
 One object per source under edsparser_amd/build/ (compiled in parallel, only when stale), then one link; three more
 libraries for the tests only (libedsx_smallstacks.so, libedsx_guard.so, libedsx_weakhash.so) relink the same objects
-with one source each compiled with other flags, and a fifth (libedsx_primitives.so) is one translation unit of the tests' own.
+with one source each compiled with other flags, and a fifth and a sixth (libedsx_primitives.so, libedsx_msagroup.so) are one
+translation unit of the tests' own each.
 """
 import os
 import subprocess
@@ -37,6 +38,11 @@ WEAKHASH_FLAGS = {"msa_device.hip": ["-DEDSX_MSA_HASH_BITS=1"]}
 # linked on its own (tests/hip/primitives_harness.hip, tests/test_primitives_gpu.py).  Never loaded by the product.
 PRIM_LIB = os.path.join(HERE, "libedsx_primitives.so")
 PRIM_SRC = os.path.join(HERE, "..", "tests", "hip", "primitives_harness.hip")
+# A sixth one, built the same way: plain C launchers around the wave64 grouping code of the MSA transform - the helpers of
+# csrc/msa_wave.hpp, fast_group of csrc/msa_fast_kernels.hpp and fused_group_run of csrc/msa_scan_kernels.hpp, called on
+# segments of the tests' own (tests/hip/msa_group_harness.hip, tests/test_msa_group_gpu.py).  Never loaded by the product.
+MSAGROUP_LIB = os.path.join(HERE, "libedsx_msagroup.so")
+MSAGROUP_SRC = os.path.join(HERE, "..", "tests", "hip", "msa_group_harness.hip")
 
 
 def _headers():
@@ -94,12 +100,13 @@ def build(force=False, verbose=False):
                 _compile(src, obj, EXTRA_FLAGS.get(name, []) + extra, verbose)
         if force or _newer(lib, tobjs):
             _link(tobjs, lib, verbose)
-    if os.path.exists(PRIM_SRC) and (force or _newer(PRIM_LIB, [PRIM_SRC] + [h for h in hdrs if h.endswith(".hpp")])):
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        cmd = [hipcc] + FLAGS + ["-I", CSRC, "-shared", PRIM_SRC, "-o", PRIM_LIB, "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        subprocess.run(cmd, check=True)
+    for src, lib in ((PRIM_SRC, PRIM_LIB), (MSAGROUP_SRC, MSAGROUP_LIB)):
+        if os.path.exists(src) and (force or _newer(lib, [src] + [h for h in hdrs if h.endswith(".hpp")])):
+            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+            cmd = [hipcc] + FLAGS + ["-I", CSRC, "-shared", src, "-o", lib, "-Wl,-rpath,/opt/rocm/lib"]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.run(cmd, check=True)
     return LIB
 
 
